@@ -17,6 +17,13 @@ Prints ONE JSON line on rank 0. `--gpus N` (N > 1) launched without WORLD_SIZE s
 itself (torch.distributed.run, one process per GPU, before this process touches a GPU); launched by
 torch.distributed.run, WORLD_SIZE must equal N. `--dry-run` exercises the rank plumbing only (gloo,
 no GPU work, value null): the CPU test of the launcher.
+
+A plain run sets up, warms up, times --steps steps and prints the line. `--full` adds what the
+headline figure does not need: the traceback / end-to-end pass (e2e_ms, gcups_fill_plus_traceback,
+pair 0's score of the fill workloads), the CPU baseline and, on N ranks, the batch's final gather
+of all scores. `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(dump_fill / dump_batch; N ranks: <name>_rank<r>.npy); the inputs are seeded, so two builds run
+with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -57,8 +64,14 @@ def parse():
     ap.add_argument("--size", type=int, default=32768)
     ap.add_argument("--pattern-len", type=int, default=0, help="headline/local: rows (default: --size)")
     ap.add_argument("--rows-per-lane", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the CPU baseline sample (default: full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the traceback / "
+                         "end-to-end pass, the CPU baseline and, on N ranks, the batch's final gather of all scores")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; large outputs as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--cpu-rows", type=int, default=0, help="--full: rows of the CPU baseline sample (default: full)")
     ap.add_argument("--batch-pipeline", type=int, default=1,
                     help="batch: overlap step k's traceback and result gather with step k+1's fill (two plan copies)")
     ap.add_argument("--shard-of", type=int, default=0,
@@ -71,7 +84,10 @@ def parse():
     ap.add_argument("--native", action="store_true",
                     help="batch: one process drives the C++ sa_align_batch over --gpus devices (host inputs, "
                          "per-device threads and plans, results gathered over RCCL); no torch.distributed")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _matrix_file(S: np.ndarray) -> str:
@@ -267,6 +283,59 @@ class Pipelined:
         self.pending = None
 
 
+DUMP_SEED = 20240531          # the samples of --dump-outputs are drawn from this seed, whatever the run
+DUMP_SAMPLE_BYTES = 48 << 20  # the sampled array's share of the 64 MB a dump may hold
+
+
+def _save(out_dir: str, name: str, arr: np.ndarray, rank: int, world: int) -> None:
+    assert arr.dtype in (np.float32, np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), arr)
+
+
+def _result_rows(res: np.ndarray) -> np.ndarray:
+    """sa_result records as a (pairs, 4) float64 array: score, aligned length, start in text, start in pattern."""
+    return np.stack([res[k].astype(np.float64) for k in ("score", "num_bytes", "start_text", "start_pattern")], axis=1)
+
+
+def dump_fill(out_dir: str, ch: Chunked, rank: int, world: int) -> None:
+    """--dump-outputs of the fill workloads: what the last fill left, the pair's DIRECTION matrix
+    (LEFT=0, DIAG=1, TOP=2, STOP=3; (pattern_len+1) x (text_len+1)), decoded through
+    sa_plan_fetch_directions. The matrix is too large to keep whole, so the dump holds its row sums
+    and column sums (every cell counts in both) and a seeded sample of whole rows."""
+    plan = ch.jobs[0].plan
+    n, m = plan.pairs[0][1], plan.pairs[0][3]
+    M = plan.directions(0, ch.s_fill.cuda_stream).reshape(m + 1, n + 1)
+    k = max(1, min(m + 1, DUMP_SAMPLE_BYTES // (4 * (n + 1))))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(m + 1, size=k, replace=False))
+    _save(out_dir, "directions_row_sums", M.sum(axis=1, dtype=np.int64).astype(np.float64), rank, world)
+    _save(out_dir, "directions_col_sums", M.sum(axis=0, dtype=np.int64).astype(np.float64), rank, world)
+    _save(out_dir, "directions_sample_rows", rows.astype(np.float64), rank, world)
+    _save(out_dir, "directions_sample", M[rows].astype(np.float32), rank, world)
+
+
+def dump_batch(out_dir: str, ch: Chunked, rank: int, world: int) -> None:
+    """--dump-outputs of the batch: every pair's result of the last step (score, aligned length, start
+    indices) and the aligned strings its traceback wrote, for a seeded sample of the rank's pairs
+    (letters as their byte values, zero-padded to text_len + pattern_len)."""
+    stream = ch.s_fill.cuda_stream  # (the device is idle: the caller has synchronised it)
+    res = np.concatenate([j.plan.results_array(stream) for j in ch.jobs])
+    _save(out_dir, "results", _result_rows(res), rank, world)
+    where = [(j, i) for j in ch.jobs for i in range(j.plan.num_pairs)]
+    k = min(len(where), 64)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(len(where), size=k, replace=False))
+    width = max(j.plan.pairs[i][1] + j.plan.pairs[i][3] for j, i in where)
+    at, ap = np.zeros((k, width), np.float32), np.zeros((k, width), np.float32)
+    for row, w in enumerate(pick):
+        j, i = where[w]
+        a, b = j.plan.alignment(i, stream)
+        at[row, :len(a)] = np.frombuffer(a.encode(), np.uint8)
+        ap[row, :len(b)] = np.frombuffer(b.encode(), np.uint8)
+    _save(out_dir, "aligned_sample_pairs", pick.astype(np.float64), rank, world)
+    _save(out_dir, "aligned_text_sample", at, rank, world)
+    _save(out_dir, "aligned_pattern_sample", ap, rank, world)
+
+
 def main_native(args) -> None:
     """--workload batch --native: each step is one sa_align_batch call (C ABI) aligning all 4096 pairs
     from host memory over devices 0..N-1 of this process: per device a thread that uploads its shard,
@@ -285,6 +354,9 @@ def main_native(args) -> None:
         res = engine.align_batch(0, texts, pats, S, 5, num_gpus=args.gpus, strings=False)
     elapsed = time.perf_counter() - t0
     stats = engine.batch_last_stats()
+    if args.dump_outputs:
+        rows = [[r[k] for k in ("score", "num_bytes", "start_text", "start_pattern")] for r in res]
+        _save(args.dump_outputs, "results", np.array(rows, dtype=np.float64), 0, 1)
     cells = npairs * L * L
     print(json.dumps({
         "metric": "GCUPS (DP cell updates/s), 4096 x 2048^2 DNA NW batch, C++ sa_align_batch end to end (config 5)",
@@ -511,25 +583,35 @@ def main():
     launch_ms = [a.elapsed_time(b) for a, b in evs]
     res = job.results()  # checks the abort flag of the last fill
 
-    # traceback / end-to-end, outside the timed region (headline: reported only); one untimed pass
-    # first, so the traceback kernels' first launch in the process (code object load) is not timed
-    if args.workload != "batch":
-        job.fill_and_traceback()
-    torch.cuda.synchronize(local)
-    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    job.fill_and_traceback((e0, e1))
-    e2.record(stream)
-    res = job.results()
-    # traceback: what runs after the last fill ends (with one chunk, the whole traceback)
-    fill_ms_e2e, tb_ms = e0.elapsed_time(e1), e1.elapsed_time(e2)
+    if args.dump_outputs:
+        if args.workload == "batch":
+            # (pipelined: the plan copy that ran the last step)
+            dump_batch(args.dump_outputs, pipe.sets[(pipe.k - 1) % 2] if pipe is not None else job, rank, world)
+        else:
+            dump_fill(args.dump_outputs, job, rank, world)
+
+    fill_ms_e2e = tb_ms = None
+    if args.full:
+        # traceback / end-to-end, outside the timed region (headline: reported only); one untimed pass
+        # first, so the traceback kernels' first launch in the process (code object load) is not timed
+        if args.workload != "batch":
+            job.fill_and_traceback()
+        torch.cuda.synchronize(local)
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        job.fill_and_traceback((e0, e1))
+        e2.record(stream)
+        res = job.results()
+        # traceback: what runs after the last fill ends (with one chunk, the whole traceback)
+        fill_ms_e2e, tb_ms = e0.elapsed_time(e1), e1.elapsed_time(e2)
 
     tmax = elapsed
-    scores = [int(x) for x in res["score"]]
+    # the scores are the traceback's: a plain run of a fill workload has none
+    scores = [int(x) for x in res["score"]] if args.full or args.workload == "batch" else []
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_device else "cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         tmax = float(tt.item())
-        if args.workload == "batch":
+        if args.full and args.workload == "batch":
             job.copy_results(gbuf)
             allres = distributed.gather_device(gbuf, npairs, world, rank)
             if rank == 0:
@@ -573,20 +655,21 @@ def main():
             "gcups_best_launch": round(cells_rank / (min(launch_ms) * 1e-3) / 1e9 * world, 3),
             "gcups_reference_convention": round(pairs_rank * (workload["text_len"] + 1) * (workload["pattern_len"] + 1)
                                                 / (min(launch_ms) * 1e-3) / 1e9 * world, 3),
-            "e2e_ms": {"fill": round(fill_ms_e2e, 4), "traceback": round(tb_ms, 4)},
-            # fill + traceback (strings included) of the same cells
-            "gcups_fill_plus_traceback": round(cells_total / ((fill_ms_e2e + tb_ms) * 1e-3) / 1e9, 3)
-            if fill_ms_e2e + tb_ms > 0 else None,
             "direction_bytes_physical_per_launch": info["mask_bytes"],
             "sample_result": {"pair0_score": scores[0] if scores else None, "pairs_per_gpu": pairs_rank},
         }
+        if args.full:
+            out["e2e_ms"] = {"fill": round(fill_ms_e2e, 4), "traceback": round(tb_ms, 4)}
+            # fill + traceback (strings included) of the same cells
+            out["gcups_fill_plus_traceback"] = (round(cells_total / ((fill_ms_e2e + tb_ms) * 1e-3) / 1e9, 3)
+                                                if fill_ms_e2e + tb_ms > 0 else None)
         if args.workload == "batch" and args.shard_of > 1:
             # one rank's step of an N-rank run, measured alone on one GPU: N ranks would finish the
             # 4096 pairs in about this step time (plus the 16-128 KiB RCCL gather, not measured here)
             out["shard_model"] = {"shard_of": args.shard_of, "pairs_this_rank": pairs_rank,
                                   "modelled_n_gpu_gcups": round(value * args.shard_of, 3),
                                   "note": "modelled, not measured on N GPUs: rank 0's shard on one GPU"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload == "batch":
                 # the batch is independent pairs: the CPU baseline is every core of this GPU's host
                 # share (OMP_NUM_THREADS, 16 on the GPU box) running the reference's fill at once, 64

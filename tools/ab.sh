@@ -15,7 +15,7 @@ mkdir -p gpurun_out
 for lib in $libs; do
   L=$PWD/build_exp/libsa_$lib.so; [ "$lib" = base ] && L=$PWD/sequence-alignment-gpu_amd/lib/libsa_hip.so
   for w in $wls; do
-    SA_HIP_LIB=$L timeout -k 10 200 python bench.py --workload $w --steps $steps --warmup 2 --no-cpu-baseline "$@" \
+    SA_HIP_LIB=$L timeout -k 10 200 python bench.py --workload $w --steps $steps --warmup 2 --full --no-cpu-baseline "$@" \
       > gpurun_out/ab_tmp.log 2>&1 || { tail -n 20 gpurun_out/ab_tmp.log; exit 1; }
     echo "== ${LABEL:-$lib} $w $(python tools/show_bench.py gpurun_out/ab_tmp.log)" | tee -a gpurun_out/ab.log
   done

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--no-cpu-baseline --steps 5 --warmup 1)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --no-cpu-baseline --steps 5 --warmup 1)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
     python3 "$ROOT/bench.py" "${ARGS[@]}" > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.err"
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- \

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prints the key fields of bench JSON lines found in the given log files."""
+"""Prints the key fields of bench JSON lines found in the given log files (e2e and f+tb: bench.py --full)."""
 import json
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One line per batch bench JSON (bench.py --workload batch [--shard-of N]): shard, plan, step and fill times."""
+"""One line per batch bench JSON (bench.py --full --workload batch [--shard-of N]): shard, plan, step and fill times."""
 import json
 import sys
 
