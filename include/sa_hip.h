@@ -164,7 +164,8 @@ enum {
     SA_FILL_STRIPS = 0,      /* one wave per strip (fill_kernel; chains hand rows off in LDS / granules) */
     SA_FILL_BAND = 1,        /* band fill: 128-row score strips feeding the 64-row strips (R = 1) */
     SA_FILL_PAIR = 2,        /* pair-packed lone strips: two pairs per wave (fill_pair_kernel) */
-    SA_FILL_PAIR_CHAIN = 3   /* pair-packed chains: a couple of pairs per workgroup, a wave per strip */
+    SA_FILL_PAIR_CHAIN = 3,  /* pair-packed chains: a couple of pairs per workgroup, a wave per strip */
+    SA_FILL_BAND3 = 4        /* band fill with 192-row bands (three rows per lane) feeding strip groups of three */
 };
 int sa_plan_fill_kind(const sa_plan *plan);
 /* Verification: synchronise `stream` and decode pair `index`'s direction bit-planes into the

@@ -203,6 +203,9 @@ struct Knobs {
                                     // feeding the 64-row strips, sa_fill.hip process_band) on / off
                                     // (1 also past kBandPersistRows*); default: on wherever it applies
                                     // (plan_create)
+    int band_r = 0;                 // SA_BAND_R: 2 / 3 force the bands' rows per lane (128-row bands and
+                                    // strip groups of W, or 192-row bands and strip groups of three)
+                                    // wherever that height applies; default: plan_create
     double handoff_timeout_s = 20;  // SA_HANDOFF_TIMEOUT_S: in-kernel hand-off give-up time
     int io_sleep = 4;               // SA_IO_SLEEP: I/O wave idle poll period (s_sleep units)
     int chain_lds_kb = 0;           // SA_CHAIN_LDS_KB: dynamic LDS per chain workgroup
@@ -238,6 +241,7 @@ const Knobs &knobs()
         if (const char *e = get("SA_WAVES_PER_GROUP")) v.waves_per_group = std::atoi(e);
         v.no_pair16 = get("SA_NO_PAIR16") != nullptr;
         if (const char *e = get("SA_BAND")) v.band = std::atoi(e) != 0 ? 1 : 0;
+        if (const char *e = get("SA_BAND_R")) v.band_r = std::atoi(e) == 3 ? 3 : 2;
         if (const char *e = get("SA_HANDOFF_TIMEOUT_S")) v.handoff_timeout_s = std::atof(e);
         if (const char *e = get("SA_IO_SLEEP")) v.io_sleep = std::max(0, std::atoi(e));
         if (const char *e = get("SA_CHAIN_LDS_KB")) v.chain_lds_kb = std::max(0, std::atoi(e));
@@ -321,6 +325,8 @@ struct sa_plan {
     bool chain_solo = false;  // one chain workgroup per CU (one compute wave per SIMD), see plan_create
     // band fill (R = 1 int8-profile chains): 128-row score strips ahead of the 64-row strips
     bool band = false;
+    int band_r = 2;      // rows per lane of the bands (3: 192-row bands, strip groups of three)
+    int strip_w = 1;     // strips per strip group of the band fill (W, or 3 under three-row bands)
     std::vector<StripDesc> bands;
     StripDesc *d_bands = nullptr;
     int num_cu = 0;
@@ -856,27 +862,38 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
         }
     }
     // the band fill (sa_fill.hip process_band): R = 1 chains with int8 text profiles (global, or local
-    // with g >= 0, which kArr8 implies), W even (a group boundary inside a pair must fall on a band
-    // boundary: every pair's first strip even), and the band groups plus the strip groups fit one
-    // workgroup per CU
+    // with g >= 0, which kArr8 implies), and the band groups plus the strip groups fit one workgroup per
+    // CU (or run as persistent workers, below). A band is BR rows per lane (64 BR rows), the strips below
+    // run in groups of SW, a multiple of BR, so that a group boundary inside a pair falls on a band
+    // boundary: every pair's first strip a multiple of BR.
+    //   BR = 2: 128-row bands, strip groups of W (W even);
+    //   BR = 3: 192-row bands, strip groups of three: every band feeds exactly one strip group (no
+    //           granule is written for nothing) and the chain has a third fewer hand-offs at 8 VALU per
+    //           band step instead of 6 (process_band3). DNA-sized alphabets reading
+    //           the four byte copies only (the kernels that exist); the default for plans whose groups
+    //           are all resident (32768^2: global +6.8 %, local +6.3 %, 8192^2 global +7.6 % in same-box
+    //           A/Bs, profiles/r07), with persistent workers behind SA_BAND_R=3 (not measured).
+    // A plan that fails the three-row conditions takes two-row bands, then the one-wave fill.
     {
-        bool band = knobs().band != 0 && pl->R == 1 && pl->sk == kArr8 && pl->chain && pl->W % 2 == 0;
-        for (const PairDesc &d : pl->pairs) band = band && (d.num_strips == 0 || d.first_strip % 2 == 0);
-        int64_t nb = 0;
-        for (const PairDesc &d : pl->pairs) nb += std::max(0, (d.num_strips + 1) / 2 - 1);
-        const int64_t stripGroups = ((int64_t)pl->strips.size() + pl->W - 1) / pl->W;
-        const int64_t bandGroups = (nb + pl->W - 1) / pl->W;
-        // every group in flight at once, or (persistent band and strip workgroups, FillArgs::band_wgs)
-        // chains up to kBandPersistRows rows: past them the fill is throughput-bound and the bands' work
-        // on top of the strips' costs more than their shorter ramp saves
         int64_t mmax = 0;
         for (const PairDesc &d : pl->pairs) mmax = std::max<int64_t>(mmax, (int64_t)d.pattern_len);
         const int64_t persistRows = knobs().band_rows > 0 ? knobs().band_rows : (A <= 4 ? kBandPersistRows : kBandPersistRowsWide);
-        band = band && nb > 0 &&
-               (stripGroups + bandGroups <= pl->num_cu || ((mmax <= persistRows || knobs().band == 1) && pl->num_cu >= 4));
-        if (band)
-        {
-            // bands b = 0 .. B-2 of each pair (B = ceil(strips / 2); the last band's bottom row feeds
+        const bool bandable = knobs().band != 0 && pl->R == 1 && pl->sk == kArr8 && pl->chain;
+        auto plan_bands = [&](int BR, int SW, bool residentOnly) {
+            bool band = bandable;
+            for (const PairDesc &d : pl->pairs) band = band && (d.num_strips == 0 || d.first_strip % BR == 0);
+            int64_t nb = 0;
+            for (const PairDesc &d : pl->pairs) nb += std::max(0, (d.num_strips + BR - 1) / BR - 1);
+            const int64_t stripGroups = ((int64_t)pl->strips.size() + SW - 1) / SW;
+            const int64_t bandGroups = (nb + pl->W - 1) / pl->W;
+            // every group in flight at once, or (persistent band and strip workgroups, FillArgs::band_wgs)
+            // chains up to kBandPersistRows rows: past them the fill is throughput-bound and the bands' work
+            // on top of the strips' costs more than their shorter ramp saves
+            const bool resident = stripGroups + bandGroups <= pl->num_cu;
+            band = band && nb > 0 &&
+                   (resident || (!residentOnly && (mmax <= persistRows || knobs().band == 1) && pl->num_cu >= 4));
+            if (!band) return false;
+            // bands b = 0 .. B-2 of each pair (B = ceil(strips / BR); the last band's bottom row feeds
             // nothing); every band publishes its bottom row to granules. The strips keep their planes;
             // a strip at a group start takes its feed from the granules of the band above, the others
             // from the strip above through the group's rings, and a group's last strip publishes nothing.
@@ -884,12 +901,12 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
             for (const PairDesc &d : pl->pairs)
             {
                 const uint64_t n = d.text_len;
-                const int B = (d.num_strips + 1) / 2;
+                const int B = (d.num_strips + BR - 1) / BR;
                 const int64_t fb = (int64_t)pl->bands.size();
                 for (int b = 0; b + 1 < B; ++b)
                 {
-                    StripDesc bd = pl->strips[d.first_strip + 2 * b];
-                    bd.row0 = 1 + b * 2 * kWave;
+                    StripDesc bd = pl->strips[d.first_strip + BR * b];
+                    bd.row0 = 1 + b * BR * kWave;
                     bd.flags = (b > 0 ? kHasPrev : 0) | kHasNext;
                     bd.mask_off = 0;
                     bd.bnd_in = b > 0 ? pl->bands.back().bnd_out : 0;
@@ -901,13 +918,20 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
                 {
                     StripDesc &sd = pl->strips[d.first_strip + k];
                     const int i = d.first_strip + k;
-                    if (k + 1 < d.num_strips && (i + 1) % pl->W == 0) sd.flags &= ~kHasNext;
+                    if (k + 1 < d.num_strips && (i + 1) % SW == 0) sd.flags &= ~kHasNext;
                     sd.bnd_out = 0;
-                    sd.bnd_in = (k > 0 && i % pl->W == 0) ? pl->bands[fb + k / 2 - 1].bnd_out : 0;
+                    sd.bnd_in = (k > 0 && i % SW == 0) ? pl->bands[fb + k / BR - 1].bnd_out : 0;
                 }
             }
             pl->band = true;
-        }
+            pl->band_r = BR;
+            pl->strip_w = SW;
+            return true;
+        };
+        // (kArr8A plans, sa_plan_fill's selector, have no three-row kernels)
+        const bool copy0 = knobs().align > (A > 4 ? 0 : 1);
+        const bool three = A <= 4 && !copy0 && pl->W >= 2 && knobs().band_r != 2;
+        if (!(three && plan_bands(3, 3, knobs().band_r != 3)) && pl->W % 2 == 0) plan_bands(2, pl->W, false);
     }
     {
         // one-wave chain fill: a second workgroup on a CU puts two compute waves on a SIMD, which
@@ -1159,6 +1183,7 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
         a.num_band_groups = 0;
         a.band_wgs = 0;
         a.pair_text_len = 0;
+        a.strip_w = 0;
         // SA_TIMELINE=<file>: debug dump of per-strip timestamps (s_memrealtime, 100 MHz)
         const char *tlPath = knobs().timeline;
         a.timeline = nullptr;
@@ -1197,6 +1222,9 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
         }
         if (pl->band)
         {
+            // (three-row bands: strip groups of three, the band groups keep W)
+            a.strip_w = pl->strip_w;
+            a.num_groups = (ns + pl->strip_w - 1) / pl->strip_w;
             // band groups on the first workgroups, strip groups on the rest, one workgroup per CU (the
             // LDS request is above half a CU's) and every group in flight at once (plan_create checked
             // that they fit): a strip group waits only for bands, which never wait for strips
@@ -1217,8 +1245,10 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
         }
         // chains of protein-sized alphabets read copy 0 of their text profiles (kArr8A, sa_fill.h)
         const int sk = pl->sk == kArr8 && pl->chain && knobs().align > (pl->A > 4 ? 0 : 1) ? kArr8A : pl->sk;
-        launch_fill(pl->R, a, pl->mode == SA_LOCAL, sk, grid, pl->sk == kPair && pl->chain ? pl->pairs[0].num_strips : W,
-                    pl->chain, st);
+        if (pl->band && pl->band_r == 3) launch_fill_band3(a, pl->mode == SA_LOCAL, grid, W, st);
+        else
+            launch_fill(pl->R, a, pl->mode == SA_LOCAL, sk, grid, pl->sk == kPair && pl->chain ? pl->pairs[0].num_strips : W,
+                        pl->chain, st);
         HIP_TRY(hipGetLastError());
         if (tlPath)
         {
@@ -1534,7 +1564,7 @@ int sa_plan_fill_kind(const sa_plan *pl)
 {
     if (!pl) return fail(SA_ERR_INVALID, "sa_plan_fill_kind: null plan");
     if (pl->sk == kPair) return pl->chain ? SA_FILL_PAIR_CHAIN : SA_FILL_PAIR;
-    return pl->band ? SA_FILL_BAND : SA_FILL_STRIPS;
+    return pl->band ? (pl->band_r == 3 ? SA_FILL_BAND3 : SA_FILL_BAND) : SA_FILL_STRIPS;
 }
 
 const void *sa_plan_device_results(const sa_plan *pl) { return pl ? (const void *)pl->d_results : nullptr; }

@@ -29,6 +29,9 @@ struct FillArgs {
     uint32_t epoch;
     int32_t key_bits;
     int32_t key_rowbits;        // local best-cell key: H | ~row (key_rowbits) | ~col (key_rowbits)
+    int32_t strip_w;            // three-row bands (fill_kernel_band3): strips per strip group (3); the band
+                                // groups keep the launch's W. (In the alignment hole before timeout_ticks:
+                                // every other field keeps its offset, the kernels their argument loads.)
     uint64_t timeout_ticks;     // hand-off give-up time in s_memrealtime ticks (100 MHz)
     uint64_t *timeline;         // debug (SA_TIMELINE): per strip {start, fed, end, hw id}, or null
     int32_t io_sleep;           // I/O wave idle poll period, in units of s_sleep 1 (64 clocks)
@@ -83,6 +86,9 @@ void launch_fill_r(const FillArgs &a, bool local, int sk, int grid, int W, bool 
 // R = 1 kArr8 chains read through copy 0 (kArr8A; fill_r1a.hip, a code object of its own so that the
 // DNA kernels' code and placement stay as they are)
 void launch_fill_align(const FillArgs &a, bool local, int grid, int W, hipStream_t st);
+// R = 1 kArr8 chains of DNA-sized alphabets with three-row bands (192-row bands feeding strip groups
+// of three; fill_r1b.hip, a code object of its own for the same reason)
+void launch_fill_band3(const FillArgs &a, bool local, int grid, int W, hipStream_t st);
 #ifndef SA_FILL_R
 extern template void launch_fill_r<1>(const FillArgs &, bool, int, int, int, bool, hipStream_t);
 extern template void launch_fill_r<2>(const FillArgs &, bool, int, int, int, bool, hipStream_t);

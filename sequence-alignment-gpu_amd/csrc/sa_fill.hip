@@ -359,6 +359,18 @@ struct BandRegs {
 };
 template <bool LOCAL, bool HN, bool HP>
 __device__ __forceinline__ void band_steps_asm(BandRegs &r);
+// The three-row bands' score steps (band_block(rows = 3)): the same rotation with no free phase, five
+// registers carry state across bodies
+struct Band3Regs {
+    int Q, diag, F0, F1, F2;     // feed queue, up of the previous step (row 0's diag), rows 0 / 1 / 2
+    int TA[4], TB[4], TC[4];     // text-profile words of the body for rows 0 / 1 / 2 (4 steps each)
+    int g;
+    int pfaddr, pf;
+    int pubaddr, pubtag, ctag, msb;
+    uint64_t bad;
+};
+template <bool LOCAL, bool HN, bool HP>
+__device__ __forceinline__ void band3_steps_asm(Band3Regs &r);
 #if defined(SA_EXPERIMENT) && defined(SA_EXP_FILL_INC)
 #include SA_EXP_FILL_INC  // tools/gen_fill_asm.py variants (timing ablations)
 #else
@@ -1255,6 +1267,247 @@ __device__ __forceinline__ void process_band(const FillArgs &a, const StripLds &
     }
 }
 
+// THREE-ROW BANDS (fill_r1b.hip): a 192-row score strip, lane k owns rows row0 + 3k .. 3k + 2 at
+// column s - k + 1. The chain of bands has a third of the one-wave chain's hand-offs (170 instead of
+// 253 with two rows at 32768 rows) at 8 VALU per step instead of 6, and the 64-row strips below run in
+// groups of three (FillArgs::strip_w), so every band's granules feed exactly one strip group and none
+// is written for nothing. The feed, publish, back-pressure and code-load protocol is process_band's,
+// with three text-profile loads per body; a kernel of its own (fill_kernel_band3), so that the two-row
+// kernels' code stays what it is (the band loop is layout-sensitive).
+template <bool LOCAL, bool HP, bool HN, bool TOUCH>
+__device__ __forceinline__ void process_band3(const FillArgs &a, const StripLds &L, lds_int *rings, int idx, int w, int lane)
+{
+    constexpr int U = 16;
+    constexpr int BR = 3;
+    typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
+    idx = uniform(idx);
+    StripDesc sd = a.bands[idx];
+    sd.pair = uniform(sd.pair);
+    sd.row0 = uniform(sd.row0);
+    sd.nsteps = uniform(sd.nsteps);
+    PairDesc pd = a.pairs[sd.pair];
+    pd.text_len = uniform64(pd.text_len);
+    pd.pattern_len = uniform64(pd.pattern_len);
+    pd.pattern_off = uniform64(pd.pattern_off);
+    pd.code_off = uniform64(pd.code_off);
+    pd.code_len = uniform64(pd.code_len);
+    const int n = (int)pd.text_len, m = (int)pd.pattern_len;
+    // the lane's three rows: byte copy k % 4 of each row letter's text profile (process_strip, kArr8)
+    uint32_t coff[BR];
+    sfor<BR>([&](auto Rc) {
+        constexpr int rho = decltype(Rc)::value;
+        const int i = sd.row0 + BR * lane + rho;
+        int c = i <= m ? (int)a.pattern[pd.pattern_off + i - 1] : 0;
+        c = min(max(c, 0), a.A - 1);
+        coff[rho] = (uint32_t)(((uint64_t)c * 4 + (lane & 3)) * pd.code_len + kPad - (lane & ~3));
+    });
+    const __amdgpu_buffer_rsrc_t crsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(a.codes + pd.code_off), 0, 0x7fffffff, kBufRsrcWord3);
+    struct Codes3 {
+        int r[BR][4];
+    };
+    auto load_codes = [&](int s0, Codes3 &d) __attribute__((always_inline)) {
+        sfor<BR>([&](auto Rc) {
+            constexpr int rho = decltype(Rc)::value;
+            const i32x4u v = __builtin_amdgcn_raw_buffer_load_b128(crsrc, coff[rho], s0, 0);
+            d.r[rho][0] = v.x;
+            d.r[rho][1] = v.y;
+            d.r[rho][2] = v.z;
+            d.r[rho][3] = v.w;
+        });
+    };
+    lds_int *rin = (lds_int *)(rings + w * kRing);
+    lds_int *rout = (lds_int *)(rings + (w + 1) * kRing);
+    lds_int *consIn = (lds_int *)&L.cons[w];
+    lds_int *consOut = (lds_int *)&L.cons[w + 1];
+    lds_int *drainOut = (lds_int *)&L.drain[w + 1];
+    lds_int *sink = rings + (L.nwaves + 1) * kRing;
+    lds_int *pubBase = lane >= kWave - U ? rout + (lane - (kWave - U)) : sink + lane;
+    const uint32_t rinLaneOff = lds_off(rin + lane);
+    int Q = 0, diag = 0, F0 = 0, F1 = 0, F2 = 0;  // column-0 boundary
+    int pfVal = 0;
+    bool pfTagged = false;
+    uint64_t pfBad = 0;
+    // the feed protocol of process_band: read after step BAND_PF_STEP, tags checked at the body end
+    auto feed = [&](int base, bool full) __attribute__((always_inline)) {
+        if constexpr (!HP)
+        {
+            asm volatile("v_mov_b32 %0, 0" : "=v"(Q));  // row 0 boundary (opaque: see process_strip)
+            return;
+        }
+        else
+        {
+            const int tag = ring_tag(base + 1);
+            uint64_t need = (1ull << U) - 1;
+            if (!full)
+            {
+                int cnt;
+                asm("s_sub_i32 %1, %2, %3\n\ts_max_i32 %1, %1, 0\n\ts_min_i32 %1, %1, %4\n\ts_bfm_b64 %0, %1, 0"
+                    : "=s"(need), "=&s"(cnt)
+                    : "s"(n), "s"(base), "i"(U)
+                    : "scc");
+            }
+            int x = pfTagged ? pfVal : pfVal ^ tag;
+            const uint64_t bad = pfTagged ? pfBad : (ballot(x < 0) & ((1ull << U) - 1));
+            pfTagged = false;
+            if (__builtin_expect((full ? bad : (bad & need)) != 0, 0))
+            {
+                uint64_t t0 = 0;
+                for (uint32_t spin = 1;; ++spin)
+                {
+                    if (spin > 16) __builtin_amdgcn_s_sleep(1);
+                    x = ds_read_sync(rin + lane + ring_slot(base + 1)) ^ tag;
+                    if ((ballot(x < 0) & need) == 0) break;
+                    if ((spin & 255) == 0)
+                    {
+                        if (t0 == 0) t0 = now_ticks();
+                        else if (!keep_waiting(a, t0, lane)) break;
+                    }
+                }
+            }
+            Q = x;
+        }
+    };
+    const uint32_t consAddr = lane == 0 ? lds_off(consIn) : lds_off(sink + lane);
+    auto consumed = [&](int upto) __attribute__((always_inline)) {
+        if constexpr (HP) asm volatile("ds_write_b32 %0, %1" ::"v"(consAddr), "v"(upto));
+    };
+    // ring slots are reused once the drain or I/O wave and the next band have read them (process_band)
+    const bool nextReads = !(w + 1 < L.nwaves && idx + 1 < a.num_bands) || (uniform(a.bands[idx + 1].flags) & kHasPrev);
+    int consKnown = 0;
+    auto pub_wait = [&](int s0) __attribute__((always_inline)) {
+        if constexpr (HN)
+        {
+            const int cLast = s0 - 64 + U;
+            if (__builtin_expect(cLast - kRing > consKnown, 0))
+            {
+                const uint64_t t0 = now_ticks();
+                for (uint32_t spin = 1;; ++spin)
+                {
+                    consKnown = uniform(lds_ld(drainOut));
+                    if (nextReads) consKnown = min(consKnown, uniform(lds_ld(consOut)));
+                    if (cLast - kRing <= consKnown) break;
+                    __builtin_amdgcn_s_sleep(1);
+                    if ((spin & 255) == 0 && !keep_waiting(a, t0, lane)) break;
+                }
+            }
+        }
+    };
+    int msbv;
+    asm volatile("v_mov_b32 %0, 0x80000000" : "=v"(msbv));
+    const uint64_t tStart = a.timeline ? now_ticks() : 0;
+    Codes3 TA, TB, TC, TD;
+    load_codes(0, TA);
+    // TA's loads before TB's, as in the steady quads (process_band)
+    __builtin_amdgcn_sched_barrier(0);
+    load_codes(U, TB);
+    if constexpr (HP)
+    {
+        int c = 1 + lane;
+        asm volatile("" : "+v"(c));
+        pfVal = lds_ld(rin + ring_slot(c));
+    }
+    feed(0, false);
+    const uint64_t tFed = a.timeline ? now_ticks() : 0;
+    const uint64_t cFed = a.timeline ? __builtin_amdgcn_s_memtime() : 0;
+    uint32_t quadPf = 0;
+    auto set_quad = [&](int s0q) __attribute__((always_inline)) {
+        quadPf = 4u * (uint32_t)s0q + 4u * (U + 64);
+        asm volatile("" : "+s"(quadPf));
+    };
+    auto body = [&](auto pos, auto full, int s0, Codes3 &T, Codes3 &Tn) __attribute__((always_inline)) {
+        constexpr int POS = decltype(pos)::value;
+        constexpr bool FULL = decltype(full)::value;
+        const int s1 = s0 + U;
+        load_codes(s0 + 2 * U, Tn);
+        Band3Regs r;
+        r.Q = Q;
+        r.diag = diag;
+        r.F0 = F0;
+        r.F1 = F1;
+        r.F2 = F2;
+        sfor<4>([&](auto Wc) {
+            constexpr int q = decltype(Wc)::value;
+            r.TA[q] = T.r[0][q];
+            r.TB[q] = T.r[1][q];
+            r.TC[q] = T.r[2][q];
+        });
+        r.g = a.gap;
+        r.pfaddr = HP ? (int)(rinLaneOff + ((quadPf + 4u * U * POS) & (4u * kRingMask))) : 0;
+        r.ctag = ring_tag_raw(s1 + 1);
+        r.msb = msbv;
+        if constexpr (POS == 0) pub_wait(s0 + 3 * U);
+        else if constexpr (POS == 2) pub_wait(s0 + U);
+        r.pubaddr = (int)lds_off(pubBase + (s0 & kRingMask));
+        r.pubtag = ring_tag_raw(s0 - 63);
+        band3_steps_asm<LOCAL, HN, HP>(r);
+        if constexpr (HP)
+        {
+            pfVal = r.pf;
+            pfBad = r.bad;
+            pfTagged = true;
+        }
+        Q = r.Q;
+        diag = r.diag;
+        F0 = r.F0;
+        F1 = r.F1;
+        F2 = r.F2;
+        feed(s1, FULL);
+        if constexpr (POS == 3) consumed(s1 + U);
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    using P2 = std::integral_constant<int, 2>;
+    using P3 = std::integral_constant<int, 3>;
+    const int nSteps = sd.nsteps;  // a multiple of 2U
+    int s0 = 0;
+    // the L1 touch of the text codes, as process_band's (global, DNA-sized alphabets)
+    constexpr int kTouch = TOUCH && !LOCAL ? 6 : 0;
+    int touch[BR] = {0, 0, 0};
+    auto phase = [&](auto full, auto touchOn, int end) __attribute__((always_inline)) {
+        for (; s0 + 2 * U < end; s0 += 4 * U)
+        {
+            if constexpr (decltype(touchOn)::value)
+            {
+                asm volatile("" ::"v"(touch[0]), "v"(touch[1]), "v"(touch[2]));
+                sfor<BR>([&](auto Rc) {
+                    constexpr int rho = decltype(Rc)::value;
+                    touch[rho] = __builtin_amdgcn_raw_buffer_load_b32(crsrc, coff[rho], min(s0 + kTouch * U, nSteps + U), 0);
+                });
+            }
+            set_quad(s0);
+            body(P0{}, full, s0, TA, TC);
+            body(P1{}, full, s0 + U, TB, TD);
+            body(P2{}, full, s0 + 2 * U, TC, TA);
+            body(P3{}, full, s0 + 3 * U, TD, TB);
+        }
+        if (s0 < end)
+        {
+            set_quad(s0 - 2 * U);
+            body(P2{}, full, s0, TA, TC);
+            body(P3{}, full, s0 + U, TB, TD);
+            s0 += 2 * U;
+            TA = TC;
+            TB = TD;
+        }
+    };
+    // bodies whose next feed lies in columns 1..n (every feed lane needed and delivered), then the rest
+    phase(std::true_type{}, std::integral_constant<bool, (kTouch > 0)>{}, min(nSteps, max(0, (n - U) / (2 * U) * (2 * U))));
+    phase(std::false_type{}, std::integral_constant<bool, (kTouch > 0)>{}, nSteps);
+    if (a.timeline && lane == 0)
+    {
+        // band records follow the strips' (kTimelineWords words each)
+        uint64_t *tl = a.timeline + kTimelineWords * ((size_t)a.num_strips + idx);
+        tl[0] = tStart;
+        tl[1] = tFed;
+        tl[2] = now_ticks();
+        tl[4] = cFed;
+        tl[5] = __builtin_amdgcn_s_memtime();
+        tl[3] = ((uint64_t)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (15 << 11)) << 32) |
+                (uint32_t)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // pair-packed fill (global mode, lone strips, DNA-sized alphabets): two independent pairs of the same
 // shape in the two 16-bit halves of every register
@@ -1823,6 +2076,71 @@ __global__ __launch_bounds__(kWave * (kMaxWaves + 1 + kDrainWaves)) void fill_ke
     }
 }
 
+// The R = 1 kArr8 chain fill with three-row bands (fill_r1b.hip): fill_kernel's group loop with
+// process_band3 in the band workgroups and strip groups of FillArgs::strip_w = 3 strips in the others,
+// whose wave 3 is the I/O wave and whose last two waves idle. A kernel of its own rather than a
+// parameter of fill_kernel: threading the strip width through that kernel changed the instruction
+// order of every instance of it.
+template <bool LOCAL, bool TOUCH>
+__global__ __launch_bounds__(kWave * (kMaxWaves + 1 + kDrainWaves)) void fill_kernel_band3(FillArgs a)
+{
+    extern __shared__ int lds_dyn[];
+    GroupHdr &H = *reinterpret_cast<GroupHdr *>(lds_dyn);
+    lds_int *rings = (lds_int *)(lds_dyn + sizeof(GroupHdr) / 4);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int w = uniform((int)(threadIdx.x / kWave));
+    const bool bandRole = (int)blockIdx.x < a.band_wgs;
+    // band workgroups: W bands, the I/O wave, the drain waves; strip workgroups: strip_w <= W + kDrainWaves
+    // strips and the I/O wave
+    const int W = bandRole ? (int)(blockDim.x / kWave) - 1 - kDrainWaves : a.strip_w;
+    const StripDesc *strips = bandRole ? a.bands : a.strips;
+    const int nstrips = bandRole ? a.num_bands : a.num_strips;
+    const int ngroups = bandRole ? a.num_band_groups : a.num_groups;
+    uint32_t *qhead = bandRole ? &a.ctrl->band_head : &a.ctrl->queue_head;
+    while (true)
+    {
+        __syncthreads();  // every wave is done with the previous group's rings
+        if (threadIdx.x == 0)
+        {
+            const bool aborted = __hip_atomic_load(&a.ctrl->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+            H.group = aborted ? ngroups : (int)atomicAdd(qhead, 1u);
+            H.nwaves = W;
+        }
+        if (threadIdx.x <= kMaxWaves) H.cons[threadIdx.x] = H.drain[threadIdx.x] = 0;
+        // tags: a zeroed ring matches no column (ring_tag)
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        for (int e = 4 * threadIdx.x; e < (W + 1) * kRing; e += 4 * blockDim.x)
+            *(__attribute__((address_space(3))) i32x4 *)(rings + e) = i32x4{0, 0, 0, 0};
+        __syncthreads();
+        const int grp = uniform(H.group);
+        if (grp >= ngroups) break;
+        if (w == W) io_wave(a, strips, nstrips, H.cons, H.drain, rings, grp, W, lane);
+        else if (w > W)
+        {
+            if (bandRole) drain_wave(a, H.drain, rings, grp, W, lane, w - W - 1);
+        }
+        else
+        {
+            const int idx = grp * W + w;
+            if (idx >= nstrips) continue;
+            const int f = uniform(strips[idx].flags) & (kHasPrev | kHasNext);
+            const StripLds L{H.S, H.cons, H.nwaves, H.drain};
+            if (bandRole)
+            {
+                // (priority over the helper waves and every band publishing: as fill_kernel)
+                __builtin_amdgcn_s_setprio(2);
+                if (f & kHasPrev) process_band3<LOCAL, true, true, TOUCH>(a, L, rings, idx, w, lane);
+                else process_band3<LOCAL, false, true, TOUCH>(a, L, rings, idx, w, lane);
+                __builtin_amdgcn_s_setprio(0);
+            }
+            else if (f == (kHasPrev | kHasNext)) process_strip<1, LOCAL, kArr8, true, true>(a, L, rings, idx, w, lane);
+            else if (f == kHasPrev) process_strip<1, LOCAL, kArr8, true, false>(a, L, rings, idx, w, lane);
+            else if (f == kHasNext) process_strip<1, LOCAL, kArr8, false, true>(a, L, rings, idx, w, lane);
+            else process_strip<1, LOCAL, kArr8, false, false>(a, L, rings, idx, w, lane);
+        }
+    }
+}
+
 // Fill launches, one translation unit per strip height R (fill_r<R>.hip instantiates
 // launch_fill_r<R>; the main unit only declares them), so the 48 fill kernels compile in parallel.
 template <int R, bool LOCAL, int SK>
@@ -1896,7 +2214,22 @@ void launch_fill_r(const FillArgs &a, bool local, int sk, int grid, int W, bool 
     }
 }
 
-#ifdef SA_FILL_ALIGN
+#if defined(SA_FILL_TU_BAND3)
+// fill_r1b.hip: the kArr8 chain kernels with three-row bands (global of DNA-sized alphabets with the
+// code touch, as the two-row launch chooses; local without)
+void launch_fill_band3(const FillArgs &a, bool local, int grid, int W, hipStream_t st)
+{
+    const size_t lds = std::max(group_lds_bytes(W), (size_t)a.chain_lds);
+    const dim3 block(kWave * (W + 1 + kDrainWaves));
+    auto go = [&](auto kern) {
+        if (lds > 65536)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(grid), block, lds, st, a);
+    };
+    if (local) go(&fill_kernel_band3<true, false>);
+    else go(&fill_kernel_band3<false, true>);
+}
+#elif defined(SA_FILL_ALIGN)
 // fill_r1a.hip: the kArr8A chain kernels (bands and strips read copy 0 of the text profiles)
 void launch_fill_align(const FillArgs &a, bool local, int grid, int W, hipStream_t st)
 {

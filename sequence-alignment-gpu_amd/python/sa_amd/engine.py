@@ -18,7 +18,7 @@ STATUS = {0: "SA_OK", 1: "SA_ERR_INVALID", 2: "SA_ERR_NOMEM", 3: "SA_ERR_HIP", 4
           5: "SA_ERR_TIMEOUT"}
 
 # sa_plan_fill_kind (include/sa_hip.h SA_FILL_*)
-FILL_KINDS = {0: "strips", 1: "band", 2: "pair", 3: "pair_chain"}
+FILL_KINDS = {0: "strips", 1: "band", 2: "pair", 3: "pair_chain", 4: "band3"}
 
 # Symbols declared in include/sa_hip.h (checked by tests/test_capi.py).
 EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill", "sa_plan_traceback",

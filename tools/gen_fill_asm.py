@@ -135,10 +135,11 @@ def block(local: bool, hn: bool, hp: bool, half: int) -> str:
     return "\\n\\t".join(out)
 
 
-def band_block(local: bool, hn: bool, hp: bool) -> str:
-    """U = 16 steps of a band score strip: two rows per lane (rows 2k, 2k+1 of a 128-row band), the
-    recurrence alone (no direction bits). Eight registers P0..P7 rotate with period 8: at step k the
-    register of phase p is P[(k - p) % 8], and the phases are
+def band_block(local: bool, hn: bool, hp: bool, rows: int = 2) -> str:
+    """U = 16 steps of a band score strip: `rows` rows per lane (rows rows * k .. rows * k + rows - 1 of
+    a 64 * rows-row band; two: 128-row bands, three: 192-row bands), the recurrence alone (no direction
+    bits). Eight registers P0..P7 rotate with period 8: at step k the register of phase p is
+    P[(k - p) % 8], and the phases are (two rows)
         p = 0  F1 of step k-2 (dead): the queue shift Qn is written here (lane 63 keeps F1, HN)
         p = 1  Q (the feed queue); up = wave_shr:1(F1 of step k-1) in place (lane 0 keeps the feed)
         p = 2  up of step k-1 (= diag of row 0): D0 = diag0 + S0 in place, then F0 = max3(D0, F0', up)
@@ -148,18 +149,27 @@ def band_block(local: bool, hn: bool, hp: bool) -> str:
         p = 4, 5  free
     (local: H = X - g saturated at 0, one v_sub_u32 with clamp after each max3; X >= 0). The up-DPP
     stands three instructions behind the max3 (and the subtract) that wrote F1, the queue shift two;
-    a body of 16 steps returns every value to its register. 6 VALU per step (8 local)."""
+    a body of 16 steps returns every value to its register. 6 VALU per step (8 local).
+    Three rows fill the free phases: row j >= 1 has its F at phase 8 - 2 (rows - j) and its F of the
+    previous step one phase later, so the bottom row always ends at phases 6 / 7 / 0:
+        p = 4  D1 = F0 of step k-1 + S1 (the register held F0 of step k-2, dead), F1 = max3(D1, F1', F0)
+        p = 5  F1 of step k-1 (left of row 1, diag of row 2)
+        p = 6  D2 = F1 of step k-1 + S2 (held F1 of step k-2, dead), F2 = max3(D2, F2', F1)
+        p = 7  F2 of step k-1 (the DPP's source); p = 0: F2 of step k-2, takes Qn
+    8 VALU per step (11 local); the up-DPP stands four instructions behind the write of F2."""
+    assert rows in (2, 3)
     P = [f"%[p{i}]" for i in range(8)]
-    T0 = [f"%[ta{i}]" for i in range(4)]
-    T1 = [f"%[tb{i}]" for i in range(4)]
+    TW = [[f"%[t{'abc'[j]}{i}]" for i in range(4)] for j in range(rows)]
+    fp = [2] + [8 - 2 * (rows - j) for j in range(1, rows)]  # phase of row j's F
     G, T = "%[g]", "%[t0]"
     PF, BAD, PFA, CTAG, PADDR, PTAG, MSB = "%[pf]", "%[bad]", "%[pfa]", "%[ctag]", "%[paddr]", "%[ptag]", "%[msb]"
-    out = ["s_nop 1"]  # the compiler's last writes of Q / F1 may stand right before
+    out = ["s_nop 1"]  # the compiler's last writes of Q / the bottom row's F may stand right before
     for k in range(U):
         ph = lambda p: P[(k - p) % 8]
         sel = f"dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_{k & 3}"
-        out.append(f"v_add_u32_sdwa {ph(2)}, {ph(2)}, sext({T0[k >> 2]}) {sel}")
-        out.append(f"v_add_u32_sdwa {ph(6)}, {ph(3)}, sext({T1[k >> 2]}) {sel}")
+        out.append(f"v_add_u32_sdwa {ph(2)}, {ph(2)}, sext({TW[0][k >> 2]}) {sel}")
+        for j in range(1, rows):
+            out.append(f"v_add_u32_sdwa {ph(fp[j])}, {ph(fp[j - 1] + 1)}, sext({TW[j][k >> 2]}) {sel}")
         if hp and k == BAND_PF_STEP:
             out.append(f"ds_read_b32 {PF}, {PFA}")
         bc = "" if hn else " bound_ctrl:1"
@@ -168,28 +178,36 @@ def band_block(local: bool, hn: bool, hp: bool) -> str:
         out.append(f"v_max3_i32 {ph(2)}, {ph(2)}, {ph(3)}, {ph(1)}")
         if local:
             out.append(f"v_sub_u32_e64 {ph(2)}, {ph(2)}, {G} clamp")
-        out.append(f"v_max3_i32 {ph(6)}, {ph(6)}, {ph(7)}, {ph(2)}")
-        if local:
-            out.append(f"v_sub_u32_e64 {ph(6)}, {ph(6)}, {G} clamp")
+        for j in range(1, rows):
+            out.append(f"v_max3_i32 {ph(fp[j])}, {ph(fp[j])}, {ph(fp[j] + 1)}, {ph(fp[j - 1])}")
+            if local:
+                out.append(f"v_sub_u32_e64 {ph(fp[j])}, {ph(fp[j])}, {G} clamp")
     if hp:
         out.append("s_waitcnt lgkmcnt(0)")
         out.append(f"v_bitop3_b32 {PF}, {PF}, {CTAG}, {MSB} bitop3:0xd2")
         out.append(f"v_cmp_gt_i32_e64 {BAD}, 0, {PF}")
         out.append(f"s_and_b64 {BAD}, {BAD}, 0xffff")
     if hn:
-        # k = 16: phase 0 = P0 holds F1 of step 14, phase 1 = P7 the queue: one more shift gives lanes
-        # 48..63 = F1 of steps s0-1 .. s0+14 (as the one-wave bodies publish)
+        # k = 16: phase 0 = P0 holds the bottom row's F of step 14, phase 1 = P7 the queue: one more
+        # shift gives lanes 48..63 = the bottom row of steps s0-1 .. s0+14 (as the one-wave bodies publish)
         out.append(f"v_mov_b32_dpp {P[0]}, {P[7]} wave_shl:1 row_mask:0xf bank_mask:0xf")
         out.append(f"v_bitop3_b32 {T}, {P[0]}, {PTAG}, {MSB} bitop3:0xf2")
         out.append(f"ds_write_b32 {PADDR}, {T}")
     return "\\n\\t".join(out)
 
 
-def band_operands(local: bool, hn: bool, hp: bool):
-    # at entry / exit: Q = P7 (phase 1), diag0 = P6 (phase 2), F0 = P5 (phase 3), F1 = P1 (phase 7)
-    outs = ['[p7] "+v"(r.Q)', '[p6] "+v"(r.diag)', '[p5] "+v"(r.F0)', '[p1] "+v"(r.F1)',
-            '[p0] "=&v"(x0)', '[p2] "=&v"(x2)', '[p3] "=&v"(x3)', '[p4] "=&v"(x4)', '[t0] "=&v"(t0)']
+def band_operands(local: bool, hn: bool, hp: bool, rows: int = 2):
+    # at entry / exit: Q = P7 (phase 1), diag0 = P6 (phase 2), F0 = P5 (phase 3), and the previous
+    # step's F of row j >= 1 at phase 9 - 2 (rows - j): two rows F1 = P1; three rows F1 = P3, F2 = P1
+    if rows == 2:
+        outs = ['[p7] "+v"(r.Q)', '[p6] "+v"(r.diag)', '[p5] "+v"(r.F0)', '[p1] "+v"(r.F1)',
+                '[p0] "=&v"(x0)', '[p2] "=&v"(x2)', '[p3] "=&v"(x3)', '[p4] "=&v"(x4)', '[t0] "=&v"(t0)']
+    else:
+        outs = ['[p7] "+v"(r.Q)', '[p6] "+v"(r.diag)', '[p5] "+v"(r.F0)', '[p3] "+v"(r.F1)', '[p1] "+v"(r.F2)',
+                '[p0] "=&v"(x0)', '[p2] "=&v"(x2)', '[p4] "=&v"(x4)', '[t0] "=&v"(t0)']
     ins = [f'[ta{i}] "v"(r.TA[{i}])' for i in range(4)] + [f'[tb{i}] "v"(r.TB[{i}])' for i in range(4)]
+    if rows == 3:
+        ins += [f'[tc{i}] "v"(r.TC[{i}])' for i in range(4)]
     if local:
         ins += ['[g] "s"(r.g)']
     if hp:
@@ -315,6 +333,25 @@ def main():
         lines.append("    (void)tx; (void)tb;")
         lines.append("}")
         lines.append("")
+    lines += [
+        "// band3_steps_asm<LOCAL, HN, HP>(r): the score-wave steps of the three-row bands (192-row bands,",
+        "// three rows per lane; band_block(rows = 3) in the generator).",
+    ]
+    for local in (False, True):
+        for hn in (False, True):
+            for hp in (False, True):
+                body = band_block(local, hn, hp, 3)
+                outs, ins = band_operands(local, hn, hp, 3)
+                lines.append(f"template <> __device__ __forceinline__ void band3_steps_asm<{str(local).lower()}, "
+                             f"{str(hn).lower()}, {str(hp).lower()}>(Band3Regs &r)")
+                lines.append("{")
+                lines.append("    int x0, x2, x4, t0;")
+                lines.append(f"    asm volatile(\"{body}\"")
+                lines.append("        : " + ", ".join(outs))
+                lines.append("        : " + ", ".join(ins) + (" : \"scc\");" if hp else ");"))
+                lines.append("    (void)x0; (void)x2; (void)x4; (void)t0;")
+                lines.append("}")
+                lines.append("")
     open(OUT, "w").write("\n".join(lines))
     print("wrote", OUT)
 

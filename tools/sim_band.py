@@ -5,7 +5,9 @@ lanes, drives it the way process_band does (16-step bodies, text-profile bytes, 
 publish shift), and compares every band's published bottom row with a direct DP of the same rows:
 global in the shifted domain F = H + g(i + j) (alignSequenceCPU.cpp:259-273), local H
 (:175-190). Catches register-rotation and hazard-order mistakes in tools/gen_fill_asm.py without a
-GPU.   python3 tools/sim_band.py
+GPU.   python3 tools/sim_band.py [--rows 3]
+(--rows 3: the three-row bands' band3_steps_asm, 192-row bands; tests/test_band3_asm.py drives the
+same functions over more cases)
 """
 import os
 import re
@@ -17,9 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "sequence-alignment-gpu_amd", "csrc", "sa_fill_steps.inc")
 
 
-def band_asm(local: bool, hn: bool, hp: bool) -> list:
+def band_asm(local: bool, hn: bool, hp: bool, rows: int = 2) -> list:
     src = open(INC).read()
-    key = f"band_steps_asm<{str(local).lower()}, {str(hn).lower()}, {str(hp).lower()}>(BandRegs &r)"
+    fn, regs = ("band_steps_asm", "BandRegs") if rows == 2 else ("band3_steps_asm", "Band3Regs")
+    key = f"{fn}<{str(local).lower()}, {str(hn).lower()}, {str(hp).lower()}>({regs} &r)"
     i = src.index(key)
     body = src[src.index('asm volatile("', i) + len('asm volatile("'):]
     body = body[: body.index('"\n')]
@@ -82,24 +85,29 @@ def dp(mode, t, p, S, g):
     return F
 
 
-def bands(mode, t, p, S, g):
-    """Published bottom rows of bands 0 .. B-2 (process_band), columns 1..n."""
+# registers of the state at a body's entry / exit (gen_fill_asm.py band_operands): Q, diag, F0, F1 (, F2)
+STATE = {2: ("%[p7]", "%[p6]", "%[p5]", "%[p1]"), 3: ("%[p7]", "%[p6]", "%[p5]", "%[p3]", "%[p1]")}
+TEMPS = {2: ("%[p0]", "%[p2]", "%[p3]", "%[p4]", "%[t0]"), 3: ("%[p0]", "%[p2]", "%[p4]", "%[t0]")}
+
+
+def bands(mode, t, p, S, g, rows=2, fed=True):
+    """Published bottom rows of bands 0 .. B-2 (process_band), columns 1..n; `rows` rows per lane.
+    fed = False: every band runs without a feed (HP = false, row 0 boundary above it), as a pair's
+    first band does; its published row is then the DP of its own rows alone."""
     m, n = len(p), len(t)
     off = 2 * g if mode == 0 else g
     U = 16
     nsteps = ((n + 64) + 2 * U - 1) // (2 * U) * (2 * U)
     lane = np.arange(64)
-    B = (m + 127) // 128
+    H = 64 * rows  # band height
+    B = (m + H - 1) // H
     feed_row = None  # the band above's bottom row, columns 1..n
     out = []
     for b in range(B - 1):
-        hp = b > 0
-        lines = band_asm(mode == 1, True, hp)
-        rows = [128 * b + 2 * lane, 128 * b + 2 * lane + 1]  # 0-based pattern index of the lane's rows
-        Q = np.zeros(64, np.int64)
-        diag = np.zeros(64, np.int64)
-        F0 = np.zeros(64, np.int64)
-        F1 = np.zeros(64, np.int64)
+        hp = fed and b > 0
+        lines = band_asm(mode == 1, True, hp, rows)
+        rowi = [H * b + rows * lane + j for j in range(rows)]  # 0-based pattern index of the lane's rows
+        st = [np.zeros(64, np.int64) for _ in STATE[rows]]  # Q, diag, F0, F1 (, F2): column-0 boundary
         pub = np.zeros(n + 1, np.int64)
 
         def feed(s):  # lanes 0..15: columns s+1 .. s+16 of the band above (0 past n / row 0)
@@ -110,48 +118,51 @@ def bands(mode, t, p, S, g):
                 q[:U][ok] = feed_row[c[ok]]
             return q
 
-        Q = feed(0)
+        st[0] = feed(0)
         for s0 in range(0, nsteps, U):
-            regs = {"%[p7]": Q, "%[p6]": diag, "%[p5]": F0, "%[p1]": F1}
-            for nm in ("%[p0]", "%[p2]", "%[p3]", "%[p4]", "%[t0]"):
+            regs = dict(zip(STATE[rows], st))
+            for nm in TEMPS[rows]:
                 regs[nm] = np.full(64, 12345, np.int64)  # garbage
-            for r, pre in ((0, "ta"), (1, "tb")):
+            for r, pre in list(enumerate(("ta", "tb", "tc")))[:rows]:
                 for w in range(4):
                     word = np.zeros(64, np.int64)
                     for byte in range(4):
                         x = s0 + 4 * w + byte - lane  # text index of lane k at this step
                         ok = (x >= 0) & (x < n)
                         sc = np.zeros(64, np.int64)
-                        sc[ok] = S[p[rows[r][ok]], t[x[ok]]] + off
+                        sc[ok] = S[p[rowi[r][ok]], t[x[ok]]] + off
                         word |= (sc & 0xFF) << (8 * byte)
                     regs[f"%[{pre}{w}]"] = word
             run(lines, regs, g)
-            Q, diag, F0, F1 = regs["%[p7]"], regs["%[p6]"], regs["%[p5]"], regs["%[p1]"]
+            st = [regs[nm] for nm in STATE[rows]]
             # publish: lanes 48..63 of p0 = bottom row of columns s0-63 .. s0-48
             v = regs["%[p0]"]
             for l in range(48, 64):
                 c = s0 - 63 + (l - 48)
                 if 1 <= c <= n:
                     pub[c] = v[l]
-            Q = feed(s0 + U)
+            st[0] = feed(s0 + U)
         out.append(pub)
         feed_row = pub
     return out
 
 
 def main():
+    rows = 3 if sys.argv[1:] == ["--rows", "3"] else 2
+    H = 64 * rows
     from_path = os.path.join(ROOT, "sequence-alignment-gpu_amd", "python")
     sys.path.insert(0, from_path)
     from sa_amd import synthetic
     S = synthetic.blast_matrix()
     bad = 0
-    for mode, n, m, g in ((0, 150, 384, 5), (0, 97, 300, 0), (0, 120, 257, -2), (1, 150, 384, 5), (1, 90, 300, 0)):
+    for mode, n, m, g in ((0, 150, 3 * H, 5), (0, 97, 300 * rows // 2, 0), (0, 120, 2 * H + 1, -2), (1, 150, 3 * H, 5),
+                          (1, 90, 300 * rows // 2, 0)):
         t = synthetic.random_sequence(11 + n, n, 4)
         p = synthetic.mutate(t, 12 + m, 4, m)
         F = dp(mode, t, p, S, g)
-        got = bands(mode, t, p, S, g)
+        got = bands(mode, t, p, S, g, rows)
         for b, row in enumerate(got):
-            r = 128 * (b + 1)
+            r = H * (b + 1)
             d = int((row[1:] != F[r, 1:]).sum())
             if d:
                 bad += 1

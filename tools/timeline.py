@@ -121,12 +121,21 @@ def main():
     W = int(os.environ.get("SA_WAVES_PER_GROUP", "4"))
     ns = args.pairs * ((args.m + 64 * args.R - 1) // (64 * args.R))
     t0 = int(tl[:, 0].astype(np.int64).min())
-    rec = {"n": args.n, "m": args.m, "R": args.R, "W": W, "pairs": args.pairs, "strips": ns}
-    rec.update(summarize(tl[:ns], args.n, W, t0))
+    # three-row bands (SA_BAND_R, or the plan's default): strip groups of three, band groups of W
+    kind = b.plan.info()["fill_kernel"]
+    SW = 3 if kind == "band3" else W
+    rec = {"n": args.n, "m": args.m, "R": args.R, "W": W, "pairs": args.pairs, "strips": ns, "fill_kernel": kind,
+           "strip_group": SW}
+    rec.update(summarize(tl[:ns], args.n, SW, t0))
     if len(tl) > ns:
         # band fill: the band records follow the strips' (one pair's chain)
         nb = (len(tl) - ns) // args.pairs
         rec["bands"] = summarize(tl[ns:ns + nb], args.n, W, t0)
+        rec["band_rows_per_lane"] = 3 if kind == "band3" else 2
+        # hand-off lags on the critical path: every band after the first starts one lag after the band
+        # above it, and the last strip group one lag after the last band
+        rec["handoffs"] = nb
+        rec["last_strip_after_last_band_us"] = round(rec["last_end_us"] - rec["bands"]["last_end_us"], 2)
     prog = tl[:ns, 6:16].astype(np.int64)
     iop = tl[:ns, 16:26].astype(np.int64)
     if prog[:, 1].any():
@@ -138,7 +147,7 @@ def main():
         kk = np.arange(1, len(prog))
         okr = (prog[1:, 1:9] > 0).all(axis=1) & (prog[:-1, 1:9] > 0).all(axis=1)
         lagq = (prog[1:, 1:9] - prog[:-1, 1:9]) * 10.0  # ns, lag of strip k behind k-1 at checkpoints 1..8
-        for nm, sel in (("in_group", (kk % W) != 0), ("cross_group", (kk % W) == 0)):
+        for nm, sel in (("in_group", (kk % SW) != 0), ("cross_group", (kk % SW) == 0)):
             L = lagq[sel & okr]
             rec[f"lag_ns_by_checkpoint_{nm}"] = [round(float(x), 1) for x in L.mean(axis=0)]
         rec["progress_lag_ns_first_strips"] = [[round(float(x), 1) for x in r] for r in pl[:6]]
@@ -148,7 +157,7 @@ def main():
         rec["ns_per_step_by_segment_every32"] = [[k] + [round(float(x), 1) for x in seg[k]] for k in range(0, len(seg), 32)]
         # I/O wave: time ring[0] of group g got column 4096q minus the time the group's first strip
         # reached column 4096q (negative: the feed was there first, the strip was the bottleneck)
-        gi = [k for k in range(W, len(prog), W) if iop[k, 1] > 0]
+        gi = [k for k in range(SW, len(prog), SW) if iop[k, 1] > 0]
         rec["io_ahead_us_every8groups"] = [[k] + [round(float(prog[k, q] - iop[k, q]) * 0.01, 1) for q in range(1, 9) if iop[k, q] > 0 and prog[k, q] > 0] for k in gi[::8]]
         mt = tl[:ns, 26:36].astype(np.int64)
         segc = np.diff(mt[:, ok], axis=1) / 4096.0
@@ -160,9 +169,9 @@ def main():
         rec["slow_paths_mean_per_strip"] = {nm: round(float(sc[1:, i].mean()), 1) for i, nm in
                                             enumerate(("feed_slow", "feed_spins", "pub_slow", "pub_spins",
                                                        "feed_slow_past_4096", "feed_spins_past_4096"))}
-        rec["feed_slow_by_wave_in_group"] = [round(float(sc[w::W, 0].mean()), 1) for w in range(W)]
-        rec["feed_slow_past_4096_by_wave_in_group"] = [round(float(sc[w::W, 4].mean()), 1) for w in range(W)]
-        rec["feed_spins_past_4096_by_wave_in_group"] = [round(float(sc[w::W, 5].mean()), 1) for w in range(W)]
+        rec["feed_slow_by_wave_in_group"] = [round(float(sc[w::SW, 0].mean()), 1) for w in range(SW)]
+        rec["feed_slow_past_4096_by_wave_in_group"] = [round(float(sc[w::SW, 4].mean()), 1) for w in range(SW)]
+        rec["feed_spins_past_4096_by_wave_in_group"] = [round(float(sc[w::SW, 5].mean()), 1) for w in range(SW)]
     print(json.dumps(rec))
     b.close()
 
