@@ -10,6 +10,8 @@
 //   tracebacks                        traceBackNW :64-114, traceBackSW :10-62
 // Kernels: the DP fill (sa_fill.hip, one translation unit per strip height), the traceback walk
 // and expansion (sa_walk.hip), and encode_text_kernel / selftest_kernel here.
+// What a plan runs is decided in sa_plan.cpp (make_plan: host-only, no HIP); this file validates,
+// plans, allocates and uploads, and launches what the plan says.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +25,7 @@
 #include "sa_fill.h"
 #include "sa_hip.h"
 #include "sa_layout.h"
+#include "sa_plan.h"
 #include "sa_walk.h"
 #include "sa_wave.h"
 
@@ -192,81 +195,6 @@ namespace {
         if (e_ != hipSuccess) return fail(SA_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
 
-// Environment knobs, read once per process (the first time the engine needs one) and never again:
-// every field is a tuning or debugging switch; the defaults are the measured best settings.
-struct Knobs {
-    bool debug_sync = false;        // SA_DEBUG_SYNC: synchronise and check after every launch
-    int rows_per_lane = 0;          // SA_ROWS_PER_LANE: force R (1..32)
-    int waves_per_group = 0;        // SA_WAVES_PER_GROUP: force W (1..4)
-    bool no_pair16 = false;         // SA_NO_PAIR16: disable the pair-packed batch fill
-    int band = -1;                  // SA_BAND: 1 / 0 force the band fill (128-row score strips
-                                    // feeding the 64-row strips, sa_fill.hip process_band) on / off
-                                    // (1 also past kBandPersistRows*); default: on wherever it applies
-                                    // (plan_create)
-    int band_r = 0;                 // SA_BAND_R: 2 / 3 force the bands' rows per lane (128-row bands and
-                                    // strip groups of W, or 192-row bands and strip groups of three)
-                                    // wherever that height applies; default: plan_create
-    double handoff_timeout_s = 20;  // SA_HANDOFF_TIMEOUT_S: in-kernel hand-off give-up time
-    int io_sleep = 4;               // SA_IO_SLEEP: I/O wave idle poll period (s_sleep units)
-    int chain_lds_kb = 0;           // SA_CHAIN_LDS_KB: dynamic LDS per chain workgroup
-    const char *timeline = nullptr; // SA_TIMELINE=<file>: per-strip fill timestamps
-    const char *tb_timing = nullptr;// SA_TB_TIMING=<file>: per-pair traceback timestamps
-    const char *tb_table_timing = nullptr;  // SA_TB_TABLE_TIMING=<file>: per-strip table kernel stamps
-    bool tb_generic = false;        // SA_TB_GENERIC: row walk without the unrolled strip code
-    bool tb_stager = true;          // SA_TB_STAGER=0: the row walker stages every strip itself
-    bool tb_tables = true;          // SA_TB_TABLES=0: no table traceback (every pair walks sequentially)
-    int tb_rounds = 0;              // SA_TB_ROUNDS: rounds of tables (default: plan_traceback)
-    bool tb_strict = false;         // SA_TB_STRICT: no sequential walk after the table traceback
-                                    // (tests: a pair it left keeps a stale head and fails its check)
-    int max_cus = 0;                // SA_MAX_CUS: plan as if the device had at most this many CUs (tests)
-    int chain_per_cu = 0;           // SA_CHAIN_PER_CU: 1 / 2 chain workgroups per CU (default: plan_create)
-    int64_t band_rows = 0;          // SA_BAND_ROWS: band fill up to this many rows past resident
-                                    // capacity (default kBandPersistRows*)
-    int pair_chain_r = 0;           // SA_PAIR_CHAIN_R: rows per lane of small batches' pair-packed chains (4 / 8)
-    int tb_cap = 0;                 // SA_TB_CAP: column-walk waves at most (0: one per pair)
-    bool tb_wide = true;            // SA_TB_WIDE=0: strip tables always 512 threads per strip
-    bool stage_kernel = true;       // SA_STAGE_KERNEL=0: one-shot calls stage through DMA copies
-    int align = 1;                  // SA_ALIGN=0: chains of alphabets larger than 4 read the four
-                                    // byte copies of their text profiles (kArr8) instead of copy 0
-                                    // shifted in registers (kArr8A); 2: every alphabet (experiments)
-};
-
-const Knobs &knobs()
-{
-    static const Knobs k = [] {
-        Knobs v;
-        auto get = [](const char *name) -> const char * { return std::getenv(name); };
-        v.debug_sync = get("SA_DEBUG_SYNC") != nullptr;
-        if (const char *e = get("SA_ROWS_PER_LANE")) v.rows_per_lane = std::atoi(e);
-        if (const char *e = get("SA_WAVES_PER_GROUP")) v.waves_per_group = std::atoi(e);
-        v.no_pair16 = get("SA_NO_PAIR16") != nullptr;
-        if (const char *e = get("SA_BAND")) v.band = std::atoi(e) != 0 ? 1 : 0;
-        if (const char *e = get("SA_BAND_R")) v.band_r = std::atoi(e) == 3 ? 3 : 2;
-        if (const char *e = get("SA_HANDOFF_TIMEOUT_S")) v.handoff_timeout_s = std::atof(e);
-        if (const char *e = get("SA_IO_SLEEP")) v.io_sleep = std::max(0, std::atoi(e));
-        if (const char *e = get("SA_CHAIN_LDS_KB")) v.chain_lds_kb = std::max(0, std::atoi(e));
-        v.timeline = get("SA_TIMELINE");
-        v.tb_timing = get("SA_TB_TIMING");
-        v.tb_table_timing = get("SA_TB_TABLE_TIMING");
-        v.tb_generic = get("SA_TB_GENERIC") != nullptr;
-        if (const char *e = get("SA_TB_STAGER")) v.tb_stager = std::atoi(e) != 0;
-        if (const char *e = get("SA_TB_TABLES")) v.tb_tables = std::atoi(e) != 0;
-        v.tb_strict = get("SA_TB_STRICT") != nullptr;
-        if (const char *e = get("SA_TB_ROUNDS")) v.tb_rounds = std::max(0, std::atoi(e));
-        if (const char *e = get("SA_MAX_CUS")) v.max_cus = std::max(0, std::atoi(e));
-        if (const char *e = get("SA_CHAIN_PER_CU")) v.chain_per_cu = std::min(2, std::max(0, std::atoi(e)));
-        if (const char *e = get("SA_BAND_ROWS")) v.band_rows = std::max(0LL, std::atoll(e));
-        if (const char *e = get("SA_PAIR_CHAIN_R")) v.pair_chain_r = std::atoi(e) == 4 ? 4 : 8;
-        if (const char *e = get("SA_TB_CAP")) v.tb_cap = std::max(0, std::atoi(e));
-        if (const char *e = get("SA_TB_WIDE")) v.tb_wide = std::atoi(e) != 0;
-        if (const char *e = get("SA_STAGE_KERNEL")) v.stage_kernel = std::atoi(e) != 0;
-        if (const char *e = get("SA_ALIGN")) v.align = std::min(2, std::max(0, std::atoi(e)));
-        return v;
-    }();
-    return k;
-}
-
-// SA_DEBUG_SYNC=1: synchronise and check after every launch (names the failing kernel).
 // Makes `device` current for a scope and restores the caller's device on every return path.
 struct DeviceGuard {
     int prev = -1;
@@ -291,6 +219,7 @@ struct DevFree {
 template <typename T>
 using DevPtr = std::unique_ptr<T, DevFree>;
 
+// SA_DEBUG_SYNC=1: synchronise and check after every launch (names the failing kernel).
 int debug_sync(hipStream_t st, const char *what)
 {
     if (!knobs().debug_sync) return SA_OK;
@@ -298,6 +227,14 @@ int debug_sync(hipStream_t st, const char *what)
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return fail(SA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     std::fprintf(stderr, "[sa debug] %s ok\n", what);
+    return SA_OK;
+}
+
+// What a fill's control word reports, read back after the fill of `epoch`.
+int check_control(const Control &ctrl, uint32_t epoch)
+{
+    if (ctrl.bad_input == epoch) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+    if (ctrl.abort_flag) return fail(SA_ERR_TIMEOUT, "fill aborted: a strip hand-off timed out");
     return SA_OK;
 }
 
@@ -317,28 +254,14 @@ int dmalloc(T **p, size_t bytes)
 
 }  // namespace
 
-struct sa_plan {
+// A plan (sa_plan.h: everything decided on the host) and its device state.
+struct sa_plan : Plan {
     int device = 0;
-    int mode = 0, A = 0, gap = 0, R = 0, U = 0, W = 1, key_bits = 12, key_rowbits = 21;
-    int sk = 0;          // ScoreKind of the fill
-    bool chain = false;  // some pair has more than one strip
-    bool chain_solo = false;  // one chain workgroup per CU (one compute wave per SIMD), see plan_create
-    // band fill (R = 1 int8-profile chains): 128-row score strips ahead of the 64-row strips
-    bool band = false;
-    int band_r = 2;      // rows per lane of the bands (3: 192-row bands, strip groups of three)
-    int strip_w = 1;     // strips per strip group of the band fill (W, or 3 under three-row bands)
-    std::vector<StripDesc> bands;
-    StripDesc *d_bands = nullptr;
-    int num_cu = 0;
-    std::vector<PairDesc> pairs;
-    std::vector<StripDesc> strips;
-    char alphabet[33] = {0};
     uint32_t epoch = 0;
     uint32_t *epoch_src = nullptr;  // workspace plans draw epochs from their DeviceCtx (see there)
     hipStream_t own = nullptr;
-    // device
     PairDesc *d_pairs = nullptr;
-    StripDesc *d_strips = nullptr;
+    StripDesc *d_strips = nullptr, *d_bands = nullptr;
     int32_t *d_prof = nullptr, *d_table = nullptr;
     int32_t *d_codes = nullptr;
     uint32_t *d_masks = nullptr;
@@ -347,20 +270,16 @@ struct sa_plan {
     Control *d_ctrl = nullptr;
     int32_t *d_rec = nullptr;  // traceback records (sa_walk.h)
     TbHead *d_heads = nullptr;
-    // table traceback (sa_walk.h TbArgs; R = 1 plans with a pair of kTbMinStrips strips or more)
-    std::vector<TbGroup> tb_groups;
-    std::vector<int32_t> tb_pg;  // [np + 1] first group of each pair
-    int64_t tb_slots = 0;        // strip tables (the strips of pairs with groups)
+    // table traceback (sa_walk.h TbArgs)
     TbGroup *d_tbgroups = nullptr;
     int32_t *d_tbpg = nullptr, *d_tbl = nullptr, *d_gtbl = nullptr, *d_gent = nullptr, *d_tbflag = nullptr, *d_win = nullptr;
     int32_t *d_tbstart = nullptr, *d_sent = nullptr, *d_sdelta = nullptr, *d_send = nullptr, *d_pend = nullptr;
     int64_t *d_csum = nullptr;  // expansion: per-chunk sums (pairs of more than kChunkRecs records)
     uint64_t *d_cflag = nullptr;  // expansion: per-chunk epoch flags (ExpandArgs::chunk_flags)
-    int64_t max_recs = 1;       // records per pair at most (row walk: pattern rows, column walk: text columns)
     char *d_out_text = nullptr, *d_out_pattern = nullptr;
     sa_result *d_results = nullptr;
     const int8_t *d_text_in = nullptr, *d_pattern_in = nullptr;
-    uint64_t bytes_total = 0, bytes_masks = 0, out_bytes = 0;
+    uint64_t bytes_total = 0;
     bool filled = false;
     bool borrowed = false;  // device buffers and stream belong to a DeviceCtx workspace (sa_align_pair)
     // workspace plans: the uploaded region [pairs .. inputs .. ctrl] and the downloaded region
@@ -369,84 +288,9 @@ struct sa_plan {
     size_t up_bytes = 0, dn_bytes = 0;
     int8_t *d_ws_text = nullptr, *d_ws_pattern = nullptr;
     bool ctrl_ready = false;  // the control word was uploaded zeroed (no memset before the next fill)
-    std::vector<int32_t> h_prof, h_table;  // host copies the (asynchronous) uploads read from
 };
 
 namespace {
-
-// Whether the pairs can run pair-packed (fill_pair_kernel / fill_pair_chain_kernel), whatever R:
-// global, an even number of pairs of one shape, a DNA-sized alphabet, every S + 2g in [0, 255] and
-// every shifted-domain value within u16 (65534 at most: chains mark unpublished LDS entries with
-// 0xffffffff, see sa_fill.hip)
-bool pair_packable(const sa_params *P, const sa_pair *pairs, int64_t np)
-{
-    const int A = P->alphabet_size;
-    const int64_t g = P->gap_penalty;
-    if (P->mode != SA_GLOBAL || np < 2 || np % 2 != 0 || A > 4 || g <= 0 || knobs().no_pair16) return false;
-    int64_t smaxp = 0;
-    for (int e = 0; e < A * A; ++e)
-    {
-        const int64_t v = P->score_matrix[e] + 2 * g;
-        if (v < 0 || v > 255) return false;
-        smaxp = std::max(smaxp, v);
-    }
-    for (int64_t p = 0; p < np; ++p)
-        if (pairs[p].text_len != pairs[0].text_len || pairs[p].pattern_len != pairs[0].pattern_len)
-            return false;
-    const uint64_t n = pairs[0].text_len, m = pairs[0].pattern_len;
-    return n > 0 && m > 0 && (uint64_t)smaxp * std::min(n, m) <= 65534;
-}
-
-int choose_R(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu)
-{
-    int R = P->rows_per_lane;
-    if (knobs().rows_per_lane) R = knobs().rows_per_lane;
-    if (R == 1 || R == 2 || R == 4 || R == 8 || R == 16 || R == 32) return R;
-    uint64_t mmax = 0;
-    for (int64_t p = 0; p < np; ++p) mmax = std::max<uint64_t>(mmax, pairs[p].pattern_len);
-    if (np >= 256)
-    {
-        // many independent pairs: one strip per pair where possible (no hand-offs at all); local
-        // mode keeps 3 registers per row (H, G, best key) and stops at 16 rows per lane, where
-        // its working set still fits the register file
-        const int rmax = P->mode == SA_LOCAL ? 16 : 32;
-        int r = 1;
-        while (r < rmax && (uint64_t)kWave * r < mmax) r <<= 1;
-        if (pair_packable(P, pairs, np))
-        {
-            // size the plan to the GPU: a couple of pairs is one wave per strip, and a batch with
-            // fewer waves than SIMDs (a shard of the batch on one of N GPUs) leaves SIMDs idle, its
-            // time set by one wave's n + 64 steps of R rows. Strips of 8 rows per lane chained in LDS
-            // (fill_pair_chain_kernel) split each couple over up to kPairChainMax waves. Measured on
-            // config 5's shards (profiles/r06/shard_sweep_v1.log): 1024 pairs 0.86 ms at R = 8 against
-            // 1.22 at 16 and 1.24 at 32; 512 pairs 0.52 / 0.73 / 1.19; 2048 pairs (one wave per SIMD
-            // at R = 32) 1.44 at 32 against 1.50 at 8 and 1.82 at 16: chains of two R = 16 strips never
-            // pay, so the choice is one strip per pair or R = 8 chains.
-            const int64_t simds = 4 * (int64_t)std::max(1, num_cu);
-            const int rc = knobs().pair_chain_r > 0 ? knobs().pair_chain_r : 8;
-            const int64_t stripsC = (int64_t)((mmax + kWave * rc - 1) / (kWave * rc));
-            if ((np / 2) * (int64_t)((mmax + kWave * r - 1) / (kWave * r)) < simds && r > rc && stripsC <= kPairChainMax)
-                r = rc;
-        }
-        return r;
-    }
-    // few long pairs: the shortest strips keep the wavefront deepest (one row per lane)
-    return 1;
-}
-
-// Waves per workgroup (strips per group). Chains of strips (pairs taller than one strip) hand
-// their rows off through LDS inside a group; single-strip pairs gain nothing from grouping.
-// band fill with persistent workers up to this many rows (DNA-sized alphabets / larger ones); past
-// them the one-wave fill with one workgroup per CU is ahead (profiles/r05/ab_chain_per_cu_v0.log, ab_chain_solo_v1.log)
-constexpr int64_t kBandPersistRows = 90112, kBandPersistRowsWide = 65536;
-
-int choose_W(const std::vector<PairDesc> &pairs)
-{
-    const int w = knobs().waves_per_group;
-    if (w >= 1 && w <= kMaxWaves) return w;
-    (void)pairs;
-    return 4;
-}
 
 void launch_fill(int R, const FillArgs &a, bool local, int sk, int grid, int W, bool chain, hipStream_t st)
 {
@@ -478,13 +322,6 @@ void free_plan(sa_plan *p)
     if (p->own) (void)hipStreamDestroy(p->own);
     (void)hipSetDevice(cur);
     delete p;
-}
-
-int bitlen(uint64_t v)
-{
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
 }
 
 // Compute units of `device`, cached (hipGetDeviceProperties costs milliseconds per call).
@@ -723,267 +560,26 @@ namespace {
 int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device, DeviceCtx *ws,
                 const OneShotInputs *in, sa_plan **out)
 {
-    if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix)
-        return fail(SA_ERR_INVALID, "sa_plan_create: null argument");
+    if (!out) return fail(SA_ERR_INVALID, "sa_plan_create: null argument");
     *out = nullptr;
-    const int A = P->alphabet_size;
-    if (A < 1 || A > 32) return fail(SA_ERR_INVALID, "alphabet_size must be 1..32");
-    if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL) return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL or SA_LOCAL");
-    // any int gap penalty, as the reference's CLI (std::stoi, utilities.cpp:188-199) and its fill
-    // (alignSequenceCPU.cpp:175-176, 259-260) take it; the range bound below rejects what int32 cannot hold
-    const int64_t g = P->gap_penalty;
-    int64_t smax = INT32_MIN, smin = INT32_MAX, sabs = 0;
-    for (int e = 0; e < A * A; ++e)
-    {
-        smax = std::max<int64_t>(smax, P->score_matrix[e]);
-        smin = std::min<int64_t>(smin, P->score_matrix[e]);
-        sabs = std::max<int64_t>(sabs, std::llabs((long long)P->score_matrix[e]));
-    }
-    // numeric limits of the engine: every intermediate fits in int32, local keys fit.
-    uint64_t hmax_local = 0, lmax = 0;
-    for (int64_t p = 0; p < np; ++p)
-    {
-        const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
-        if (n >= (1u << 24) - 1 || m >= (1u << 24) - 1)
-            return fail(SA_ERR_UNSUPPORTED, "sequence longer than 2^24-2 letters");
-        lmax = std::max(lmax, std::max(n, m));
-        const uint64_t span = n + m;
-        const uint64_t bound = ((uint64_t)sabs + (uint64_t)std::llabs(g)) * span + (uint64_t)std::llabs(g) * span;
-        if (bound >= (1ull << 30)) return fail(SA_ERR_UNSUPPORTED, "scores may exceed the int32 range");
-        const uint64_t h = g >= 0 ? (uint64_t)std::max<int64_t>(smax, 0) * std::min(n, m)
-                                  : ((uint64_t)sabs + (uint64_t)(-g)) * span;
-        hmax_local = std::max(hmax_local, h);
-    }
-    // local best-cell keys: H | ~row | ~col in 64 bits, row / column fields sized for the longest
-    // sequence; the in-kernel block key (H << key_bits) + step must stay inside int32
-    const int key_rowbits = std::max(1, bitlen(lmax + 1));
-    if (P->mode == SA_LOCAL && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * key_rowbits))
-        return fail(SA_ERR_UNSUPPORTED, "local scores may exceed the best-cell key range");
-
-    sa_plan *pl = new sa_plan();
+    std::unique_ptr<sa_plan> fresh(new sa_plan());
+    std::string err;
+    if (int rc = make_plan(P, pairs, np, device_cus(device), knobs(), fresh.get(), &err)) return fail(rc, err);
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    // (from here every return releases what the plan owns: nothing of a workspace's arena)
+    std::unique_ptr<sa_plan, void (*)(sa_plan *)> hold(fresh.release(), free_plan);
+    sa_plan *pl = hold.get();
     pl->device = device;
-    pl->mode = P->mode;
-    pl->A = A;
-    pl->gap = (int)g;
-    pl->R = choose_R(P, pairs, np, knobs().max_cus > 0 ? std::min(device_cus(device), knobs().max_cus) : device_cus(device));
-    pl->U = (16 / pl->R) > 4 ? 16 / pl->R : 4;
-    pl->key_bits = std::min(12, std::max(4, 30 - bitlen(hmax_local)));
-    pl->key_rowbits = key_rowbits;
-    // the tables hold S + 2g (global, shifted domain) or S + g (local), see run_body
-    const int64_t off2 = P->mode == SA_GLOBAL ? 2 * g : g;
-    bool fits8 = true;
-    for (int e = 0; e < A * A; ++e)
-    {
-        const int64_t v = P->score_matrix[e] + off2;
-        if (v < -128 || v > 127) fits8 = false;
-    }
-    // kArr8's hand-scheduled bodies keep the direction differences in bytes (sa_fill_steps.inc): every
-    // |M - D|, |left - up| is at most 2 (|S| + 2|g|) (global, shifted domain: every boundary is 0 and
-    // adjacent cells differ by at most max(S + 2g, 0)) or 2 (|S| + |g|) + |g| (local, g >= 0), below
-    // 4 (max|S| + |g|). Local with g < 0 has no such bound: H(i, 1) grows like -g * i next to the
-    // column-0 zeros, so M - D at column 1 (and row 1) leaves the byte range.
-    const bool byte_diffs = 4 * (sabs + std::llabs(g)) <= 127 && !(P->mode == SA_LOCAL && g < 0);
-    if (pl->R == 1) pl->sk = fits8 && byte_diffs ? kArr8 : kArr;
-    else pl->sk = (A <= 4 && fits8) ? kProf : kTable;
-    if (P->alphabet) std::memcpy(pl->alphabet, P->alphabet, std::min<size_t>(A + 1, 33));
-    else for (int c = 0; c <= A; ++c) pl->alphabet[c] = c == A ? '-' : (char)('A' + c);
-
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    auto restore = [&]() { (void)hipSetDevice(cur); };
-    if (hipSetDevice(device) != hipSuccess) { delete pl; restore(); return fail(SA_ERR_HIP, "hipSetDevice failed"); }
-    pl->num_cu = device_cus(device);
-    if (knobs().max_cus > 0) pl->num_cu = std::min(pl->num_cu, knobs().max_cus);
-
-    // ---- layout ----
-    const int R = pl->R, U = pl->U, RB = kWave * R;
-    uint64_t code_bytes = 0, mask_entries = 0, granules = 0, outb = 0, recw = 0;
-    pl->pairs.resize(np);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        PairDesc &d = pl->pairs[p];
-        d.text_off = pairs[p].text_offset;
-        d.text_len = pairs[p].text_len;
-        d.pattern_off = pairs[p].pattern_offset;
-        d.pattern_len = pairs[p].pattern_len;
-        d.code_off = code_bytes;
-        // kArr8: code_len bytes per copy (4A copies); kArr: A arrays of code_len dwords; else one
-        d.code_len = (kPad + d.text_len + 4 * kPad + 3) / 4 * 4;
-        // (a possible pair-packed plan, decided below, needs two column profiles per column)
-        const bool maybePair = P->mode == SA_GLOBAL && R >= 4 && A <= 4;
-        code_bytes += pl->sk == kArr8 ? (uint64_t)A * d.code_len : pl->sk == kArr ? (uint64_t)A * d.code_len
-                                                                                : (maybePair ? 2 : 1) * d.code_len;
-        d.out_off = outb;
-        outb += d.text_len + d.pattern_len + 16;
-        d.rec_off = recw;
-        recw += std::max(d.text_len, d.pattern_len) + 64;
-        d.first_strip = (int32_t)pl->strips.size();
-        const uint64_t n = d.text_len, m = d.pattern_len;
-        const int ns = (n == 0 || m == 0) ? 0 : (int)((m + RB - 1) / RB);
-        d.num_strips = ns;
-        // n + 63 steps reach column n in lane 63; one more step moves its bottom-row value into the
-        // publishing register (sa_fill.hip run_body); two bodies per loop trip
-        const int nsteps = (int)(((n + kWave) + 2 * U - 1) / (2 * U) * (2 * U));
-        for (int b = 0; b < ns; ++b)
-        {
-            StripDesc s;
-            s.pair = (int32_t)p;
-            s.row0 = 1 + b * RB;
-            s.flags = (b > 0 ? kHasPrev : 0) | (b + 1 < ns ? kHasNext : 0);
-            s.nsteps = nsteps;
-            s.mask_off = mask_entries;
-            mask_entries += (uint64_t)nsteps * R;
-            s.bnd_in = b > 0 ? pl->strips.back().bnd_out : 0;
-            s.bnd_out = granules;
-            if (b + 1 < ns) granules += n + 8;
-            pl->strips.push_back(s);
-        }
-    }
-    if (pl->strips.size() >= (1u << 31)) { delete pl; restore(); return fail(SA_ERR_UNSUPPORTED, "too many strips"); }
-    pl->out_bytes = outb;
-    pl->bytes_masks = mask_entries * 16;
-    pl->W = choose_W(pl->pairs);
-    for (const PairDesc &d : pl->pairs) pl->chain = pl->chain || d.num_strips > 1;
-    {
-        // pair-packed fill: global, pairs of one shape, DNA-sized alphabet, every S + 2g in [0, 255]
-        // and every value within u16 (see process_pair). Lone strips: fill_pair_kernel; chains of up
-        // to kPairChainMax strips per pair (every pair the same count): fill_pair_chain_kernel, one
-        // workgroup per couple, its LDS rows within a CU's
-        bool pair = R >= 4 && pair_packable(P, pairs, np);
-        if (pair && pl->chain)
-        {
-            const int S = pl->pairs[0].num_strips;
-            pair = S <= kPairChainMax && (size_t)(S - 1) * pair_row_entries((int)pl->pairs[0].text_len) * 4 <= 160 * 1024;
-        }
-        if (pair)
-        {
-            pl->sk = kPair;
-            granules = 0;  // (the chains hand their rows off in LDS: no granules)
-        }
-    }
-    // the band fill (sa_fill.hip process_band): R = 1 chains with int8 text profiles (global, or local
-    // with g >= 0, which kArr8 implies), and the band groups plus the strip groups fit one workgroup per
-    // CU (or run as persistent workers, below). A band is BR rows per lane (64 BR rows), the strips below
-    // run in groups of SW, a multiple of BR, so that a group boundary inside a pair falls on a band
-    // boundary: every pair's first strip a multiple of BR.
-    //   BR = 2: 128-row bands, strip groups of W (W even);
-    //   BR = 3: 192-row bands, strip groups of three: every band feeds exactly one strip group (no
-    //           granule is written for nothing) and the chain has a third fewer hand-offs at 8 VALU per
-    //           band step instead of 6 (process_band3). DNA-sized alphabets reading
-    //           the four byte copies only (the kernels that exist); the default for plans whose groups
-    //           are all resident (32768^2: global +6.8 %, local +6.3 %, 8192^2 global +7.6 % in same-box
-    //           A/Bs, profiles/r07), with persistent workers behind SA_BAND_R=3 (not measured).
-    // A plan that fails the three-row conditions takes two-row bands, then the one-wave fill.
-    {
-        int64_t mmax = 0;
-        for (const PairDesc &d : pl->pairs) mmax = std::max<int64_t>(mmax, (int64_t)d.pattern_len);
-        const int64_t persistRows = knobs().band_rows > 0 ? knobs().band_rows : (A <= 4 ? kBandPersistRows : kBandPersistRowsWide);
-        const bool bandable = knobs().band != 0 && pl->R == 1 && pl->sk == kArr8 && pl->chain;
-        auto plan_bands = [&](int BR, int SW, bool residentOnly) {
-            bool band = bandable;
-            for (const PairDesc &d : pl->pairs) band = band && (d.num_strips == 0 || d.first_strip % BR == 0);
-            int64_t nb = 0;
-            for (const PairDesc &d : pl->pairs) nb += std::max(0, (d.num_strips + BR - 1) / BR - 1);
-            const int64_t stripGroups = ((int64_t)pl->strips.size() + SW - 1) / SW;
-            const int64_t bandGroups = (nb + pl->W - 1) / pl->W;
-            // every group in flight at once, or (persistent band and strip workgroups, FillArgs::band_wgs)
-            // chains up to kBandPersistRows rows: past them the fill is throughput-bound and the bands' work
-            // on top of the strips' costs more than their shorter ramp saves
-            const bool resident = stripGroups + bandGroups <= pl->num_cu;
-            band = band && nb > 0 &&
-                   (resident || (!residentOnly && (mmax <= persistRows || knobs().band == 1) && pl->num_cu >= 4));
-            if (!band) return false;
-            // bands b = 0 .. B-2 of each pair (B = ceil(strips / BR); the last band's bottom row feeds
-            // nothing); every band publishes its bottom row to granules. The strips keep their planes;
-            // a strip at a group start takes its feed from the granules of the band above, the others
-            // from the strip above through the group's rings, and a group's last strip publishes nothing.
-            granules = 0;
-            for (const PairDesc &d : pl->pairs)
-            {
-                const uint64_t n = d.text_len;
-                const int B = (d.num_strips + BR - 1) / BR;
-                const int64_t fb = (int64_t)pl->bands.size();
-                for (int b = 0; b + 1 < B; ++b)
-                {
-                    StripDesc bd = pl->strips[d.first_strip + BR * b];
-                    bd.row0 = 1 + b * BR * kWave;
-                    bd.flags = (b > 0 ? kHasPrev : 0) | kHasNext;
-                    bd.mask_off = 0;
-                    bd.bnd_in = b > 0 ? pl->bands.back().bnd_out : 0;
-                    bd.bnd_out = granules;
-                    granules += n + 8;
-                    pl->bands.push_back(bd);
-                }
-                for (int k = 0; k < d.num_strips; ++k)
-                {
-                    StripDesc &sd = pl->strips[d.first_strip + k];
-                    const int i = d.first_strip + k;
-                    if (k + 1 < d.num_strips && (i + 1) % SW == 0) sd.flags &= ~kHasNext;
-                    sd.bnd_out = 0;
-                    sd.bnd_in = (k > 0 && i % SW == 0) ? pl->bands[fb + k / BR - 1].bnd_out : 0;
-                }
-            }
-            pl->band = true;
-            pl->band_r = BR;
-            pl->strip_w = SW;
-            return true;
-        };
-        // (kArr8A plans, sa_plan_fill's selector, have no three-row kernels)
-        const bool copy0 = knobs().align > (A > 4 ? 0 : 1);
-        const bool three = A <= 4 && !copy0 && pl->W >= 2 && knobs().band_r != 2;
-        if (!(three && plan_bands(3, 3, knobs().band_r != 3)) && pl->W % 2 == 0) plan_bands(2, pl->W, false);
-    }
-    {
-        // one-wave chain fill: a second workgroup on a CU puts two compute waves on a SIMD, which
-        // raises the step time 25 -> 41 ns and the hand-off lag 2.5 -> 4.6 us (tools/timeline.py,
-        // 120000^2); the strip chains of a few long pairs are latency-bound (a strip starts one lag
-        // after the one above), so they get one workgroup per CU; many chained pairs keep two
-        int64_t chained = 0;
-        for (const PairDesc &d : pl->pairs) chained += d.num_strips > 1;
-        pl->chain_solo = pl->chain && !pl->band && chained < pl->num_cu;
-        if (knobs().chain_per_cu) pl->chain_solo = pl->chain && !pl->band && knobs().chain_per_cu == 1;
-    }
-
-    // ---- tables ----
-    std::vector<int32_t> &prof = pl->h_prof, &table = pl->h_table;
-    prof.assign(4, 0);
-    table.resize(A * A);
-    for (int e = 0; e < A * A; ++e) table[e] = (int32_t)(P->score_matrix[e] + off2);
-    if (pl->sk == kProf || pl->sk == kPair)
-        for (int cp = 0; cp < A; ++cp)
-        {
-            uint32_t w = 0;
-            for (int ct = 0; ct < A; ++ct) w |= (uint32_t)(table[cp * A + ct] & 0xff) << (8 * ct);
-            prof[cp] = (int32_t)w;
-        }
-
-    // ---- table traceback groups (sa_walk.h) ----
-    if (pl->R == 1 && knobs().tb_tables)
-    {
-        pl->tb_pg.assign(np + 1, 0);
-        for (int64_t p = 0; p < np; ++p)
-        {
-            const PairDesc &d = pl->pairs[p];
-            pl->tb_pg[p] = (int32_t)pl->tb_groups.size();
-            if (d.num_strips < kTbMinStrips || d.text_len == 0) continue;
-            // strip tables only for the strips of pairs with groups (slot tbl0 + s - s_lo)
-            for (int s = 0; s < d.num_strips; s += kTbG)
-                pl->tb_groups.push_back({(int32_t)p, d.first_strip + s, d.first_strip + std::min(d.num_strips, s + kTbG) - 1,
-                                         (int32_t)pl->tb_slots + s});
-            pl->tb_slots += d.num_strips;
-        }
-        pl->tb_pg[np] = (int32_t)pl->tb_groups.size();
-        if (pl->tb_groups.empty()) pl->tb_pg.clear();
-    }
-    const size_t ntg = pl->tb_groups.size();
-    for (const PairDesc &d : pl->pairs)
-        pl->max_recs = std::max<int64_t>(pl->max_recs, (int64_t)(pl->R == 1 ? d.pattern_len : d.text_len));
+    pl->borrowed = ws != nullptr;
 
     // ---- device buffers ----
-    const size_t nstr = std::max<size_t>(1, pl->strips.size()), npp = std::max<size_t>(1, np);
-    const size_t codeB = 4 * code_bytes + 16, bndB = granules * 8 + 16, bestB = sizeof(uint64_t) * nstr;
+    const int A = pl->A;
+    const size_t ntg = pl->tb_groups.size(), nstr = std::max<size_t>(1, pl->strips.size()), npp = std::max<size_t>(1, np);
+    const size_t codeB = 4 * pl->code_bytes + 16, bndB = pl->granules * 8 + 16, bestB = sizeof(uint64_t) * nstr;
+    const uint64_t outb = pl->out_bytes, inN = in ? in->n : 0, inM = in ? in->m : 0;
+    const bool tbLocal = ntg && pl->mode == SA_LOCAL, chunked = pl->max_recs > kChunkRecs;
     struct Buf { void **ptr; size_t bytes; };
-    const uint64_t inN = in ? in->n : 0, inM = in ? in->m : 0;
     // order matters for workspace plans: [pairs .. ctrl] is the upload region, [ctrl .. out_pattern]
     // the download region (zero-sized entries are skipped)
     const Buf bufs[] = {
@@ -1002,11 +598,11 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
         {(void **)&pl->d_out_pattern, outb + 16},
         {(void **)&pl->d_codes, codeB},
         // (+8 KiB: the traceback's plane prefetch may read a few chunks past a strip)
-        {(void **)&pl->d_masks, pl->bytes_masks + 8192},
+        {(void **)&pl->d_masks, pl->mask_entries * 16 + 8192},
         {(void **)&pl->d_bnd, ws ? 0 : bndB},  // (workspace plans: the context's granule buffer)
         {(void **)&pl->d_best, bestB},
         {(void **)&pl->d_score, sizeof(int32_t) * npp},
-        {(void **)&pl->d_rec, 4 * recw + 16},
+        {(void **)&pl->d_rec, 4 * pl->rec_words + 16},
         {(void **)&pl->d_heads, sizeof(TbHead) * npp},
         {(void **)&pl->d_tbl, ntg ? sizeof(int32_t) * kTbK * pl->tb_slots : 0},
         {(void **)&pl->d_gtbl, sizeof(int32_t) * kTbK * ntg},
@@ -1015,18 +611,28 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
         {(void **)&pl->d_win, ntg ? sizeof(int32_t) * nstr : 0},
         {(void **)&pl->d_tbstart, ntg ? sizeof(int32_t) * kTbStartWords * npp : 0},
         {(void **)&pl->d_pend, ntg ? sizeof(int32_t) * npp : 0},
-        {(void **)&pl->d_sent, ntg && P->mode == SA_LOCAL ? sizeof(int32_t) * nstr : 0},
-        {(void **)&pl->d_sdelta, ntg && P->mode == SA_LOCAL ? sizeof(int32_t) * nstr : 0},
-        {(void **)&pl->d_send, ntg && P->mode == SA_LOCAL ? sizeof(int32_t) * 4 * nstr : 0},
-        {(void **)&pl->d_csum, pl->max_recs > kChunkRecs ? sizeof(int64_t) * kMaxChunks * npp : 0},
-        {(void **)&pl->d_cflag, pl->max_recs > kChunkRecs ? sizeof(uint64_t) * kMaxChunks * npp : 0},
+        {(void **)&pl->d_sent, tbLocal ? sizeof(int32_t) * nstr : 0},
+        {(void **)&pl->d_sdelta, tbLocal ? sizeof(int32_t) * nstr : 0},
+        {(void **)&pl->d_send, tbLocal ? sizeof(int32_t) * 4 * nstr : 0},
+        {(void **)&pl->d_csum, chunked ? sizeof(int64_t) * kMaxChunks * npp : 0},
+        {(void **)&pl->d_cflag, chunked ? sizeof(uint64_t) * kMaxChunks * npp : 0},
     };
-    int rc = SA_OK;
+    // what goes up with every plan (zero-sized entries are skipped)
+    struct Up { void **dst; const void *src; size_t bytes; };
+    const Up ups[] = {
+        {(void **)&pl->d_pairs, pl->pairs.data(), sizeof(PairDesc) * np},
+        {(void **)&pl->d_strips, pl->strips.data(), sizeof(StripDesc) * pl->strips.size()},
+        {(void **)&pl->d_prof, pl->h_prof.data(), sizeof(int32_t) * 4},
+        {(void **)&pl->d_table, pl->h_table.data(), sizeof(int32_t) * A * A},
+        {(void **)&pl->d_bands, pl->bands.data(), sizeof(StripDesc) * pl->bands.size()},
+        {(void **)&pl->d_tbgroups, pl->tb_groups.data(), sizeof(TbGroup) * ntg},
+        {(void **)&pl->d_tbpg, pl->tb_pg.data(), ntg ? sizeof(int32_t) * (np + 1) : 0},
+    };
     if (ws)
     {
         size_t total = 0;
         for (const Buf &b : bufs) total += b.bytes ? arena_round(b.bytes) : 0;
-        if ((rc = ctx_prepare(ws, total)) != SA_OK) { delete pl; restore(); return rc; }
+        if (int rc = ctx_prepare(ws, total)) return rc;
         size_t off = 0;
         for (const Buf &b : bufs)
         {
@@ -1034,17 +640,16 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
             *b.ptr = ws->arena + off;
             off += arena_round(b.bytes);
         }
-        if ((rc = ctx_bnd(ws, bndB)) != SA_OK) { delete pl; restore(); return rc; }
+        if (int rc = ctx_bnd(ws, bndB)) return rc;
         pl->d_bnd = (uint64_t *)ws->bnd;
         pl->bytes_total = total + bndB;
-        pl->borrowed = true;
         pl->own = ws->stream;
         pl->epoch_src = &ws->epoch;
         pl->d_up = (char *)pl->d_pairs;
         pl->up_bytes = (size_t)((char *)pl->d_ctrl - pl->d_up) + sizeof(Control);
         pl->d_dn = (char *)pl->d_ctrl;
         pl->dn_bytes = (size_t)(pl->d_out_pattern - pl->d_dn) + outb + 16;
-        if ((rc = ctx_pinned(ws, std::max(pl->up_bytes, pl->dn_bytes))) != SA_OK) { delete pl; restore(); return rc; }
+        if (int rc = ctx_pinned(ws, std::max(pl->up_bytes, pl->dn_bytes))) return rc;
         // one upload: descriptors, tables, the inputs and a zeroed control word at their arena
         // offsets. The code block is written whole by the encode kernel, granules carry growing
         // epochs in their own buffer (DeviceCtx) and every strip writes its best key, so nothing
@@ -1053,39 +658,27 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
         auto put = [&](const void *dptr, const void *src, size_t bytes) {
             if (bytes) std::memcpy(h + ((const char *)dptr - pl->d_up), src, bytes);
         };
-        put(pl->d_pairs, pl->pairs.data(), sizeof(PairDesc) * np);
-        put(pl->d_strips, pl->strips.data(), sizeof(StripDesc) * pl->strips.size());
-        put(pl->d_prof, prof.data(), sizeof(int32_t) * 4);
-        put(pl->d_table, table.data(), sizeof(int32_t) * A * A);
-        put(pl->d_bands, pl->bands.data(), sizeof(StripDesc) * pl->bands.size());
-        put(pl->d_tbgroups, pl->tb_groups.data(), sizeof(TbGroup) * ntg);
-        if (ntg) put(pl->d_tbpg, pl->tb_pg.data(), sizeof(int32_t) * (np + 1));
+        for (const Up &u : ups) put(*u.dst, u.src, u.bytes);
         put(pl->d_ws_text, in->text, inN);
         put(pl->d_ws_pattern, in->pattern, inM);
         std::memset(h + ((char *)pl->d_ctrl - pl->d_up), 0, sizeof(Control));
         if ((knobs().stage_kernel ? stage_copy(pl->d_up, ws->pinned_dev, pl->up_bytes, pl->own)
                                   : hipMemcpyAsync(pl->d_up, h, pl->up_bytes, hipMemcpyHostToDevice, pl->own)) != hipSuccess)
-        {
-            free_plan(pl);
-            restore();
             return fail(SA_ERR_HIP, "plan upload failed");
-        }
         pl->ctrl_ready = true;
-        restore();
-        *out = pl;
+        *out = hold.release();
         return SA_OK;
     }
     for (const Buf &b : bufs)
-        if (rc == SA_OK && b.bytes) { rc = dmalloc(b.ptr, b.bytes); pl->bytes_total += b.bytes; }
-    if (rc != SA_OK) { free_plan(pl); restore(); return rc; }
-    if (hipStreamCreateWithFlags(&pl->own, hipStreamNonBlocking) != hipSuccess) { free_plan(pl); restore(); return fail(SA_ERR_HIP, "stream creation failed"); }
+        if (b.bytes)
+        {
+            if (int rc = dmalloc(b.ptr, b.bytes)) return rc;
+            pl->bytes_total += b.bytes;
+        }
+    if (hipStreamCreateWithFlags(&pl->own, hipStreamNonBlocking) != hipSuccess) return fail(SA_ERR_HIP, "stream creation failed");
     // uploads (asynchronous on the plan's stream; the host sources live in the plan)
     hipStream_t st = pl->own;
-    bool okc = hipMemcpyAsync(pl->d_pairs, pl->pairs.data(), sizeof(PairDesc) * np, hipMemcpyHostToDevice, st) == hipSuccess &&
-               hipMemcpyAsync(pl->d_strips, pl->strips.data(), sizeof(StripDesc) * pl->strips.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
-               hipMemcpyAsync(pl->d_prof, prof.data(), sizeof(int32_t) * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
-               hipMemcpyAsync(pl->d_table, table.data(), sizeof(int32_t) * A * A, hipMemcpyHostToDevice, st) == hipSuccess &&
-               hipMemsetAsync(pl->d_bnd, 0, bndB, st) == hipSuccess &&
+    bool okc = hipMemsetAsync(pl->d_bnd, 0, bndB, st) == hipSuccess &&
                hipMemsetAsync(pl->d_best, 0, bestB, st) == hipSuccess &&
                hipMemsetAsync(pl->d_ctrl, 0, sizeof(Control), st) == hipSuccess;  // (bad_input: no stale epoch)
     // expansion flags carry the plan's epoch, which starts again at 1 for a plan of its own: a freed
@@ -1093,16 +686,12 @@ int plan_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device
     // context, which only grow, so their arena needs no clearing)
     if (okc && pl->d_cflag)
         okc = hipMemsetAsync(pl->d_cflag, 0, sizeof(uint64_t) * kMaxChunks * npp, st) == hipSuccess;
-    if (okc && pl->band)
-        okc = hipMemcpyAsync(pl->d_bands, pl->bands.data(), sizeof(StripDesc) * pl->bands.size(), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (okc && ntg)
-        okc = hipMemcpyAsync(pl->d_tbgroups, pl->tb_groups.data(), sizeof(TbGroup) * ntg, hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(pl->d_tbpg, pl->tb_pg.data(), sizeof(int32_t) * (np + 1), hipMemcpyHostToDevice, st) == hipSuccess;
+    for (const Up &u : ups)
+        if (okc && u.bytes) okc = hipMemcpyAsync(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice, st) == hipSuccess;
     // a plan of its own is complete when sa_plan_create returns (callers fill on other streams)
     if (okc) okc = hipStreamSynchronize(st) == hipSuccess;
-    if (!okc) { free_plan(pl); restore(); return fail(SA_ERR_HIP, "plan upload failed"); }
-    restore();
-    *out = pl;
+    if (!okc) return fail(SA_ERR_HIP, "plan upload failed");
+    *out = hold.release();
     return SA_OK;
 }
 
@@ -1157,6 +746,9 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
     const int ns = (int)pl->strips.size();
     if (ns > 0)
     {
+        // the launch geometry is the plan's (sa_plan.cpp fill_launch); per call: the epoch, the
+        // timeout, the I/O wave's poll period, SA_CHAIN_LDS_KB and the debug dumps
+        const FillLaunch &g = pl->launch;
         FillArgs a;
         a.pattern = (const int8_t *)d_pattern;
         a.codes = pl->d_codes;
@@ -1170,20 +762,21 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
         a.pair_score = pl->d_score;
         a.ctrl = pl->d_ctrl;
         a.num_strips = ns;
+        a.num_groups = g.num_groups;
         a.gap = pl->gap;
         a.A = pl->A;
         a.epoch = pl->epoch;
         a.key_bits = pl->key_bits;
         a.key_rowbits = pl->key_rowbits;
+        a.strip_w = g.strip_w;
         a.timeout_ticks = (uint64_t)(knobs().handoff_timeout_s * 1e8);
         a.io_sleep = knobs().io_sleep;
-        a.chain_lds = knobs().chain_lds_kb * 1024;
+        a.chain_lds = std::max(knobs().chain_lds_kb * 1024, g.chain_lds);
         a.bands = pl->d_bands;
-        a.num_bands = 0;
-        a.num_band_groups = 0;
-        a.band_wgs = 0;
-        a.pair_text_len = 0;
-        a.strip_w = 0;
+        a.num_bands = g.num_bands;
+        a.num_band_groups = g.num_band_groups;
+        a.band_wgs = g.band_wgs;
+        a.pair_text_len = g.pair_text_len;
         // SA_TIMELINE=<file>: debug dump of per-strip timestamps (s_memrealtime, 100 MHz)
         const char *tlPath = knobs().timeline;
         a.timeline = nullptr;
@@ -1193,62 +786,8 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
             HIP_TRY(hipMalloc((void **)&a.timeline, sizeof(uint64_t) * kTimelineWords * (ns + pl->bands.size())));
             tlBuf.reset(a.timeline);
         }
-        // (the pair-packed kernel always runs kPairWaves waves per workgroup)
-        const int W = pl->sk == kPair ? kPairWaves : pl->W;
-        a.num_groups = (ns + W - 1) / W;
-        // chains: two workgroups of W compute waves + an I/O wave per CU; lone strips: W compute
-        // waves per workgroup and up to 16 waves per CU (the batch kernel stays under 128 VGPRs)
-        const int perCU = pl->chain ? std::max(1, 8 / W) : std::max(1, 16 / W);
-        int grid = std::min(a.num_groups, std::max(1, pl->num_cu) * perCU);
-        if (pl->sk == kPair)
-        {
-            // one wave per two strips
-            const int units = ns / 2;
-            a.num_groups = (units + W - 1) / W;
-            grid = std::min(a.num_groups, std::max(1, pl->num_cu) * std::max(1, 8 / W));
-        }
-        if (pl->sk == kPair && pl->chain)
-        {
-            // pair-packed chains: one workgroup per couple of pairs, one wave per strip of the couple
-            a.num_groups = ns / 2 / pl->pairs[0].num_strips;
-            a.pair_text_len = (int32_t)pl->pairs[0].text_len;
-            grid = a.num_groups;
-        }
-        else if (pl->chain_solo)
-        {
-            // (plan_create) an LDS request above half a CU's keeps a second workgroup off the CU
-            a.chain_lds = std::max(a.chain_lds, 96 * 1024);
-            grid = std::min(a.num_groups, std::max(1, pl->num_cu));
-        }
-        if (pl->band)
-        {
-            // (three-row bands: strip groups of three, the band groups keep W)
-            a.strip_w = pl->strip_w;
-            a.num_groups = (ns + pl->strip_w - 1) / pl->strip_w;
-            // band groups on the first workgroups, strip groups on the rest, one workgroup per CU (the
-            // LDS request is above half a CU's) and every group in flight at once (plan_create checked
-            // that they fit): a strip group waits only for bands, which never wait for strips
-            a.num_bands = (int32_t)pl->bands.size();
-            a.num_band_groups = (a.num_bands + W - 1) / W;
-            a.band_wgs = a.num_band_groups;
-            a.chain_lds = std::max(a.chain_lds, 96 * 1024);
-            grid = a.num_band_groups + a.num_groups;
-            if (grid > pl->num_cu)
-            {
-                // more groups than CUs: persistent workers, each taking groups from its queue in chain
-                // order until it is empty (a group waits only for groups dequeued before it, so every
-                // worker count makes progress); the split that a model of the band and strip chains
-                //  puts ahead for 65536^2 .. 120000^2 is about 0.31 of the CUs to bands
-                a.band_wgs = std::max(1, std::min(a.num_band_groups, (int)(0.31 * pl->num_cu + 0.5)));
-                grid = a.band_wgs + std::max(1, std::min(a.num_groups, pl->num_cu - a.band_wgs));
-            }
-        }
-        // chains of protein-sized alphabets read copy 0 of their text profiles (kArr8A, sa_fill.h)
-        const int sk = pl->sk == kArr8 && pl->chain && knobs().align > (pl->A > 4 ? 0 : 1) ? kArr8A : pl->sk;
-        if (pl->band && pl->band_r == 3) launch_fill_band3(a, pl->mode == SA_LOCAL, grid, W, st);
-        else
-            launch_fill(pl->R, a, pl->mode == SA_LOCAL, sk, grid, pl->sk == kPair && pl->chain ? pl->pairs[0].num_strips : W,
-                        pl->chain, st);
+        if (g.band3) launch_fill_band3(a, pl->mode == SA_LOCAL, g.grid, g.W, st);
+        else launch_fill(pl->R, a, pl->mode == SA_LOCAL, g.sk, g.grid, g.W, pl->chain, st);
         HIP_TRY(hipGetLastError());
         if (tlPath)
         {
@@ -1419,9 +958,7 @@ int sa_plan_fetch_results(sa_plan *pl, sa_result *out, void *stream)
     if (out && !pl->pairs.empty())
         HIP_TRY(hipMemcpyAsync(out, pl->d_results, sizeof(sa_result) * pl->pairs.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (ctrl.bad_input == pl->epoch) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
-    if (ctrl.abort_flag) return fail(SA_ERR_TIMEOUT, "fill aborted: a strip hand-off timed out");
-    return SA_OK;
+    return check_control(ctrl, pl->epoch);
 }
 
 int sa_plan_fetch_alignment(sa_plan *pl, int64_t index, char *at, char *ap, uint64_t cap, void *stream)
@@ -1462,9 +999,7 @@ int sa_plan_fetch_all(sa_plan *pl, sa_result *out, char *tb, char *pb, uint64_t 
     if (pb && pl->out_bytes) HIP_TRY(hipMemcpyAsync(pb, pl->d_out_pattern, pl->out_bytes, hipMemcpyDeviceToHost, st));
     for (size_t i = 0; i < pl->pairs.size(); ++i) offsets[i] = pl->pairs[i].out_off;
     HIP_TRY(hipStreamSynchronize(st));
-    if (ctrl.bad_input == pl->epoch) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
-    if (ctrl.abort_flag) return fail(SA_ERR_TIMEOUT, "fill aborted: a strip hand-off timed out");
-    return SA_OK;
+    return check_control(ctrl, pl->epoch);
 }
 
 int sa_plan_fetch_directions(sa_plan *pl, int64_t index, uint8_t *M, void *stream)
@@ -1486,7 +1021,8 @@ int sa_plan_fetch_directions(sa_plan *pl, int64_t index, uint8_t *M, void *strea
     HIP_TRY(hipMemcpyAsync(h.data(), pl->d_masks + e0 * 4, h.size() * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int R = pl->R, RB = kWave * R;
-    const uint64_t CS = std::max(32, pl->U * R), NW = CS / 32, LW = 2 * NW;  // Cfg<R>
+    const ChunkGeom cg = chunk_geom(R);
+    const uint64_t CS = cg.CS, NW = cg.NW, LW = cg.LW;
     for (uint64_t i = 1; i <= m; ++i)
     {
         const uint64_t b = (i - 1) / RB, il = (i - 1) % RB, k = il / R, rho = il % R;
@@ -1556,15 +1092,14 @@ int sa_plan_info(const sa_plan *pl, int64_t *num_strips, int32_t *rows_per_lane,
     if (num_strips) *num_strips = (int64_t)pl->strips.size();
     if (rows_per_lane) *rows_per_lane = pl->R;
     if (device_bytes) *device_bytes = pl->bytes_total;
-    if (mask_bytes) *mask_bytes = pl->bytes_masks;
+    if (mask_bytes) *mask_bytes = pl->mask_entries * 16;
     return SA_OK;
 }
 
 int sa_plan_fill_kind(const sa_plan *pl)
 {
     if (!pl) return fail(SA_ERR_INVALID, "sa_plan_fill_kind: null plan");
-    if (pl->sk == kPair) return pl->chain ? SA_FILL_PAIR_CHAIN : SA_FILL_PAIR;
-    return pl->band ? (pl->band_r == 3 ? SA_FILL_BAND3 : SA_FILL_BAND) : SA_FILL_STRIPS;
+    return fill_kind(*pl);
 }
 
 const void *sa_plan_device_results(const sa_plan *pl) { return pl ? (const void *)pl->d_results : nullptr; }
@@ -1619,8 +1154,7 @@ int sa_align_pair(const sa_params *P, const char *text, uint64_t n, const char *
     Control ctrl;
     std::memcpy(&ctrl, h, sizeof(Control));
     // also in fill-only mode: a fill whose hand-off timed out produced garbage, not a fill time
-    if (ctrl.bad_input == pl->epoch) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
-    if (ctrl.abort_flag) return fail(SA_ERR_TIMEOUT, "fill aborted: a strip hand-off timed out");
+    if ((rc = check_control(ctrl, pl->epoch))) return rc;
     if (!fillOnly)
     {
         std::memcpy(out, h + ((char *)pl->d_results - pl->d_dn), sizeof(sa_result));

@@ -48,15 +48,7 @@ struct FillArgs {
 };
 
 constexpr int kTimelineWords = 48;  // SA_TIMELINE record per strip, then per band (words 6..37: experiment progress stamps)
-constexpr int kMaxWaves = 4;       // compute waves per chain workgroup (+1 I/O wave: 320 threads; one
-                                   // compute wave per SIMD: two per SIMD ran 2.2x slower per step)
-constexpr int kPairWaves = 4;      // waves per workgroup of the pair-packed batch kernel
-constexpr int kPairChainMax = 8;   // strips per pair (waves per workgroup) of a pair-packed chain
-constexpr int kPairFeedOff = 64;   // LDS row entry of column c: c + kPairFeedOff (c >= -63)
-// (entries: columns -63 .. n + 2U published, and every lane of a consumer's feed read up to column
-// nSteps + 63 <= n + 2U + 126)
-__host__ __device__ constexpr int pair_row_entries(int n) { return (n + kPairFeedOff + 4 * kWave + 63) / 64 * 64; }
-
+// (kMaxWaves, kPairWaves, kPairChainMax, kPairFeedOff, pair_row_entries: sa_layout.h)
 
 // Where a strip's substitution scores come from (SK). Every table already holds S + 2g (global) or
 // S + g (local), the offsets the recurrences below fold in:
@@ -76,7 +68,7 @@ __host__ __device__ constexpr int pair_row_entries(int n) { return (n + kPairFee
 //           with v_alignbyte (fill_r1a.hip, launch_fill_align). A wave's 64 lanes then touch one
 //           array per letter instead of one per letter and copy: the CU's L1 holds the working set.
 // The zero padding of the profiles keeps the ramp cells left of column 1 at the boundary value.
-enum ScoreKind { kProf = 0, kTable = 1, kArr = 2, kArr8 = 3, kPair = 4, kArr8A = 5 };
+// (enum ScoreKind itself: sa_layout.h, where the host planner reads it)
 template <int SK>
 constexpr bool kIsArr = SK == kArr || SK == kArr8;
 

@@ -39,6 +39,46 @@ namespace sa {
 constexpr int kWave = 64;
 constexpr int kPad = 64;          // text-code padding before/after each pair
 
+// Fill constants the host planner (sa_plan.cpp) shares with the kernels (sa_fill.hip).
+constexpr int kMaxWaves = 4;       // compute waves per chain workgroup (+1 I/O wave: 320 threads; one
+                                   // compute wave per SIMD: two per SIMD ran 2.2x slower per step)
+constexpr int kPairWaves = 4;      // waves per workgroup of the pair-packed batch kernel
+constexpr int kPairChainMax = 8;   // strips per pair (waves per workgroup) of a pair-packed chain
+constexpr int kPairFeedOff = 64;   // LDS row entry of column c: c + kPairFeedOff (c >= -63)
+// (entries: columns -63 .. n + 2U published, and every lane of a consumer's feed read up to column
+// nSteps + 63 <= n + 2U + 126)
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+constexpr int pair_row_entries(int n) { return (n + kPairFeedOff + 4 * kWave + 63) / 64 * 64; }
+
+// Chunk geometry of a strip height R (DIRECTIONS above; the fill's Cfg<R>): U steps per unrolled
+// body, chunks of CS slots, NW words per plane and LW dwords per lane and chunk.
+struct ChunkGeom {
+    int U, CS, NW, LW;
+};
+inline ChunkGeom chunk_geom(int R)
+{
+    const int U = (16 / R) > 4 ? 16 / R : 4, CS = U * R > 32 ? U * R : 32;
+    return {U, CS, CS / 32, 2 * (CS / 32)};
+}
+
+// Traceback constants the planner shares with sa_walk.hip (see sa_walk.h for what they mean).
+constexpr int kTbK = 2048;       // start columns per strip window
+constexpr int kTbG = 16;         // strips per group
+constexpr int kTbMinStrips = 8;  // pairs with fewer strips take the sequential walk
+constexpr int kTbStartWords = 12;   // words of a pair's TbStart block
+constexpr int kChunkRecs = 2048;    // pairs of at most this many records: one expansion block each
+constexpr int kMaxChunks = 256;     // blocks per pair (chunks past a pair's records exit at once)
+struct TbGroup {
+    int32_t pair, s_lo, s_hi;  // the plan's strip indices, s_lo <= s_hi (one pair's)
+    int32_t tbl0;              // strip s_lo's table slot (tables exist only for pairs with groups:
+                               // slot of strip s = tbl0 + s - s_lo)
+};
+
+// Where a strip's substitution scores come from (sa_fill.h describes each kind).
+enum ScoreKind { kProf = 0, kTable = 1, kArr = 2, kArr8 = 3, kPair = 4, kArr8A = 5 };
+
 struct StripDesc {
     int32_t pair;       // owning pair
     int32_t row0;       // first DP row (1-based) of the strip

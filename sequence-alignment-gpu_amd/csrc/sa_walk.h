@@ -65,9 +65,8 @@ struct WalkArgs {
 // STOP) from the best cell down to row 1; each strip then sums its H steps, and tb_check_kernel finds
 // per strip, from H at the strip's entry (the sums of the strips before it), where traceBackSW ends
 // in it; the first such strip in walk order gives the pair's head (tb_finish_kernel).
-constexpr int kTbK = 2048;       // start columns per strip window
-constexpr int kTbG = 16;         // strips per group
-constexpr int kTbMinStrips = 8;  // pairs with fewer strips take the sequential walk
+// (kTbK start columns per window, kTbG strips per group, kTbMinStrips, kTbStartWords and TbGroup:
+// sa_layout.h, shared with the host planner)
 // ROUNDS. The windows of a round are centred on a line through an anchor: the start cell, then (a
 // round that found the path leaving a window at group g) the path's entry column into group g, which
 // is then known. The next round rebuilds the tables of the strips at and above the anchor and resumes
@@ -81,14 +80,9 @@ enum TbStart {
     kTbI0, kTbJ0, kTbH, kTbBs,       // start cell, its H, its strip
     kTbRa, kTbXa, kTbDr, kTbDx,      // anchor row / column, line slope dx / dr (columns per row)
     kTbGres,                         // group the chain resumes at (-1: the start cell's group)
-    kTbBmin,                         // local: the lowest strip resolved (the walk may end above it)
-    kTbStartWords = 12
+    kTbBmin                          // local: the lowest strip resolved (the walk may end above it)
 };
-struct TbGroup {
-    int32_t pair, s_lo, s_hi;  // the plan's strip indices, s_lo <= s_hi (one pair's)
-    int32_t tbl0;              // strip s_lo's table slot (tables exist only for pairs with groups:
-                               // slot of strip s = tbl0 + s - s_lo)
-};
+static_assert(kTbBmin < kTbStartWords, "a pair's TbStart block holds every word");
 struct TbArgs {
     const StripDesc *strips;
     const PairDesc *pairs;
@@ -153,9 +147,8 @@ struct ExpandArgs {
 void launch_walk(int R, bool local, const WalkArgs &a, int np, hipStream_t st);
 // every plan: records -> aligned strings and sa_result; max_records bounds h.nrec over the pairs
 // (pattern rows for the row walk, text columns for the column walk)
-constexpr int kChunkRecs = 2048;    // pairs of at most this many records: one expansion block each
+// (kChunkRecs records per single-block pair, kMaxChunks blocks per pair: sa_layout.h)
 constexpr int kMinChunkRecs = 256;  // records per block of a longer pair (at least)
-constexpr int kMaxChunks = 256;     // blocks per pair (chunks past a pair's records exit at once)
 // chunk_sums and chunk_flags must hold np * kMaxChunks entries when max_records > kChunkRecs
 void launch_expand(const ExpandArgs &a, int np, int64_t max_records, hipStream_t st);
 

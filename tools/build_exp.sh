@@ -17,7 +17,7 @@ fi
 flags="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$root/include -I$src -DSA_EXPERIMENT=1 $*"
 # EXP_ONLY="fill_r1 ..." recompiles only those units and takes the others from the product build
 pids=()
-for f in sa_engine sa_walk sa_batch fill_r1 fill_r1a fill_r2 fill_r4 fill_r8 fill_r16 fill_r32; do
+for f in sa_engine sa_walk sa_batch fill_r1 fill_r1a fill_r1b fill_r2 fill_r4 fill_r8 fill_r16 fill_r32; do
   if [ -n "$EXP_ONLY" ] && [[ " $EXP_ONLY " != *" $f "* ]]; then
     cp $root/sequence-alignment-gpu_amd/build/$f.o $out/$f.o
   else
@@ -27,6 +27,7 @@ done
 for p in "${pids[@]}"; do wait $p; done
 mkdir -p $root/build_exp
 cp $root/sequence-alignment-gpu_amd/build/build_id.o $out/build_id.o
+cp $root/sequence-alignment-gpu_amd/build/sa_plan.o $out/sa_plan.o  # (host planner: plain C++, no experiment defines)
 /opt/rocm/bin/hipcc $flags -shared $out/*.o -L/opt/rocm/lib -ldl -o $root/build_exp/libsa_$tag.so
 rm -f $root/build_exp/libsa_$tag.so.[0-9]*
 echo built build_exp/libsa_$tag.so

@@ -22,7 +22,7 @@ One step (four registers rotate through the roles Qn -> Q/up -> diag/F' -> left,
     h   Y[4h + (k & 3)] byte 3 - (k >> 2) = left - up  (sign = raw "up > left" / raw TOP)
 with k the step in the body and h = HALF the body's word of the 32-slot chunk. A difference's low
 byte has the sign of the difference when the difference lies in [-128, 127]: the plan uses these
-bodies only when every difference is bounded so (sa_engine.hip, byte_diffs). The R = 1 plane word
+bodies only when every difference is bounded so (sa_plan.cpp, byte_diffs). The R = 1 plane word
 is INTERLEAVED (sa_layout.h): slot k of a word has DIAG at bit 31 - 2k and the second plane at bit
 30 - 2k, so register r = 4h + t0 (steps t0, t0 + 4, t0 + 8, t0 + 12 in bytes 3..0) lands with one
 shift: (X[r] & 0x80808080) >> 2 t0, (Y[r] & 0x80808080) >> (2 t0 + 1). The merge costs 15 VALU per
