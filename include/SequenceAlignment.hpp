@@ -134,6 +134,12 @@ uint64_t alignSequenceGPUFillMicros(const Request &, Response *);
 /// Fills responses[i] as alignSequenceGPU would. Returns 0, or 1 with the message on stdout.
 uint64_t alignSequenceGPUBatch(const Request *requests, Response *responses, uint64_t numRequests, int numGpus);
 
+/// Extension: Response::score of numRequests requests on `device`, without alignments (sa_score_batch:
+/// no direction matrix, no traceback). All requests must share one scoring scheme (alignment type,
+/// alphabet, score matrix, gap penalty). scores: numRequests entries. Returns 0, or 1 with the
+/// message on stdout.
+uint64_t scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

@@ -185,6 +185,48 @@ const void *sa_plan_device_results(const sa_plan *plan);
  * a host round trip). The abort / bad-input flags are not checked here (sa_plan_fetch_results does). */
 int sa_plan_copy_results(const sa_plan *plan, void *d_dst, void *stream);
 
+/* ---- score only: many pairs without direction planes or traceback ----------------------- */
+
+/* The score of a pair and the cell it is read from. No direction planes, no traceback: a scorer's
+ * device memory is the inputs, the results and one boundary row per resident wave, whatever the
+ * number of cells. The limits of the plans apply unchanged. */
+typedef struct sa_score_result {
+    int32_t score;         /* Response::score of the reference for this pair            */
+    int32_t status;        /* SA_OK or this pair's error                                */
+    uint64_t end_text;     /* column j of the scored cell (global: text_len)            */
+    uint64_t end_pattern;  /* row i of the scored cell (global: pattern_len); local: the
+                              first maximum in row-major order, (0,0) when the score is 0 */
+} sa_score_result;
+typedef struct sa_scorer sa_scorer;
+
+/* Score num_pairs pairs held in host memory on `device`. Synchronous. out: num_pairs entries. */
+int sa_score_batch(const sa_params *params, const sa_host_pair *pairs, int64_t num_pairs, int device,
+                   sa_score_result *out);
+
+/* A scorer for num_pairs pairs addressed in device-resident arenas (as sa_plan_create). It may be
+ * run any number of times. params->rows_per_lane: 0 = automatic, else 1, 2, 4, 8 (16 and 32 are
+ * taken as 8). */
+int sa_scorer_create(const sa_params *params, const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+/* Enqueue the scoring of every pair on `stream` (NULL = the HIP null stream). */
+int sa_scorer_run(sa_scorer *scorer, const void *d_text, const void *d_pattern, void *stream);
+/* Synchronise `stream` and copy the per-pair results to host (num_pairs entries). Returns
+ * SA_ERR_INVALID if an input byte was outside the alphabet. */
+int sa_scorer_fetch(sa_scorer *scorer, sa_score_result *out, void *stream);
+/* Waves launched, rows per lane and device bytes (inputs, results, row buffers, constants). */
+int sa_scorer_info(const sa_scorer *scorer, int64_t *num_waves, int32_t *rows_per_lane, uint64_t *device_bytes);
+int sa_scorer_destroy(sa_scorer *scorer);
+
+/* Score `query` (the pattern) against num_texts texts and align the k best: ranked by score
+ * descending, ties to the lower index; *num_hits = min(k, num_texts). scores (num_texts entries) may
+ * be NULL. hit_index / hit_results: k entries. aligned_text / aligned_pattern: both NULL, or k host
+ * buffers each of at least (its hit's text_len + query_len) bytes; buffers sized for the longest text
+ * always do. The hits are aligned through a plan on the same device: their results and strings are
+ * what sa_align_pair returns for the pair. k = 0 gives scores only. Synchronous. */
+int sa_search(const sa_params *params, const char *query, uint64_t query_len, const char *const *texts,
+              const uint64_t *text_lens, int64_t num_texts, int k, int device, sa_score_result *scores,
+              int64_t *hit_index, sa_result *hit_results, char *const *aligned_text,
+              char *const *aligned_pattern, int64_t *num_hits);
+
 /* ---- misc ------------------------------------------------------------------------------ */
 int sa_device_count(int *count);
 const char *sa_last_error(void);

@@ -171,3 +171,34 @@ uint64_t SequenceAlignment::alignSequenceGPUFillMicros(const Request &request, R
 {
     return runGPU(request, response, true);
 }
+
+uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
+{
+    if (numRequests == 0) return 0;
+    std::vector<sa_params> params(numRequests);
+    std::vector<sa_host_pair> pairs(numRequests);
+    for (uint64_t i = 0; i < numRequests; ++i)
+    {
+        if (!toParams(requests[i], &params[i]))
+        {
+            std::cout << "error: only --global and --local alignments are implemented\n";
+            return 1;
+        }
+        if (!sameScheme(params[0], params[i]))
+        {
+            std::cout << "error: scoreSequencesGPU needs one scoring scheme for all requests\n";
+            return 1;
+        }
+        pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
+                                requests[i].patternNumBytes};
+    }
+    std::vector<sa_score_result> res(numRequests);
+    const int rc = sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
+    if (rc != SA_OK)
+    {
+        std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
+        return 1;
+    }
+    for (uint64_t i = 0; i < numRequests; ++i) scores[i] = res[i].score;
+    return 0;
+}

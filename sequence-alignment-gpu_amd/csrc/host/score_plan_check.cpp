@@ -1,0 +1,85 @@
+// bin/sa_score_plan_check: the score-only planner (sa_score_plan.cpp) as a stand-alone program. No
+// GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
+// the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
+//   sa_score_plan_check --mode global|local|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
+//                       [--match M --mismatch X] NxM[xCOUNT] ...
+// NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
+// A planning error prints {"error": code, "message": text}.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sa_score_plan.h"
+
+using namespace sa;
+
+int main(int argc, char **argv)
+{
+    sa_params P;
+    std::memset(&P, 0, sizeof(P));
+    P.alphabet_size = 4;
+    P.gap_penalty = 5;
+    int cus = 256, match = 5, mismatch = -4;
+    std::vector<sa_pair> pairs;
+    for (int i = 1; i < argc; ++i)
+    {
+        const std::string a = argv[i];
+        auto value = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
+        if (a == "--mode")
+        {
+            const std::string v = value();
+            P.mode = v == "global" ? SA_GLOBAL : v == "local" ? SA_LOCAL : std::atoi(v.c_str());
+        }
+        else if (a == "--alphabet") P.alphabet_size = std::atoi(value());
+        else if (a == "--gap") P.gap_penalty = std::atoi(value());
+        else if (a == "--cus") cus = std::atoi(value());
+        else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
+        else if (a == "--match") match = std::atoi(value());
+        else if (a == "--mismatch") mismatch = std::atoi(value());
+        else
+        {
+            unsigned long long n = 0, m = 0, count = 1;
+            if (std::sscanf(a.c_str(), "%llux%llux%llu", &n, &m, &count) < 2)
+            {
+                std::fprintf(stderr, "sa_score_plan_check: bad argument %s\n", a.c_str());
+                return 2;
+            }
+            for (unsigned long long k = 0; k < count; ++k)
+            {
+                sa_pair pr;
+                pr.text_offset = pairs.empty() ? 0 : pairs.back().text_offset + pairs.back().text_len;
+                pr.text_len = n;
+                pr.pattern_offset = pairs.empty() ? 0 : pairs.back().pattern_offset + pairs.back().pattern_len;
+                pr.pattern_len = m;
+                pairs.push_back(pr);
+            }
+        }
+    }
+    const int a = std::min(std::max(P.alphabet_size, 1), 64);
+    std::vector<int32_t> S((size_t)a * a, mismatch);
+    for (int c = 0; c < a; ++c) S[(size_t)c * a + c] = match;
+    P.score_matrix = S.data();
+
+    ScorePlan pl;
+    std::string err;
+    const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err);
+    if (rc != SA_OK)
+    {
+        std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+        return 0;
+    }
+    std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"R\": %d, \"key_rowbits\": %d, \"num_cu\": %d, \"waves_per_simd\": %d, "
+                "\"grid\": %d, \"num_pairs\": %lld, \"max_text\": %llu, \"row_stride\": %llu, \"input_bytes\": %llu, "
+                "\"device_bytes\": %llu, \"padded_cells\": %llu, \"cost\": [%llu, %llu, %llu, %llu], \"order\": [",
+                pl.mode, pl.A, pl.gap, pl.R, pl.key_rowbits, pl.num_cu, pl.waves_per_simd, pl.grid, (long long)pl.num_pairs,
+                (unsigned long long)pl.max_text, (unsigned long long)pl.row_stride, (unsigned long long)pl.input_bytes,
+                (unsigned long long)pl.device_bytes, (unsigned long long)pl.padded_cells, (unsigned long long)pl.cost[0],
+                (unsigned long long)pl.cost[1], (unsigned long long)pl.cost[2], (unsigned long long)pl.cost[3]);
+    // the order of a large batch is long: the first 64 entries
+    for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
+    std::printf("]}\n");
+    return 0;
+}

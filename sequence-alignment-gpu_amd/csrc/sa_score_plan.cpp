@@ -1,0 +1,130 @@
+// The score-only planner (sa_score_plan.h): validation, work order, rows per lane, launch and
+// workspace of a scorer. Host only, no HIP.
+#include "sa_score_plan.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <numeric>
+
+namespace sa {
+
+const ScoreKnobs &score_knobs()
+{
+    static const ScoreKnobs k = [] {
+        ScoreKnobs v;
+        if (const char *e = std::getenv("SA_SCORE_ROWS_PER_LANE")) v.rows_per_lane = std::atoi(e);
+        if (const char *e = std::getenv("SA_SCORE_WAVES")) v.waves_per_simd = std::atoi(e);
+        if (const char *e = std::getenv("SA_MAX_CUS")) v.max_cus = std::atoi(e);
+        return v;
+    }();
+    return k;
+}
+
+// the instance of each R with the most registers (local, alphabets up to 4): 53, 71, 101 and 165
+// VGPRs of the SIMD's 512
+int score_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 7 : 8; }
+
+namespace {
+
+int bitlen(uint64_t v)
+{
+    int b = 0;
+    while (v) { ++b; v >>= 1; }
+    return b;
+}
+
+}  // namespace
+
+int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                    ScorePlan *out, std::string *err)
+{
+    auto fail = [&](int code, const char *msg) { *err = msg; return code; };
+    if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
+    const int A = P->alphabet_size;
+    if (A < 1 || A > 32) return fail(SA_ERR_INVALID, "alphabet_size must be 1..32");
+    if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL) return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL or SA_LOCAL");
+    if (np > INT32_MAX) return fail(SA_ERR_UNSUPPORTED, "more than 2^31-1 pairs");
+    int R = P->rows_per_lane;
+    if (kn.rows_per_lane) R = kn.rows_per_lane;
+    if (R == 16 || R == 32) R = 8;  // a params struct shared with a plan: the scorer's tallest strip
+    if (R != 0 && R != 1 && R != 2 && R != 4 && R != 8) return fail(SA_ERR_INVALID, "rows_per_lane must be 0, 1, 2, 4, 8, 16 or 32");
+
+    // ---- the limits of the plans, unchanged ----
+    const int64_t g = P->gap_penalty;
+    int64_t smax = INT32_MIN, sabs = 0;
+    for (int e = 0; e < A * A; ++e)
+    {
+        smax = std::max<int64_t>(smax, P->score_matrix[e]);
+        sabs = std::max<int64_t>(sabs, std::llabs((long long)P->score_matrix[e]));
+    }
+    uint64_t lmax = 0, hmax_local = 0;
+    ScorePlan &pl = *out;
+    pl = ScorePlan();
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
+        if (n >= (1u << 24) - 1 || m >= (1u << 24) - 1) return fail(SA_ERR_UNSUPPORTED, "sequence longer than 2^24-2 letters");
+        lmax = std::max(lmax, std::max(n, m));
+        const uint64_t span = n + m;
+        const uint64_t bound = ((uint64_t)sabs + (uint64_t)std::llabs(g)) * span + (uint64_t)std::llabs(g) * span;
+        if (bound >= (1ull << 30)) return fail(SA_ERR_UNSUPPORTED, "scores may exceed the int32 range");
+        const uint64_t h = g >= 0 ? (uint64_t)std::max<int64_t>(smax, 0) * std::min(n, m)
+                                  : ((uint64_t)sabs + (uint64_t)(-g)) * span;
+        hmax_local = std::max(hmax_local, h);
+        pl.max_text = std::max(pl.max_text, n);
+        pl.input_bytes += n + m;
+    }
+    pl.key_rowbits = std::max(1, bitlen(lmax + 1));
+    if (P->mode == SA_LOCAL && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * pl.key_rowbits))
+        return fail(SA_ERR_UNSUPPORTED, "local scores may exceed the best-cell key range");
+
+    pl.mode = P->mode;
+    pl.A = A;
+    pl.gap = (int)g;
+    pl.num_pairs = np;
+    pl.num_cu = kn.max_cus > 0 ? std::min(num_cu, kn.max_cus) : num_cu;
+
+    // ---- work order: most cells first, ties by index (waves draw pairs in this order, so the long
+    // pairs start first and the short ones fill the tail) ----
+    pl.order.resize((size_t)np);
+    std::iota(pl.order.begin(), pl.order.end(), 0);
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](int32_t a, int32_t b) {
+        return pairs[a].text_len * pairs[a].pattern_len > pairs[b].text_len * pairs[b].pattern_len;
+    });
+
+    // ---- rows per lane: a strip of 64R rows over n columns takes n + 63 steps of
+    // kScoreStepBase + R * kScoreStepRow* instructions; the cheapest total wins, ties to the
+    // smaller R (fewer registers, more resident waves) ----
+    static const int kR[4] = {1, 2, 4, 8};
+    int best = 0;
+    for (int k = 0; k < 4; ++k)
+    {
+        const uint64_t rows = 64ull * kR[k], per_step = (uint64_t)(kScoreStepBase + kR[k] * (P->mode == SA_LOCAL ? kScoreStepRowLocal : kScoreStepRowGlobal));
+        uint64_t c = 0;
+        for (int64_t p = 0; p < np; ++p)
+        {
+            const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
+            if (n == 0 || m == 0) continue;
+            c += (n + 63) * ((m + rows - 1) / rows) * per_step;
+        }
+        pl.cost[k] = c;
+        if (c < pl.cost[best]) best = k;
+    }
+    pl.R = R ? R : kR[best];
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const uint64_t rows = 64ull * pl.R;
+        pl.padded_cells += pairs[p].text_len * ((pairs[p].pattern_len + rows - 1) / rows) * rows;
+    }
+
+    // ---- launch and workspace ----
+    pl.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, 8) : score_waves_per_simd(pl.R);
+    pl.grid = (int)std::min<int64_t>(np, (int64_t)pl.num_cu * 4 * pl.waves_per_simd);
+    pl.row_stride = (pl.max_text + 63) / 64 * 64 + 64;
+    const uint64_t per_pair = 24 /* descriptor */ + 4 /* order */ + sizeof(sa_score_result);
+    pl.device_bytes = pl.input_bytes + (uint64_t)np * per_pair + (uint64_t)pl.grid * pl.row_stride * 4 +
+                      32 * 32 * 4 /* score table */ + 256 /* counter and flags */;
+    return SA_OK;
+}
+
+}  // namespace sa

@@ -25,7 +25,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_plan_fetch_results", "sa_plan_fetch_alignment", "sa_plan_info", "sa_plan_device_results", "sa_plan_copy_results",
            "sa_device_count", "sa_last_error", "sa_abi_version", "sa_selftest", "sa_plan_fetch_directions", "sa_release_workspace",
            "sa_plan_output_bytes", "sa_plan_fetch_all", "sa_align_batch", "sa_batch_deal", "sa_build_id",
-           "sa_batch_last_stats", "sa_plan_fill_kind")
+           "sa_batch_last_stats", "sa_plan_fill_kind", "sa_score_batch", "sa_scorer_create", "sa_scorer_run",
+           "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search")
 
 
 class SaParams(ctypes.Structure):
@@ -41,6 +42,11 @@ class SaPair(ctypes.Structure):
 class SaResult(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("num_alignment_bytes", ctypes.c_uint64),
                 ("start_text", ctypes.c_uint64), ("start_pattern", ctypes.c_uint64)]
+
+
+class SaScoreResult(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("end_text", ctypes.c_uint64),
+                ("end_pattern", ctypes.c_uint64)]
 
 
 class SaError(RuntimeError):
@@ -91,6 +97,15 @@ def _load():
     L.sa_build_id.restype = ctypes.c_char_p
     L.sa_batch_last_stats.argtypes = [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), P,
                                       ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
+    L.sa_score_batch.argtypes = [ctypes.POINTER(SaParams), P, ctypes.c_int64, I, P]
+    L.sa_scorer_create.argtypes = [ctypes.POINTER(SaParams), ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                   ctypes.POINTER(P)]
+    L.sa_scorer_run.argtypes = [P, P, P, P]
+    L.sa_scorer_fetch.argtypes = [P, P, P]
+    L.sa_scorer_info.argtypes = [P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(U64)]
+    L.sa_scorer_destroy.argtypes = [P]
+    L.sa_search.argtypes = [ctypes.POINTER(SaParams), P, U64, P, P, ctypes.c_int64, I, I, P, P, P, P, P,
+                            ctypes.POINTER(ctypes.c_int64)]
     for name in EXPORTS:
         getattr(L, name)
     check_build_id(L)
@@ -288,3 +303,95 @@ class Plan:
             res.append({"score": r.score, "num_bytes": L, "start_text": r.start_text, "start_pattern": r.start_pattern,
                         "aligned_text": tb[o:o + L].tobytes().decode(), "aligned_pattern": pb[o:o + L].tobytes().decode()})
         return res
+
+
+# numpy view of sa_score_result (include/sa_hip.h): int32 score, int32 status, uint64 x 2
+SCORE_DTYPE = np.dtype([("score", "<i4"), ("status", "<i4"), ("end_text", "<u8"), ("end_pattern", "<u8")])
+assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
+
+
+def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
+                device: int = 0, rows_per_lane: int = 0) -> np.ndarray:
+    """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
+    direction planes or traceback (synchronous)."""
+    p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
+    ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
+    ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
+    n = len(ts)
+    hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
+    out = np.zeros(max(1, n), SCORE_DTYPE)
+    _check(lib.sa_score_batch(ctypes.byref(p), hp, n, device, out.ctypes.data))
+    return out[:n]
+
+
+class Scorer:
+    """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback)."""
+
+    def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
+                 device: int = 0, rows_per_lane: int = 0):
+        self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
+        arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
+        self.num_pairs = len(pairs)
+        self.pairs = pairs
+        self.device = device
+        h = ctypes.c_void_p()
+        _check(lib.sa_scorer_create(ctypes.byref(self._p), arr, len(pairs), device, ctypes.byref(h)))
+        self.handle = h
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            lib.sa_scorer_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def info(self) -> dict:
+        nw, r, db = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_uint64()
+        _check(lib.sa_scorer_info(self.handle, ctypes.byref(nw), ctypes.byref(r), ctypes.byref(db)))
+        return {"num_waves": nw.value, "rows_per_lane": r.value, "device_bytes": db.value}
+
+    def run(self, d_text: int, d_pattern: int, stream: int | None = None) -> None:
+        _check(lib.sa_scorer_run(self.handle, d_text, d_pattern, stream))
+
+    def results(self, stream: int | None = None) -> np.ndarray:
+        """Every pair's sa_score_result as one numpy structured array (SCORE_DTYPE); synchronises."""
+        out = np.zeros(max(1, self.num_pairs), SCORE_DTYPE)
+        _check(lib.sa_scorer_fetch(self.handle, out.ctypes.data, stream))
+        return out[: self.num_pairs]
+
+
+def search(mode: int, query: np.ndarray, texts: list[np.ndarray], S: np.ndarray, gap: int, k: int,
+           device: int = 0, strings: bool = True) -> tuple[np.ndarray, list[dict]]:
+    """sa_search: `query` (the pattern) against every text. Returns (scores, hits): scores is a
+    SCORE_DTYPE array over the texts; hits holds the min(k, len(texts)) best (score descending, ties
+    to the lower index), each {"index", "score", "num_bytes", "start_text", "start_pattern"} and, with
+    strings, "aligned_text" / "aligned_pattern", as align_pair gives them for that pair."""
+    p, S_keep, alpha_keep = _params(mode, S, gap, None, 0)
+    q = np.ascontiguousarray(query, dtype=np.int8)
+    ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
+    n = len(ts)
+    tp = (ctypes.c_void_p * max(1, n))(*[t.ctypes.data for t in ts])
+    tl = np.array([len(t) for t in ts] or [0], dtype=np.uint64)
+    scores = np.zeros(max(1, n), SCORE_DTYPE)
+    kk = max(1, k)
+    idx = np.zeros(kk, np.int64)
+    res = (SaResult * kk)()
+    cap = max(1, int(tl.max()) + len(q))
+    bufs_t = [ctypes.create_string_buffer(cap) for _ in range(k)] if strings else []
+    bufs_p = [ctypes.create_string_buffer(cap) for _ in range(k)] if strings else []
+    at = (ctypes.c_void_p * kk)(*[ctypes.addressof(b) for b in bufs_t]) if strings else None
+    ap = (ctypes.c_void_p * kk)(*[ctypes.addressof(b) for b in bufs_p]) if strings else None
+    nh = ctypes.c_int64(0)
+    _check(lib.sa_search(ctypes.byref(p), q.ctypes.data, len(q), tp, tl.ctypes.data, n, k, device, scores.ctypes.data,
+                         idx.ctypes.data, res, at, ap, ctypes.byref(nh)))
+    hits = []
+    for h in range(nh.value):
+        r = res[h]
+        d = {"index": int(idx[h]), "score": r.score, "num_bytes": r.num_alignment_bytes, "start_text": r.start_text,
+             "start_pattern": r.start_pattern}
+        if strings:
+            L = r.num_alignment_bytes
+            d["aligned_text"] = bufs_t[h].raw[:L].decode()
+            d["aligned_pattern"] = bufs_p[h].raw[:L].decode()
+        hits.append(d)
+    return scores[:n], hits

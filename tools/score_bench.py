@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Score-only path against the plan path, on one GPU (fails without one).
+
+For each workload, in one process, after a warm-up and alternated round by round, timed with device
+events around steps that end in a synchronise:
+  (a) Scorer.run                      scores and scored cells, no planes
+  (b) Plan.fill alone, and Plan.fill + Plan.traceback: the only way to the same scores without (a)
+and the scores of (a) and (b) are asserted equal at the timed size. Then the forced rows-per-lane
+sweep of the scorer (the numbers behind the automatic rule).
+
+Workloads: `batch` 4096 pairs of 2048 x 2048 DNA, global (bench.py's batch config); `search` one
+512-letter protein query, local, against 20000 seeded texts of 64..2048 letters.
+
+    python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.join(ROOT, "sequence-alignment-gpu_amd", "python"))
+
+
+def blosum50():
+    with open(os.path.join(ROOT, "tests", "golden", "matrices.json")) as f:
+        return np.array(json.load(f)["blosum50"], dtype=np.int32).reshape(23, 23)
+
+
+def workloads(small: bool):
+    from sa_amd import synthetic
+    npairs, side = (256, 2048) if small else (4096, 2048)
+    ta = synthetic.random_sequence(1, npairs * side, 4)
+    pa = synthetic.mutate(ta, 2, 4, npairs * side)
+    yield {"name": "batch", "mode": 0, "S": synthetic.blast_matrix(), "gap": 5, "text": ta, "pattern": pa,
+           "pairs": [(k * side, side, k * side, side) for k in range(npairs)]}
+    ntexts = 2000 if small else 20000
+    rng = np.random.default_rng(9)
+    lens = rng.integers(64, 2049, ntexts)
+    offs = np.concatenate([[0], np.cumsum(lens)])
+    yield {"name": "search", "mode": 1, "S": blosum50(), "gap": 5, "text": synthetic.random_sequence(3, int(offs[-1]), 20),
+           "pattern": synthetic.random_sequence(4, 512, 20),
+           "pairs": [(int(offs[k]), int(lens[k]), 0, 512) for k in range(ntexts)]}
+
+
+def timed(fn, sync) -> float:
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    sync()
+    return e0.elapsed_time(e1)
+
+
+def stats(ms: list[float]) -> dict:
+    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
+            "runs": len(ms)}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "score_bench.json"))
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--small", action="store_true", help="a sixteenth of the batch, a tenth of the texts")
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        print("score_bench: no GPU", file=sys.stderr)
+        return 1
+    from sa_amd import engine
+    report = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "workloads": []}
+    for w in workloads(args.small):
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        cells = sum(p[1] * p[3] for p in w["pairs"])
+        row = {"name": w["name"], "pairs": len(w["pairs"]), "cells": cells}
+        sc = engine.Scorer(w["mode"], w["S"], w["gap"], w["pairs"])
+        row["scorer"] = sc.info()
+        run_a = lambda: sc.run(dt.data_ptr(), dp.data_ptr())  # noqa: E731
+        try:
+            pl = engine.Plan(w["mode"], w["S"], w["gap"], w["pairs"])
+        except engine.SaError as e:
+            pl = None
+            row["plan"] = {"error": str(e)}
+        run_a()
+        a_scores = sc.results()["score"].copy()
+        ta, tf, tft = [], [], []
+        if pl is not None:
+            row["plan"] = pl.info()
+            pl.fill(dt.data_ptr(), dp.data_ptr())
+            pl.traceback()
+            b_scores = pl.results_array()["score"]
+            assert (a_scores == b_scores).all(), f"{w['name']}: scorer and plan scores differ"
+            row["scores_agree"] = True
+        for _ in range(args.rounds):
+            ta.append(timed(run_a, lambda: sc.results()))
+            if pl is not None:
+                tf.append(timed(lambda: pl.fill(dt.data_ptr(), dp.data_ptr()), torch.cuda.synchronize))
+
+                def both():
+                    pl.fill(dt.data_ptr(), dp.data_ptr())
+                    pl.traceback()
+                tft.append(timed(both, lambda: pl.results_array()))
+        row["scorer_run"] = stats(ta)
+        row["scorer_gcups"] = round(cells / statistics.median(ta) / 1e6, 1)
+        if pl is not None:
+            row["plan_fill"] = stats(tf)
+            row["plan_fill_traceback"] = stats(tft)
+            pl.close()
+        sc.close()
+        # the forced rows-per-lane sweep behind the automatic rule
+        sweep = {}
+        for R in (1, 2, 4, 8):
+            s = engine.Scorer(w["mode"], w["S"], w["gap"], w["pairs"], rows_per_lane=R)
+            s.run(dt.data_ptr(), dp.data_ptr())
+            assert (s.results()["score"] == a_scores).all(), f"{w['name']}: R = {R} scores differ"
+            ms = [timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()) for _ in range(max(3, args.rounds))]
+            sweep[str(R)] = dict(stats(ms), num_waves=s.info()["num_waves"])
+            s.close()
+        row["rows_per_lane_sweep"] = sweep
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+        f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
