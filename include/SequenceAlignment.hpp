@@ -140,6 +140,12 @@ uint64_t alignSequenceGPUBatch(const Request *requests, Response *responses, uin
 /// message on stdout.
 uint64_t scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores);
 
+/// Extension: the same under affine gap penalties (sa_score_batch_affine, Gotoh): a gap of k letters
+/// costs gapOpen + (k - 1) * gapExtend and Request::gapPenalty is ignored. One scoring scheme for all
+/// requests, as above. Returns 0, or 1 with the message on stdout.
+uint64_t scoreSequencesGPUAffine(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                 int *scores);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

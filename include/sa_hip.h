@@ -216,7 +216,26 @@ int sa_scorer_fetch(sa_scorer *scorer, sa_score_result *out, void *stream);
 int sa_scorer_info(const sa_scorer *scorer, int64_t *num_waves, int32_t *rows_per_lane, uint64_t *device_bytes);
 int sa_scorer_destroy(sa_scorer *scorer);
 
-/* Score `query` (the pattern) against num_texts texts and align the k best: ranked by score
+/* Affine gap penalties (Gotoh) for the score-only path: a gap of k cells costs
+ * gap_open + (k - 1) * gap_extend, both subtracted as gap_penalty is; params->gap_penalty is ignored.
+ *   E[i][j] = max(E[i][j-1] - gap_extend, H[i][j-1] - gap_open)
+ *   F[i][j] = max(F[i-1][j] - gap_extend, H[i-1][j] - gap_open)
+ *   H[i][j] = max(H[i-1][j-1] + S[p[i-1]][t[j-1]], E[i][j], F[i][j]), local: max(0, .)
+ * with H[0][j] = -(gap_open + (j - 1) gap_extend) (local: 0), likewise H[i][0], H[0][0] = 0. With
+ * gap_open == gap_extend == g this is the linear recurrence of gap penalty g. Results as above; an
+ * empty side scores -(gap_open + (max(m, n) - 1) gap_extend) in global mode (0 when both are empty).
+ * Any int penalties; the limits of the plans apply with |gap_penalty| read as
+ * max(|gap_open|, |gap_extend|) (SA_ERR_UNSUPPORTED). The scorer works with sa_scorer_run, _fetch,
+ * _info and _destroy; pairs may share one pattern (pattern_offset 0 for all): a query against a
+ * database. */
+int sa_score_batch_affine(const sa_params *params, int32_t gap_open, int32_t gap_extend,
+                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_score_result *out);
+int sa_scorer_create_affine(const sa_params *params, int32_t gap_open, int32_t gap_extend,
+                            const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+
+/* Linear gap penalty only: aligning the hits under affine gaps needs an affine traceback, which the
+ * plans do not have (rank with sa_scorer_create_affine instead).
+ * Score `query` (the pattern) against num_texts texts and align the k best: ranked by score
  * descending, ties to the lower index; *num_hits = min(k, num_texts). scores (num_texts entries) may
  * be NULL. hit_index / hit_results: k entries. aligned_text / aligned_pattern: both NULL, or k host
  * buffers each of at least (its hit's text_len + query_len) bytes; buffers sized for the longest text

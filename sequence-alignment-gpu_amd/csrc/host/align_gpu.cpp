@@ -172,7 +172,12 @@ uint64_t SequenceAlignment::alignSequenceGPUFillMicros(const Request &request, R
     return runGPU(request, response, true);
 }
 
-uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
+namespace
+{
+// scoreSequencesGPU and scoreSequencesGPUAffine: `gap` null is the requests' linear gapPenalty, else
+// {gap open, gap extend} and gapPenalty is ignored
+uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
+                       int *scores, const char *name)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -184,16 +189,18 @@ uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t 
             std::cout << "error: only --global and --local alignments are implemented\n";
             return 1;
         }
+        if (gap) params[i].gap_penalty = 0;
         if (!sameScheme(params[0], params[i]))
         {
-            std::cout << "error: scoreSequencesGPU needs one scoring scheme for all requests\n";
+            std::cout << "error: " << name << " needs one scoring scheme for all requests\n";
             return 1;
         }
         pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
                                 requests[i].patternNumBytes};
     }
     std::vector<sa_score_result> res(numRequests);
-    const int rc = sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
+    const int rc = gap ? sa_score_batch_affine(&params[0], gap[0], gap[1], pairs.data(), (int64_t)numRequests, device, res.data())
+                       : sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
     if (rc != SA_OK)
     {
         std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
@@ -201,4 +208,17 @@ uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t 
     }
     for (uint64_t i = 0; i < numRequests; ++i) scores[i] = res[i].score;
     return 0;
+}
+}  // namespace
+
+uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
+{
+    return scoreRequests(requests, numRequests, device, nullptr, scores, "scoreSequencesGPU");
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUAffine(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                    int gapExtend, int *scores)
+{
+    const int gap[2] = {gapOpen, gapExtend};
+    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUAffine");
 }

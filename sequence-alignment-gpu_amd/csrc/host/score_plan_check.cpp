@@ -2,7 +2,8 @@
 // GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
 // the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
 //   sa_score_plan_check --mode global|local|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
-//                       [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--gap-extend E] [--match M --mismatch X] NxM[xCOUNT] ...
+// With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -23,6 +24,8 @@ int main(int argc, char **argv)
     P.alphabet_size = 4;
     P.gap_penalty = 5;
     int cus = 256, match = 5, mismatch = -4;
+    bool affine = false;
+    ScoreGap gapm = {0, 0};
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
     {
@@ -35,6 +38,11 @@ int main(int argc, char **argv)
         }
         else if (a == "--alphabet") P.alphabet_size = std::atoi(value());
         else if (a == "--gap") P.gap_penalty = std::atoi(value());
+        else if (a == "--gap-extend")
+        {
+            affine = true;
+            gapm.extend = std::atoi(value());
+        }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
         else if (a == "--match") match = std::atoi(value());
@@ -63,9 +71,10 @@ int main(int argc, char **argv)
     for (int c = 0; c < a; ++c) S[(size_t)c * a + c] = match;
     P.score_matrix = S.data();
 
+    gapm.open = P.gap_penalty;
     ScorePlan pl;
     std::string err;
-    const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err);
+    const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -73,11 +82,12 @@ int main(int argc, char **argv)
     }
     std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"R\": %d, \"key_rowbits\": %d, \"num_cu\": %d, \"waves_per_simd\": %d, "
                 "\"grid\": %d, \"num_pairs\": %lld, \"max_text\": %llu, \"row_stride\": %llu, \"input_bytes\": %llu, "
-                "\"device_bytes\": %llu, \"padded_cells\": %llu, \"cost\": [%llu, %llu, %llu, %llu], \"order\": [",
+                "\"device_bytes\": %llu, \"padded_cells\": %llu, \"cost\": [%llu, %llu, %llu, %llu], \"affine\": %s, \"gap_extend\": %d, \"order\": [",
                 pl.mode, pl.A, pl.gap, pl.R, pl.key_rowbits, pl.num_cu, pl.waves_per_simd, pl.grid, (long long)pl.num_pairs,
                 (unsigned long long)pl.max_text, (unsigned long long)pl.row_stride, (unsigned long long)pl.input_bytes,
                 (unsigned long long)pl.device_bytes, (unsigned long long)pl.padded_cells, (unsigned long long)pl.cost[0],
-                (unsigned long long)pl.cost[1], (unsigned long long)pl.cost[2], (unsigned long long)pl.cost[3]);
+                (unsigned long long)pl.cost[1], (unsigned long long)pl.cost[2], (unsigned long long)pl.cost[3],
+                pl.affine ? "true" : "false", pl.gap_extend);
     // the order of a large batch is long: the first 64 entries
     for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
     std::printf("]}\n");

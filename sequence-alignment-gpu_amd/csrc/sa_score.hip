@@ -24,30 +24,13 @@
 #include <vector>
 
 #include "sa_hip.h"
+#include "sa_score_args.h"
 #include "sa_score_plan.h"
 #include "sa_wave.h"
 
 namespace sa {
 
 int set_error(int code, const std::string &msg);  // sa_engine.hip: what sa_last_error() reports
-
-struct ScorePair {
-    uint64_t text_off, pattern_off;
-    uint32_t n, m;
-};
-static_assert(sizeof(ScorePair) == 24, "the planner counts 24 bytes per descriptor");
-
-struct ScoreArgs {
-    const int8_t *text, *pattern;
-    const ScorePair *pairs;
-    const int32_t *order;   // work order: pair indices, most cells first
-    const int32_t *table;   // A x A scores, [pattern][text]
-    int32_t *rows;          // one boundary row of row_stride ints per wave
-    sa_score_result *out;
-    uint32_t *ctrl;         // [0] the next position of the work order, [1] bad-input flag
-    int32_t np, A, gap, key_rowbits;
-    uint64_t row_stride;
-};
 
 template <int R, bool LOCAL, bool SMALL>
 __global__ __launch_bounds__(64) void score_kernel(ScoreArgs a)
@@ -322,9 +305,8 @@ void free_scorer(sa_scorer *s)
 
 }  // namespace
 
-extern "C" {
-
-int sa_scorer_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+// sa_scorer_create and sa_scorer_create_affine: `gapm` null is the linear scorer
+static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
     if (!out) return fail_s(SA_ERR_INVALID, "sa_scorer_create: null argument");
     *out = nullptr;
@@ -339,7 +321,7 @@ int sa_scorer_create(const sa_params *P, const sa_pair *pairs, int64_t np, int d
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    if (int rc = make_score_plan(P, pairs, np, cus, score_knobs(), s.get(), &err)) return fail_s(rc, err);
+    if (int rc = make_score_plan(P, pairs, np, cus, score_knobs(), s.get(), &err, gapm)) return fail_s(rc, err);
     std::vector<ScorePair> h((size_t)np);
     for (int64_t p = 0; p < np; ++p)
         h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
@@ -348,7 +330,7 @@ int sa_scorer_create(const sa_params *P, const sa_pair *pairs, int64_t np, int d
     if ((rc = dmalloc_s(&s->d_pairs, h.size() * sizeof(ScorePair)))) return rc;
     if ((rc = dmalloc_s(&s->d_order, (size_t)np * 4))) return rc;
     if ((rc = dmalloc_s(&s->d_table, 32 * 32 * 4))) return rc;
-    if ((rc = dmalloc_s(&s->d_rows, (size_t)s->grid * s->row_stride * 4))) return rc;
+    if ((rc = dmalloc_s(&s->d_rows, (size_t)s->grid * s->row_stride * (s->affine ? 8 : 4)))) return rc;
     if ((rc = dmalloc_s(&s->d_out, (size_t)np * sizeof(sa_score_result)))) return rc;
     if ((rc = dmalloc_s(&s->d_ctrl, 256))) return rc;
     if (np)
@@ -359,6 +341,55 @@ int sa_scorer_create(const sa_params *P, const sa_pair *pairs, int64_t np, int d
     HIP_TRY_S(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
     *out = s.release();
     return SA_OK;
+}
+
+// sa_score_batch and sa_score_batch_affine
+static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_pair *pairs, int64_t np, int device,
+                       sa_score_result *out)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail_s(SA_ERR_INVALID, "sa_score_batch: null argument");
+    std::vector<sa_pair> dp((size_t)np);
+    uint64_t tb = 0, pb = 0;
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
+            return fail_s(SA_ERR_INVALID, "sa_score_batch: null sequence");
+        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
+        tb += pairs[p].text_len;
+        pb += pairs[p].pattern_len;
+    }
+    DevGuard dg(device);
+    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
+    sa_scorer *raw = nullptr;
+    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw)) return rc;
+    std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
+    std::vector<char> ht(tb), hp(pb);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
+        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
+    }
+    DevBuf dt, dpat;
+    int rc;
+    if ((rc = dmalloc_s(&dt.p, tb)) || (rc = dmalloc_s(&dpat.p, pb))) return rc;
+    if (tb) HIP_TRY_S(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
+    if (pb) HIP_TRY_S(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
+    if ((rc = sa_scorer_run(s.get(), dt.p, dpat.p, nullptr))) return rc;
+    return sa_scorer_fetch(s.get(), out, nullptr);
+}
+
+extern "C" {
+
+int sa_scorer_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+{
+    return create_scorer(P, nullptr, pairs, np, device, out);
+}
+
+int sa_scorer_create_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
+                            int device, sa_scorer **out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return create_scorer(P, &gapm, pairs, np, device, out);
 }
 
 int sa_scorer_destroy(sa_scorer *s)
@@ -392,6 +423,12 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     a.key_rowbits = s->key_rowbits;
     a.row_stride = s->row_stride;
     const bool local = s->mode == SA_LOCAL, small = s->A <= 4;
+    if (s->affine)
+    {
+        launch_score_affine(a, s->gap_extend, s->R, local, small, s->grid, st);
+        HIP_TRY_S(hipGetLastError());
+        return SA_OK;
+    }
     switch (s->R)
     {
     case 1: launch_score_r<1>(a, local, small, s->grid, st); break;
@@ -430,35 +467,14 @@ int sa_scorer_info(const sa_scorer *s, int64_t *num_waves, int32_t *rows_per_lan
 
 int sa_score_batch(const sa_params *P, const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
 {
-    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail_s(SA_ERR_INVALID, "sa_score_batch: null argument");
-    std::vector<sa_pair> dp((size_t)np);
-    uint64_t tb = 0, pb = 0;
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
-            return fail_s(SA_ERR_INVALID, "sa_score_batch: null sequence");
-        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
-        tb += pairs[p].text_len;
-        pb += pairs[p].pattern_len;
-    }
-    DevGuard dg(device);
-    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
-    sa_scorer *raw = nullptr;
-    if (int rc = sa_scorer_create(P, dp.data(), np, device, &raw)) return rc;
-    std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
-    std::vector<char> ht(tb), hp(pb);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
-        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
-    }
-    DevBuf dt, dpat;
-    int rc;
-    if ((rc = dmalloc_s(&dt.p, tb)) || (rc = dmalloc_s(&dpat.p, pb))) return rc;
-    if (tb) HIP_TRY_S(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
-    if (pb) HIP_TRY_S(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
-    if ((rc = sa_scorer_run(s.get(), dt.p, dpat.p, nullptr))) return rc;
-    return sa_scorer_fetch(s.get(), out, nullptr);
+    return score_batch(P, nullptr, pairs, np, device, out);
+}
+
+int sa_score_batch_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_host_pair *pairs, int64_t np,
+                          int device, sa_score_result *out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return score_batch(P, &gapm, pairs, np, device, out);
 }
 
 int sa_search(const sa_params *P, const char *query, uint64_t m, const char *const *texts, const uint64_t *text_lens,

@@ -24,6 +24,9 @@ const ScoreKnobs &score_knobs()
 // VGPRs of the SIMD's 512
 int score_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 7 : 8; }
 
+// score_affine_kernel: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4)
+int score_affine_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 5 : 8; }
+
 namespace {
 
 int bitlen(uint64_t v)
@@ -36,7 +39,7 @@ int bitlen(uint64_t v)
 }  // namespace
 
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err)
+                    ScorePlan *out, std::string *err, const ScoreGap *affine)
 {
     auto fail = [&](int code, const char *msg) { *err = msg; return code; };
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
@@ -49,8 +52,14 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     if (R == 16 || R == 32) R = 8;  // a params struct shared with a plan: the scorer's tallest strip
     if (R != 0 && R != 1 && R != 2 && R != 4 && R != 8) return fail(SA_ERR_INVALID, "rows_per_lane must be 0, 1, 2, 4, 8, 16 or 32");
 
-    // ---- the limits of the plans, unchanged ----
-    const int64_t g = P->gap_penalty;
+    // ---- the limits of the plans, unchanged; an affine gap counts as the larger of
+    // |open| and |extend|, and as negative if either is ----
+    int64_t g = P->gap_penalty;
+    if (affine)
+    {
+        g = std::max(std::llabs((long long)affine->open), std::llabs((long long)affine->extend));
+        if (affine->open < 0 || affine->extend < 0) g = -g;
+    }
     int64_t smax = INT32_MIN, sabs = 0;
     for (int e = 0; e < A * A; ++e)
     {
@@ -80,7 +89,9 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
 
     pl.mode = P->mode;
     pl.A = A;
-    pl.gap = (int)g;
+    pl.gap = affine ? affine->open : (int)g;
+    pl.affine = affine != nullptr;
+    pl.gap_extend = affine ? affine->extend : 0;
     pl.num_pairs = np;
     pl.num_cu = kn.max_cus > 0 ? std::min(num_cu, kn.max_cus) : num_cu;
 
@@ -94,12 +105,15 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
 
     // ---- rows per lane: a strip of 64R rows over n columns takes n + 63 steps of
     // kScoreStepBase + R * kScoreStepRow* instructions; the cheapest total wins, ties to the
-    // smaller R (fewer registers, more resident waves) ----
+    // smaller R (fewer registers, more resident waves); the affine kernel has its own counts ----
     static const int kR[4] = {1, 2, 4, 8};
+    const int step_base = affine ? kScoreAffineStepBase : kScoreStepBase;
+    const int step_row = P->mode == SA_LOCAL ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
+                                             : (affine ? kScoreAffineStepRowGlobal : kScoreStepRowGlobal);
     int best = 0;
     for (int k = 0; k < 4; ++k)
     {
-        const uint64_t rows = 64ull * kR[k], per_step = (uint64_t)(kScoreStepBase + kR[k] * (P->mode == SA_LOCAL ? kScoreStepRowLocal : kScoreStepRowGlobal));
+        const uint64_t rows = 64ull * kR[k], per_step = (uint64_t)(step_base + kR[k] * step_row);
         uint64_t c = 0;
         for (int64_t p = 0; p < np; ++p)
         {
@@ -118,11 +132,12 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     }
 
     // ---- launch and workspace ----
-    pl.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, 8) : score_waves_per_simd(pl.R);
+    pl.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, 8)
+                        : affine ? score_affine_waves_per_simd(pl.R) : score_waves_per_simd(pl.R);
     pl.grid = (int)std::min<int64_t>(np, (int64_t)pl.num_cu * 4 * pl.waves_per_simd);
     pl.row_stride = (pl.max_text + 63) / 64 * 64 + 64;
     const uint64_t per_pair = 24 /* descriptor */ + 4 /* order */ + sizeof(sa_score_result);
-    pl.device_bytes = pl.input_bytes + (uint64_t)np * per_pair + (uint64_t)pl.grid * pl.row_stride * 4 +
+    pl.device_bytes = pl.input_bytes + (uint64_t)np * per_pair + (uint64_t)pl.grid * pl.row_stride * (affine ? 8 : 4) +
                       32 * 32 * 4 /* score table */ + 256 /* counter and flags */;
     return SA_OK;
 }

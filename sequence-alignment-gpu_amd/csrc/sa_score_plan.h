@@ -28,13 +28,28 @@ const ScoreKnobs &score_knobs();
 constexpr int kScoreStepBase = 14;
 constexpr int kScoreStepRowGlobal = 6;
 constexpr int kScoreStepRowLocal = 10;
+// The same of score_affine_kernel's steady loop (sa_score_affine.hip): eight lane shifts where the
+// linear kernel has five, and per row the two extra states E and F (two subtractions and a maximum
+// each, where the linear row has two subtractions).
+constexpr int kScoreAffineStepBase = 18;
+constexpr int kScoreAffineStepRowGlobal = 10;
+constexpr int kScoreAffineStepRowLocal = 14;
+
+// The affine gap model of a scorer: a gap of k cells costs open + (k - 1) * extend. With it,
+// sa_params.gap_penalty is ignored.
+struct ScoreGap {
+    int32_t open, extend;
+};
 
 struct ScorePlan {
-    int mode = 0, A = 0, gap = 0, R = 1, key_rowbits = 1;
+    int mode = 0, A = 0, gap = 0, R = 1, key_rowbits = 1;  // gap: the linear penalty, or gap open
+    bool affine = false;           // score_affine_kernel: gap, gap_extend
+    int gap_extend = 0;
     int num_cu = 0, waves_per_simd = 0, grid = 0;
     int64_t num_pairs = 0;
     uint64_t max_text = 0;         // longest text
-    uint64_t row_stride = 0;       // ints of one wave's boundary row (max_text plus padding)
+    uint64_t row_stride = 0;       // columns of one wave's boundary row (max_text plus padding): an int
+                                   // each, affine an (H, F) pair of ints each
     uint64_t input_bytes = 0;      // text and pattern letters of every pair (the caller's arenas)
     uint64_t device_bytes = 0;     // inputs, descriptors, results, row buffers, constants
     uint64_t padded_cells = 0;     // sum of n * ceil(m / 64R) * 64R
@@ -43,12 +58,13 @@ struct ScorePlan {
 };
 
 // Plans `np` pairs for a device of `num_cu` compute units. Returns SA_OK, or the SA_ERR_* code with
-// its message in *err.
+// its message in *err. `affine` null: the linear gap P->gap_penalty; else the affine gap model.
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err);
+                    ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr);
 
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).
 int score_waves_per_simd(int R);
+int score_affine_waves_per_simd(int R);
 
 }  // namespace sa

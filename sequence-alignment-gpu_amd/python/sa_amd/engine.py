@@ -26,7 +26,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_device_count", "sa_last_error", "sa_abi_version", "sa_selftest", "sa_plan_fetch_directions", "sa_release_workspace",
            "sa_plan_output_bytes", "sa_plan_fetch_all", "sa_align_batch", "sa_batch_deal", "sa_build_id",
            "sa_batch_last_stats", "sa_plan_fill_kind", "sa_score_batch", "sa_scorer_create", "sa_scorer_run",
-           "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search")
+           "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search", "sa_score_batch_affine",
+           "sa_scorer_create_affine")
 
 
 class SaParams(ctypes.Structure):
@@ -100,6 +101,9 @@ def _load():
     L.sa_score_batch.argtypes = [ctypes.POINTER(SaParams), P, ctypes.c_int64, I, P]
     L.sa_scorer_create.argtypes = [ctypes.POINTER(SaParams), ctypes.POINTER(SaPair), ctypes.c_int64, I,
                                    ctypes.POINTER(P)]
+    L.sa_score_batch_affine.argtypes = [ctypes.POINTER(SaParams), ctypes.c_int32, ctypes.c_int32, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_affine.argtypes = [ctypes.POINTER(SaParams), ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.POINTER(SaPair), ctypes.c_int64, I, ctypes.POINTER(P)]
     L.sa_scorer_run.argtypes = [P, P, P, P]
     L.sa_scorer_fetch.argtypes = [P, P, P]
     L.sa_scorer_info.argtypes = [P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(U64)]
@@ -311,31 +315,40 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
-                device: int = 0, rows_per_lane: int = 0) -> np.ndarray:
+                device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
-    direction planes or traceback (synchronous)."""
+    direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
+    the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend."""
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
     n = len(ts)
     hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
     out = np.zeros(max(1, n), SCORE_DTYPE)
-    _check(lib.sa_score_batch(ctypes.byref(p), hp, n, device, out.ctypes.data))
+    if gap_extend is None:
+        _check(lib.sa_score_batch(ctypes.byref(p), hp, n, device, out.ctypes.data))
+    else:
+        _check(lib.sa_score_batch_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, out.ctypes.data))
     return out[:n]
 
 
 class Scorer:
-    """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback)."""
+    """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback).
+    With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
-                 device: int = 0, rows_per_lane: int = 0):
+                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None):
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)
         self.pairs = pairs
         self.device = device
         h = ctypes.c_void_p()
-        _check(lib.sa_scorer_create(ctypes.byref(self._p), arr, len(pairs), device, ctypes.byref(h)))
+        if gap_extend is None:
+            _check(lib.sa_scorer_create(ctypes.byref(self._p), arr, len(pairs), device, ctypes.byref(h)))
+        else:
+            _check(lib.sa_scorer_create_affine(ctypes.byref(self._p), gap, gap_extend, arr, len(pairs), device,
+                                               ctypes.byref(h)))
         self.handle = h
 
     def close(self) -> None:

@@ -11,7 +11,14 @@ sweep of the scorer (the numbers behind the automatic rule).
 Workloads: `batch` 4096 pairs of 2048 x 2048 DNA, global (bench.py's batch config); `search` one
 512-letter protein query, local, against 20000 seeded texts of 64..2048 letters.
 
+With --gap-extend E the comparison is another one: the affine scorer (gap open --gap-open, gap extend
+E; sa_scorer_create_affine) against the linear scorer of the same workload, Scorer.run of the two
+alternated round by round in the same process, then the forced rows-per-lane sweep of the affine
+scorer. The report holds the measured affine / linear ratio of the medians next to the ratio of the
+planner's step-cost model. The plan path is not run.
+
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+    python3 tools/score_bench.py --gap-extend 2 [--gap-open 11] --out profiles/r10/score_affine_bench.json
 """
 from __future__ import annotations
 
@@ -63,11 +70,57 @@ def stats(ms: list[float]) -> dict:
             "runs": len(ms)}
 
 
+def model_cost(pairs, R: int, local: bool, affine: bool) -> int:
+    """The planner's instruction count of a workload (sa_score_plan.h: kScoreStep*, kScoreAffineStep*)."""
+    base, row = (18, 14 if local else 10) if affine else (14, 10 if local else 6)
+    return sum((n + 63) * -(-m // (64 * R)) * (base + R * row) for _, n, _, m in pairs if n and m)
+
+
+def affine_rows(args, engine, w, dt, dp) -> dict:
+    """Linear against affine Scorer.run on one workload, alternated; then the affine forced-R sweep."""
+    cells = sum(p[1] * p[3] for p in w["pairs"])
+    local = w["mode"] == 1
+    lin = engine.Scorer(w["mode"], w["S"], w["gap"], w["pairs"])
+    aff = engine.Scorer(w["mode"], w["S"], args.gap_open, w["pairs"], gap_extend=args.gap_extend)
+    row = {"name": w["name"], "pairs": len(w["pairs"]), "cells": cells, "gap": w["gap"], "gap_open": args.gap_open,
+           "gap_extend": args.gap_extend, "linear": lin.info(), "affine": aff.info()}
+    run_l = lambda: lin.run(dt.data_ptr(), dp.data_ptr())  # noqa: E731
+    run_a = lambda: aff.run(dt.data_ptr(), dp.data_ptr())  # noqa: E731
+    run_l()
+    lin.results()
+    run_a()
+    a_scores = aff.results()["score"].copy()
+    tl, ta = [], []
+    for _ in range(args.rounds):
+        tl.append(timed(run_l, lambda: lin.results()))
+        ta.append(timed(run_a, lambda: aff.results()))
+    row["linear_run"], row["affine_run"] = stats(tl), stats(ta)
+    row["linear_gcups"] = round(cells / statistics.median(tl) / 1e6, 1)
+    row["affine_gcups"] = round(cells / statistics.median(ta) / 1e6, 1)
+    row["affine_over_linear"] = round(statistics.median(ta) / statistics.median(tl), 3)
+    row["model_affine_over_linear"] = round(model_cost(w["pairs"], row["affine"]["rows_per_lane"], local, True) /
+                                            model_cost(w["pairs"], row["linear"]["rows_per_lane"], local, False), 3)
+    lin.close()
+    aff.close()
+    sweep = {}
+    for R in (1, 2, 4, 8):
+        s = engine.Scorer(w["mode"], w["S"], args.gap_open, w["pairs"], rows_per_lane=R, gap_extend=args.gap_extend)
+        s.run(dt.data_ptr(), dp.data_ptr())
+        assert (s.results()["score"] == a_scores).all(), f"{w['name']}: affine R = {R} scores differ"
+        ms = [timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()) for _ in range(max(3, args.rounds))]
+        sweep[str(R)] = dict(stats(ms), num_waves=s.info()["num_waves"], model=model_cost(w["pairs"], R, local, True))
+        s.close()
+    row["affine_rows_per_lane_sweep"] = sweep
+    return row
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "score_bench.json"))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--small", action="store_true", help="a sixteenth of the batch, a tenth of the texts")
+    ap.add_argument("--gap-extend", type=int, default=None, help="compare the affine scorer with the linear one")
+    ap.add_argument("--gap-open", type=int, default=11, help="gap-open penalty of the affine scorer")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -77,6 +130,11 @@ def main() -> int:
     report = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "workloads": []}
     for w in workloads(args.small):
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        if args.gap_extend is not None:
+            row = affine_rows(args, engine, w, dt, dp)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+            continue
         cells = sum(p[1] * p[3] for p in w["pairs"])
         row = {"name": w["name"], "pairs": len(w["pairs"]), "cells": cells}
         sc = engine.Scorer(w["mode"], w["S"], w["gap"], w["pairs"])
