@@ -36,14 +36,11 @@
 #include <vector>
 
 #include "sa_hip.h"
+#include "sa_host.h"
 
-namespace sa {
-int set_error(int code, const std::string &msg);  // sa_engine.hip: what sa_last_error() reports
-}
+using sa::fail;
 
 namespace {
-
-int fail_b(int code, const std::string &msg) { return sa::set_error(code, msg); }
 
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
@@ -282,7 +279,7 @@ extern "C" {
 int sa_batch_deal(const uint64_t *cells, int64_t num_pairs, int num_shards, int32_t *shard_of)
 {
     if (num_pairs < 0 || num_shards < 1 || (num_pairs > 0 && (!cells || !shard_of)))
-        return fail_b(SA_ERR_INVALID, "sa_batch_deal: bad argument");
+        return fail(SA_ERR_INVALID, "sa_batch_deal: bad argument");
     bool equal = true;
     for (int64_t i = 1; i < num_pairs; ++i) equal = equal && cells[i] == cells[0];
     if (equal)
@@ -316,20 +313,20 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
                    sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
     if (!P || num_pairs < 0 || num_gpus < 1 || (num_pairs > 0 && (!pairs || !results)))
-        return fail_b(SA_ERR_INVALID, "sa_align_batch: bad argument");
+        return fail(SA_ERR_INVALID, "sa_align_batch: bad argument");
     for (int64_t i = 0; i < num_pairs; ++i)
     {
         const sa_host_pair &h = pairs[i];
         if ((h.text_len && !h.text) || (h.pattern_len && !h.pattern))
-            return fail_b(SA_ERR_INVALID, "sa_align_batch: null sequence");
+            return fail(SA_ERR_INVALID, "sa_align_batch: null sequence");
         for (uint64_t x = 0; x < h.text_len; ++x)
-            if (h.text[x] < 0 || h.text[x] >= P->alphabet_size) return fail_b(SA_ERR_INVALID, "text byte outside the alphabet");
+            if (h.text[x] < 0 || h.text[x] >= P->alphabet_size) return fail(SA_ERR_INVALID, "text byte outside the alphabet");
         for (uint64_t x = 0; x < h.pattern_len; ++x)
-            if (h.pattern[x] < 0 || h.pattern[x] >= P->alphabet_size) return fail_b(SA_ERR_INVALID, "pattern byte outside the alphabet");
+            if (h.pattern[x] < 0 || h.pattern[x] >= P->alphabet_size) return fail(SA_ERR_INVALID, "pattern byte outside the alphabet");
     }
     std::lock_guard<std::mutex> lock(g_batch_mu);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail_b(SA_ERR_HIP, "no HIP device");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(SA_ERR_HIP, "no HIP device");
     int cur = 0;
     (void)hipGetDevice(&cur);
     const int G = (int)std::min<int64_t>(num_gpus, std::max<int64_t>(1, num_pairs));
@@ -373,7 +370,7 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
             (void)hipGetLastError();
             c.st = nullptr;
             restore();
-            return fail_b(SA_ERR_HIP, "sa_align_batch: stream creation failed");
+            return fail(SA_ERR_HIP, "sa_align_batch: stream creation failed");
         }
     }
     std::vector<ncclComm_t> *comms = nullptr;
@@ -383,7 +380,7 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
         if (!R.ok)
         {
             restore();
-            return fail_b(SA_ERR_HIP, "sa_align_batch: " + R.err);
+            return fail(SA_ERR_HIP, "sa_align_batch: " + R.err);
         }
         auto it = g_comms.find(G);
         if (it == g_comms.end())
@@ -394,7 +391,7 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
             if (R.commInitAll(c.data(), G, devs.data()) != ncclSuccess)
             {
                 restore();
-                return fail_b(SA_ERR_HIP, "sa_align_batch: ncclCommInitAll failed");
+                return fail(SA_ERR_HIP, "sa_align_batch: ncclCommInitAll failed");
             }
             it = g_comms.emplace(G, std::move(c)).first;
         }
@@ -405,14 +402,14 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
             if (!ensure(&sh[s].c->d_send, sh[s].c->send_cap, width * sizeof(sa_result)))
             {
                 restore();
-                return fail_b(SA_ERR_NOMEM, "sa_align_batch: RCCL buffer allocation failed");
+                return fail(SA_ERR_NOMEM, "sa_align_batch: RCCL buffer allocation failed");
             }
         }
         (void)hipSetDevice(0);
         if (!ensure(&g_gather, g_gather_cap, (size_t)G * width * sizeof(sa_result)))
         {
             restore();
-            return fail_b(SA_ERR_NOMEM, "sa_align_batch: RCCL buffer allocation failed");
+            return fail(SA_ERR_NOMEM, "sa_align_batch: RCCL buffer allocation failed");
         }
     }
     const bool strings = aligned_text || aligned_pattern;
@@ -426,7 +423,7 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
         if (x.rc)
         {
             restore();
-            return fail_b(x.rc, "sa_align_batch: shard on device " + std::to_string(x.device) + ": " + x.err);
+            return fail(x.rc, "sa_align_batch: shard on device " + std::to_string(x.device) + ": " + x.err);
         }
     // per-pair results: gathered over RCCL (the exchange step) or straight from each shard
     std::vector<sa_result> all;
@@ -457,7 +454,7 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
             // (the failed ones are abandoned, not destroyed: their state is unknown)
             g_comms.erase(G);
             restore();
-            return fail_b(SA_ERR_HIP, "sa_align_batch: RCCL result gather failed");
+            return fail(SA_ERR_HIP, "sa_align_batch: RCCL result gather failed");
         }
         t_last_gather_ms = ms_since(tg);
         t_last_rccl = 1;

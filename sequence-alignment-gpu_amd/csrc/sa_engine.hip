@@ -24,6 +24,7 @@
 #include <utility>
 #include "sa_fill.h"
 #include "sa_hip.h"
+#include "sa_host.h"
 #include "sa_layout.h"
 #include "sa_plan.h"
 #include "sa_walk.h"
@@ -173,51 +174,19 @@ using namespace sa;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
+thread_local std::string g_err;  // what sa_last_error() reports, for every translation unit
 
 }  // namespace
 
 namespace sa {
-int set_error(int code, const std::string &msg) { return fail(code, msg); }
+int set_error(int code, const std::string &msg)
+{
+    g_err = msg;
+    return code;
+}
 }  // namespace sa
 
 namespace {
-
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail(SA_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-// Makes `device` current for a scope and restores the caller's device on every return path.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int device)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
-// Device buffer released on every return path (debug dumps).
-struct DevFree {
-    void operator()(void *p) const { (void)hipFree(p); }
-};
-template <typename T>
-using DevPtr = std::unique_ptr<T, DevFree>;
 
 // SA_DEBUG_SYNC=1: synchronise and check after every launch (names the failing kernel).
 int debug_sync(hipStream_t st, const char *what)
@@ -235,20 +204,6 @@ int check_control(const Control &ctrl, uint32_t epoch)
 {
     if (ctrl.bad_input == epoch) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
     if (ctrl.abort_flag) return fail(SA_ERR_TIMEOUT, "fill aborted: a strip hand-off timed out");
-    return SA_OK;
-}
-
-template <typename T>
-int dmalloc(T **p, size_t bytes)
-{
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc((void **)p, bytes) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return fail(SA_ERR_NOMEM, "device allocation of " + std::to_string(bytes) + " bytes failed");
-    }
     return SA_OK;
 }
 
@@ -309,9 +264,7 @@ void free_plan(sa_plan *p)
 {
     if (!p) return;
     if (p->borrowed) { delete p; return; }
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(p->device);
+    DeviceGuard dg(p->device);
     void *bufs[] = {p->d_pairs, p->d_strips, p->d_prof, p->d_table, p->d_codes, p->d_masks, p->d_bnd,
                     p->d_best, p->d_score, p->d_ctrl, p->d_rec, p->d_heads, p->d_out_text,
                     p->d_out_pattern, p->d_results, p->d_bands, p->d_tbgroups, p->d_tbpg, p->d_tbl,
@@ -320,28 +273,7 @@ void free_plan(sa_plan *p)
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (p->own) (void)hipStreamDestroy(p->own);
-    (void)hipSetDevice(cur);
     delete p;
-}
-
-// Compute units of `device`, cached (hipGetDeviceProperties costs milliseconds per call).
-int device_cus(int device)
-{
-    static std::mutex mu;
-    static std::vector<int> cus;
-    std::lock_guard<std::mutex> lk(mu);
-    if (device >= (int)cus.size()) cus.resize(device + 1, 0);
-    if (cus[device] == 0)
-    {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || v <= 0)
-        {
-            (void)hipGetLastError();
-            v = 256;
-        }
-        cus[device] = v;
-    }
-    return cus[device];
 }
 
 // Per-device state of the one-shot entry point (sa_align_pair, i.e. alignSequenceGPU): a stream,
@@ -377,9 +309,7 @@ std::vector<DeviceCtx *> g_ctx;
 void release_ctx(DeviceCtx *c)
 {
     std::lock_guard<std::mutex> lk(c->mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(c->device);
+    DeviceGuard dg(c->device);
     if (c->arena) (void)hipFree(c->arena);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->bnd) (void)hipFree(c->bnd);
@@ -394,7 +324,6 @@ void release_ctx(DeviceCtx *c)
     c->arena_bytes = 0;
     c->e0 = c->e1 = nullptr;
     c->stream = nullptr;
-    (void)hipSetDevice(cur);
 }
 
 void release_all_ctx()
@@ -780,11 +709,11 @@ int sa_plan_fill(sa_plan *pl, const void *d_text, const void *d_pattern, void *s
         // SA_TIMELINE=<file>: debug dump of per-strip timestamps (s_memrealtime, 100 MHz)
         const char *tlPath = knobs().timeline;
         a.timeline = nullptr;
-        DevPtr<uint64_t> tlBuf;
+        DevBuf<uint64_t> tlBuf;
         if (tlPath)
         {
-            HIP_TRY(hipMalloc((void **)&a.timeline, sizeof(uint64_t) * kTimelineWords * (ns + pl->bands.size())));
-            tlBuf.reset(a.timeline);
+            HIP_TRY(hipMalloc((void **)&tlBuf.p, sizeof(uint64_t) * kTimelineWords * (ns + pl->bands.size())));
+            a.timeline = tlBuf.p;
         }
         if (g.band3) launch_fill_band3(a, pl->mode == SA_LOCAL, g.grid, g.W, st);
         else launch_fill(pl->R, a, pl->mode == SA_LOCAL, g.sk, g.grid, g.W, pl->chain, st);
@@ -817,13 +746,9 @@ int sa_plan_traceback(sa_plan *pl, void *stream)
     const Knobs &kn = knobs();
     // SA_TB_TIMING=<file>: debug dump of per-pair phase timestamps (s_memrealtime, 100 MHz)
     const char *tmPath = kn.tb_timing;
-    uint64_t *timing = nullptr;
-    DevPtr<uint64_t> tmBuf;
-    if (tmPath)
-    {
-        HIP_TRY(hipMalloc((void **)&timing, sizeof(uint64_t) * 9 * np));
-        tmBuf.reset(timing);
-    }
+    DevBuf<uint64_t> tmBuf;
+    if (tmPath) HIP_TRY(hipMalloc((void **)&tmBuf.p, sizeof(uint64_t) * 9 * np));
+    uint64_t *const timing = tmBuf.p;
     // row / column walk (records) + expansion (sa_walk.hip)
     WalkArgs w;
     w.strips = pl->d_strips;
@@ -869,12 +794,12 @@ int sa_plan_traceback(sa_plan *pl, void *stream)
         t.key_rowbits = pl->key_rowbits;
         t.local = pl->mode == SA_LOCAL ? 1 : 0;
         t.dbg = nullptr;
-        DevPtr<uint64_t> dbgBuf;
+        DevBuf<uint64_t> dbgBuf;
         const size_t dbgWords = 12 * pl->strips.size();
         if (kn.tb_table_timing)
         {
-            HIP_TRY(hipMalloc((void **)&t.dbg, sizeof(uint64_t) * dbgWords));
-            dbgBuf.reset(t.dbg);
+            HIP_TRY(hipMalloc((void **)&dbgBuf.p, sizeof(uint64_t) * dbgWords));
+            t.dbg = dbgBuf.p;
             HIP_TRY(hipMemsetAsync(t.dbg, 0, sizeof(uint64_t) * dbgWords, st));
         }
         t.tbl = pl->d_tbl;

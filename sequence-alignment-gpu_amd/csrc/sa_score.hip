@@ -1,18 +1,9 @@
-// Score-only path (sa_hip.h: sa_score_batch, sa_scorer_*, sa_search): the score of every pair and
+// Score-only path (sa_hip.h: sa_score_batch*, sa_scorer_*, sa_search): the score of every pair and
 // the cell it is read from, without direction planes, strip descriptors, records or a traceback.
-//
-// score_kernel<R, LOCAL, SMALL> is persistent with one wave per workgroup. A wave draws the next
-// pair of the work order (sa_score_plan.cpp: most cells first) with one atomicAdd and runs the pair's
-// strips of 64 R rows one after another; no wave ever waits for another wave. Lane l owns rows
-// 64R s + R l + 1 .. + R of strip s and computes, at step t, its R cells of column t - l + 1; H of the
-// row above its first row and the text letter come from lane l - 1 by a DPP shift, everything else
-// stays in registers. The strip's top row H[64R s][1..n] is read from the wave's own row buffer in
-// 64-column bodies (one coalesced dword per lane per 64 steps, shifted to lane 0 one lane per step)
-// and its bottom row is collected from lane 63 the same way and written back in place: the writes
-// trail the reads by at least 63 columns. The recurrence is the reference's
-// (alignSequenceCPU.cpp:175-192, :259-273) in int32; the local result is the first maximum in
-// row-major order, taken as the maximum of the key (H, ~row, ~col) over rows, lanes and strips.
-// DESIGN.md §3.4 has the resource usage of the instances and the rule for R.
+// Here are the two kernels, score_kernel<R, LOCAL, SMALL> (linear gap) and
+// score_affine_kernel<R, LOCAL, SMALL> (gap open / gap extend), both the one wave program of
+// sa_score_wave.h, their launcher, and the host side of both. What a scorer runs is decided in
+// sa_score_plan.cpp (host-only, no HIP).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,190 +15,24 @@
 #include <vector>
 
 #include "sa_hip.h"
-#include "sa_score_args.h"
+#include "sa_host.h"
 #include "sa_score_plan.h"
-#include "sa_wave.h"
+#include "sa_score_wave.h"
 
 namespace sa {
-
-int set_error(int code, const std::string &msg);  // sa_engine.hip: what sa_last_error() reports
 
 template <int R, bool LOCAL, bool SMALL>
 __global__ __launch_bounds__(64) void score_kernel(ScoreArgs a)
 {
     __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    const int lane = threadIdx.x;
-    const int A = a.A, g = a.gap;
-    if (!SMALL)
-    {
-        for (int e = lane; e < A * A; e += kWave) tab[e] = a.table[e];
-        __syncthreads();
-    }
-    int32_t *const rowbuf = a.rows + (uint64_t)blockIdx.x * a.row_stride;
-    const int kb = a.key_rowbits;
-    const uint32_t kmask = (1u << kb) - 1u;
-    bool bad = false;
-    for (;;)
-    {
-        int w = 0;
-        if (lane == 0) w = (int)atomicAdd(&a.ctrl[0], 1u);
-        w = uniform(w);
-        if (w >= a.np) break;
-        const int pi = uniform(a.order[w]);
-        const ScorePair pd = a.pairs[pi];
-        const int n = uniform((int)pd.n), m = uniform((int)pd.m);
-        if (n == 0 || m == 0)
-        {
-            // H[m][n] of an empty side is a run of gaps (alignSequenceCPU.cpp:232-236, :247-248)
-            if (lane == 0)
-            {
-                sa_score_result r;
-                r.score = LOCAL ? 0 : -g * max(n, m);
-                r.status = SA_OK;
-                r.end_text = LOCAL ? 0 : (uint64_t)n;
-                r.end_pattern = LOCAL ? 0 : (uint64_t)m;
-                a.out[pi] = r;
-            }
-            continue;
-        }
-        const int8_t *const text = a.text + pd.text_off;
-        const int8_t *const pattern = a.pattern + pd.pattern_off;
-        const int nstrips = (m + 64 * R - 1) / (64 * R);
-        const int nbodies = (n + 63 + 63) / 64;  // steps 0 .. n + 62
-        int hl[R];  // H[row][column - 1] of the lane's rows; after a strip, H[row][n]
-        uint64_t lanekey = 0;
-        for (int s = 0; s < nstrips; ++s)
-        {
-            const int row1 = s * 64 * R + R * lane;  // rows row1 + 1 .. row1 + R
-            int s0[R], s1[R], s2[R], s3[R];  // S[pattern letter of the row][0..3] (SMALL)
-            int prow[R];               // A * pattern letter of the row (LDS table row)
-            int best[R], bestt[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-            {
-                int c = 0;
-                if (row1 + r < m)
-                {
-                    c = pattern[row1 + r];
-                    bad = bad || c < 0 || c >= A;
-                    c = min(max(c, 0), A - 1);
-                }
-                prow[r] = c * A;
-                if constexpr (SMALL)
-                {
-                    s0[r] = a.table[c * A];
-                    s1[r] = 1 < A ? a.table[c * A + 1] : 0;
-                    s2[r] = 2 < A ? a.table[c * A + 2] : 0;
-                    s3[r] = 3 < A ? a.table[c * A + 3] : 0;
-                }
-                hl[r] = LOCAL ? 0 : -(row1 + r + 1) * g;
-                best[r] = 0;
-                bestt[r] = 0;
-            }
-            int upprev = LOCAL ? 0 : -row1 * g;  // H[row1][column - 1]
-            int tl = 0, ofeed = 0, feed = 0, tfeed = 0;
-            auto step = [&](auto predc, const int t) {
-                constexpr bool PRED = decltype(predc)::value;
-                const int up = dpp_shr1(feed, hl[R - 1]);  // lane 0: the top row's next column
-                tl = dpp_shr1(tfeed, tl);                  // lane 0: the next text letter
-                feed = dpp_shl1(feed, feed);
-                tfeed = dpp_shl1(tfeed, tfeed);
-                // ramp-up and ramp-down bodies: a lane outside columns 1..n keeps its state
-                const bool valid = !PRED || (unsigned)(t - lane) < (unsigned)n;
-                const bool b0 = (tl & 1) != 0, b1 = (tl & 2) != 0;
-                int d = upprev, u = up;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                {
-                    int sv;
-                    if constexpr (SMALL)
-                    {
-                        const int x0 = s0[r], x1 = s1[r], x2 = s2[r], x3 = s3[r];
-                        sv = b1 ? (b0 ? x3 : x2) : (b0 ? x1 : x0);
-                    }
-                    else sv = tab[prow[r] + tl];
-                    int h = max(d + sv, max(hl[r] - g, u - g));
-                    if (LOCAL) h = max(h, 0);
-                    d = hl[r];
-                    if (PRED) h = valid ? h : hl[r];
-                    if (LOCAL)
-                    {
-                        // a row meets its columns in ascending order: strictly greater keeps the first
-                        const bool better = h > best[r];
-                        best[r] = better ? h : best[r];
-                        bestt[r] = better ? t : bestt[r];
-                    }
-                    hl[r] = h;
-                    u = h;
-                }
-                upprev = valid ? up : upprev;
-                ofeed = dpp_shl1(hl[R - 1], ofeed);  // lane 63's bottom-row value enters, the rest move down
-            };
-            for (int b = 0; b < nbodies; ++b)
-            {
-                const int c0 = 64 * b + lane;  // text index of tfeed; feed holds column c0 + 1
-                tfeed = 0;
-                if (c0 < n)
-                {
-                    const int c = text[c0];
-                    bad = bad || c < 0 || c >= A;
-                    tfeed = min(max(c, 0), A - 1);
-                }
-                if (s == 0) feed = LOCAL ? 0 : -(c0 + 1) * g;
-                else feed = c0 < n ? rowbuf[c0] : 0;
-                if (b == 0 || 64 * b + 64 > n)
-                {
-#pragma unroll 2
-                    for (int k = 0; k < 64; ++k) step(std::true_type{}, 64 * b + k);
-                }
-                else
-                {
-#pragma unroll 4
-                    for (int k = 0; k < 64; ++k) step(std::false_type{}, 64 * b + k);
-                }
-                // the 64 values lane 63 produced in this body: columns 64 b - 62 .. 64 b + 1, all read before
-                if (s + 1 < nstrips)
-                {
-                    const int col = 64 * b - 62 + lane;
-                    if (col >= 1 && col <= n) rowbuf[col - 1] = ofeed;
-                }
-            }
-            if (LOCAL)
-            {
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                {
-                    const int row = row1 + r + 1, col = bestt[r] - lane + 1;
-                    const uint64_t key = ((uint64_t)(uint32_t)best[r] << (2 * kb)) |
-                                         ((uint64_t)(~(uint32_t)row & kmask) << kb) | (uint64_t)(~(uint32_t)col & kmask);
-                    if (row <= m && best[r] > 0 && key > lanekey) lanekey = key;
-                }
-            }
-        }
-        sa_score_result res;
-        res.status = SA_OK;
-        if (LOCAL)
-        {
-            const uint64_t key = wave_max_u64(lanekey);
-            const uint32_t H = (uint32_t)(key >> (2 * kb));
-            res.score = (int32_t)H;
-            res.end_pattern = H ? (uint64_t)(~(uint32_t)(key >> kb) & kmask) : 0;
-            res.end_text = H ? (uint64_t)(~(uint32_t)key & kmask) : 0;
-        }
-        else
-        {
-            const int last = m - 1 - (nstrips - 1) * 64 * R;  // row m inside the last strip
-            const int rm = last % R;
-            int v = hl[0];
-#pragma unroll
-            for (int r = 1; r < R; ++r) v = r == rm ? hl[r] : v;
-            res.score = __builtin_amdgcn_readlane(v, last / R);
-            res.end_text = (uint64_t)n;
-            res.end_pattern = (uint64_t)m;
-        }
-        if (lane == 0) a.out[pi] = res;
-    }
-    if (bad) __hip_atomic_store(&a.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    score_wave<false, R, LOCAL, SMALL>(a, 0, tab);
+}
+
+template <int R, bool LOCAL, bool SMALL>
+__global__ __launch_bounds__(64) void score_affine_kernel(ScoreAffineArgs aa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, R, LOCAL, SMALL>(aa.s, aa.gap_extend, tab);
 }
 
 }  // namespace sa
@@ -219,66 +44,32 @@ using namespace sa;
 
 namespace {
 
-int fail_s(int code, const std::string &msg) { return sa::set_error(code, msg); }
-
-#define HIP_TRY_S(expr)                                                                        \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return fail_s(SA_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DevGuard(int device)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DevGuard(const DevGuard &) = delete;
-    DevGuard &operator=(const DevGuard &) = delete;
-};
-
-template <typename T>
-int dmalloc_s(T **p, size_t bytes)
+// score_kernel or, with AFFINE, score_affine_kernel on `grid` one-wave workgroups: the one place that
+// picks <R, LOCAL, SMALL>. R is 1, 2, 4 or 8; a.gap is the linear penalty or the gap-open penalty.
+template <bool AFFINE>
+void launch_score(const ScoreArgs &a, int gap_extend, int R, bool local, bool small, int grid, hipStream_t st)
 {
-    *p = nullptr;
-    if (hipMalloc((void **)p, std::max<size_t>(bytes, 16)) != hipSuccess)
+    const ScoreAffineArgs aa = {a, gap_extend};
+    auto launch = [&](auto rc, auto localc, auto smallc) {
+        constexpr int RR = decltype(rc)::value;
+        constexpr bool LOCAL = decltype(localc)::value, SMALL = decltype(smallc)::value;
+        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, LOCAL, SMALL>), dim3(grid), dim3(64), 0, st, aa);
+        else hipLaunchKernelGGL((score_kernel<RR, LOCAL, SMALL>), dim3(grid), dim3(64), 0, st, a);
+    };
+    auto with_r = [&](auto rc) {
+        const std::true_type yes;
+        const std::false_type no;
+        if (local) small ? launch(rc, yes, yes) : launch(rc, yes, no);
+        else small ? launch(rc, no, yes) : launch(rc, no, no);
+    };
+    switch (R)
     {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return fail_s(SA_ERR_NOMEM, "device allocation of " + std::to_string(bytes) + " bytes failed");
-    }
-    return SA_OK;
-}
-
-template <int R>
-void launch_score_r(const ScoreArgs &a, bool local, bool small, int grid, hipStream_t st)
-{
-    if (local)
-    {
-        if (small) hipLaunchKernelGGL((score_kernel<R, true, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((score_kernel<R, true, false>), dim3(grid), dim3(64), 0, st, a);
-    }
-    else
-    {
-        if (small) hipLaunchKernelGGL((score_kernel<R, false, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((score_kernel<R, false, false>), dim3(grid), dim3(64), 0, st, a);
+    case 1: with_r(std::integral_constant<int, 1>{}); break;
+    case 2: with_r(std::integral_constant<int, 2>{}); break;
+    case 4: with_r(std::integral_constant<int, 4>{}); break;
+    default: with_r(std::integral_constant<int, 8>{}); break;
     }
 }
-
-// Device buffer freed on every return path of the one-shot calls.
-struct DevBuf {
-    char *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-};
 
 }  // namespace
 
@@ -296,7 +87,7 @@ namespace {
 void free_scorer(sa_scorer *s)
 {
     if (!s) return;
-    DevGuard dg(s->device);
+    DeviceGuard dg(s->device);
     void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -308,37 +99,31 @@ void free_scorer(sa_scorer *s)
 // sa_scorer_create and sa_scorer_create_affine: `gapm` null is the linear scorer
 static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
-    if (!out) return fail_s(SA_ERR_INVALID, "sa_scorer_create: null argument");
+    if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create: null argument");
     *out = nullptr;
-    DevGuard dg(device);
-    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
-    {
-        (void)hipGetLastError();
-        cus = 256;
-    }
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    if (int rc = make_score_plan(P, pairs, np, cus, score_knobs(), s.get(), &err, gapm)) return fail_s(rc, err);
+    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm)) return fail(rc, err);
     std::vector<ScorePair> h((size_t)np);
     for (int64_t p = 0; p < np; ++p)
         h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
     const int A = s->A;
     int rc;
-    if ((rc = dmalloc_s(&s->d_pairs, h.size() * sizeof(ScorePair)))) return rc;
-    if ((rc = dmalloc_s(&s->d_order, (size_t)np * 4))) return rc;
-    if ((rc = dmalloc_s(&s->d_table, 32 * 32 * 4))) return rc;
-    if ((rc = dmalloc_s(&s->d_rows, (size_t)s->grid * s->row_stride * (s->affine ? 8 : 4)))) return rc;
-    if ((rc = dmalloc_s(&s->d_out, (size_t)np * sizeof(sa_score_result)))) return rc;
-    if ((rc = dmalloc_s(&s->d_ctrl, 256))) return rc;
+    if ((rc = dmalloc(&s->d_pairs, h.size() * sizeof(ScorePair)))) return rc;
+    if ((rc = dmalloc(&s->d_order, (size_t)np * 4))) return rc;
+    if ((rc = dmalloc(&s->d_table, 32 * 32 * 4))) return rc;
+    if ((rc = dmalloc(&s->d_rows, (size_t)s->grid * s->row_stride * (s->affine ? 8 : 4)))) return rc;
+    if ((rc = dmalloc(&s->d_out, (size_t)np * sizeof(sa_score_result)))) return rc;
+    if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
     if (np)
     {
-        HIP_TRY_S(hipMemcpy(s->d_pairs, h.data(), h.size() * sizeof(ScorePair), hipMemcpyHostToDevice));
-        HIP_TRY_S(hipMemcpy(s->d_order, s->order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_pairs, h.data(), h.size() * sizeof(ScorePair), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_order, s->order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY_S(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
     *out = s.release();
     return SA_OK;
 }
@@ -347,19 +132,19 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
 static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_pair *pairs, int64_t np, int device,
                        sa_score_result *out)
 {
-    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail_s(SA_ERR_INVALID, "sa_score_batch: null argument");
+    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch: null argument");
     std::vector<sa_pair> dp((size_t)np);
     uint64_t tb = 0, pb = 0;
     for (int64_t p = 0; p < np; ++p)
     {
         if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
-            return fail_s(SA_ERR_INVALID, "sa_score_batch: null sequence");
+            return fail(SA_ERR_INVALID, "sa_score_batch: null sequence");
         dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
         tb += pairs[p].text_len;
         pb += pairs[p].pattern_len;
     }
-    DevGuard dg(device);
-    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     sa_scorer *raw = nullptr;
     if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
@@ -369,11 +154,11 @@ static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_p
         if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
         if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
     }
-    DevBuf dt, dpat;
+    DevBuf<char> dt, dpat;
     int rc;
-    if ((rc = dmalloc_s(&dt.p, tb)) || (rc = dmalloc_s(&dpat.p, pb))) return rc;
-    if (tb) HIP_TRY_S(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
-    if (pb) HIP_TRY_S(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
+    if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
+    if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
+    if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
     if ((rc = sa_scorer_run(s.get(), dt.p, dpat.p, nullptr))) return rc;
     return sa_scorer_fetch(s.get(), out, nullptr);
 }
@@ -400,12 +185,12 @@ int sa_scorer_destroy(sa_scorer *s)
 
 int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void *stream)
 {
-    if (!s || ((!d_text || !d_pattern) && s->input_bytes)) return fail_s(SA_ERR_INVALID, "sa_scorer_run: null argument");
-    DevGuard dg(s->device);
-    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
+    if (!s || ((!d_text || !d_pattern) && s->input_bytes)) return fail(SA_ERR_INVALID, "sa_scorer_run: null argument");
+    DeviceGuard dg(s->device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     // the run's first enqueued operation: the work counter and the bad-input flag at zero
-    HIP_TRY_S(hipMemsetAsync(s->d_ctrl, 0, 256, st));
+    HIP_TRY(hipMemsetAsync(s->d_ctrl, 0, 256, st));
     s->ran = true;
     if (s->num_pairs == 0) return SA_OK;
     ScoreArgs a;
@@ -423,42 +208,31 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     a.key_rowbits = s->key_rowbits;
     a.row_stride = s->row_stride;
     const bool local = s->mode == SA_LOCAL, small = s->A <= 4;
-    if (s->affine)
-    {
-        launch_score_affine(a, s->gap_extend, s->R, local, small, s->grid, st);
-        HIP_TRY_S(hipGetLastError());
-        return SA_OK;
-    }
-    switch (s->R)
-    {
-    case 1: launch_score_r<1>(a, local, small, s->grid, st); break;
-    case 2: launch_score_r<2>(a, local, small, s->grid, st); break;
-    case 4: launch_score_r<4>(a, local, small, s->grid, st); break;
-    default: launch_score_r<8>(a, local, small, s->grid, st); break;
-    }
-    HIP_TRY_S(hipGetLastError());
+    if (s->affine) launch_score<true>(a, s->gap_extend, s->R, local, small, s->grid, st);
+    else launch_score<false>(a, 0, s->R, local, small, s->grid, st);
+    HIP_TRY(hipGetLastError());
     return SA_OK;
 }
 
 int sa_scorer_fetch(sa_scorer *s, sa_score_result *out, void *stream)
 {
-    if (!s || (!out && s->num_pairs)) return fail_s(SA_ERR_INVALID, "sa_scorer_fetch: null argument");
-    if (!s->ran) return fail_s(SA_ERR_INVALID, "sa_scorer_fetch: the scorer has not been run");
-    DevGuard dg(s->device);
-    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
+    if (!s || (!out && s->num_pairs)) return fail(SA_ERR_INVALID, "sa_scorer_fetch: null argument");
+    if (!s->ran) return fail(SA_ERR_INVALID, "sa_scorer_fetch: the scorer has not been run");
+    DeviceGuard dg(s->device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     uint32_t ctrl[2] = {0, 0};
-    HIP_TRY_S(hipMemcpyAsync(ctrl, s->d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctrl, s->d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
     if (s->num_pairs)
-        HIP_TRY_S(hipMemcpyAsync(out, s->d_out, (size_t)s->num_pairs * sizeof(sa_score_result), hipMemcpyDeviceToHost, st));
-    HIP_TRY_S(hipStreamSynchronize(st));
-    if (ctrl[1]) return fail_s(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+        HIP_TRY(hipMemcpyAsync(out, s->d_out, (size_t)s->num_pairs * sizeof(sa_score_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
     return SA_OK;
 }
 
 int sa_scorer_info(const sa_scorer *s, int64_t *num_waves, int32_t *rows_per_lane, uint64_t *device_bytes)
 {
-    if (!s) return fail_s(SA_ERR_INVALID, "sa_scorer_info: null scorer");
+    if (!s) return fail(SA_ERR_INVALID, "sa_scorer_info: null scorer");
     if (num_waves) *num_waves = s->grid;
     if (rows_per_lane) *rows_per_lane = s->R;
     if (device_bytes) *device_bytes = s->device_bytes;
@@ -483,21 +257,21 @@ int sa_search(const sa_params *P, const char *query, uint64_t m, const char *con
 {
     if (!P || nt < 0 || k < 0 || (m && !query) || (nt > 0 && (!texts || !text_lens)) || !num_hits ||
         (k > 0 && (!hit_index || !hit_results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
-        return fail_s(SA_ERR_INVALID, "sa_search: bad argument");
+        return fail(SA_ERR_INVALID, "sa_search: bad argument");
     *num_hits = 0;
-    DevGuard dg(device);
-    if (!dg.ok) return fail_s(SA_ERR_HIP, "hipSetDevice failed");
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     // every text against the one copy of the query
     std::vector<sa_pair> dp((size_t)nt);
     uint64_t tb = 0;
     for (int64_t i = 0; i < nt; ++i)
     {
-        if (text_lens[i] && !texts[i]) return fail_s(SA_ERR_INVALID, "sa_search: null text");
+        if (text_lens[i] && !texts[i]) return fail(SA_ERR_INVALID, "sa_search: null text");
         dp[i] = sa_pair{tb, text_lens[i], 0, m};
         tb += text_lens[i];
     }
     std::vector<sa_score_result> sc((size_t)nt);
-    DevBuf dt, dq;
+    DevBuf<char> dt, dq;
     int rc;
     {
         sa_scorer *raw = nullptr;
@@ -506,9 +280,9 @@ int sa_search(const sa_params *P, const char *query, uint64_t m, const char *con
         std::vector<char> ht(tb);
         for (int64_t i = 0; i < nt; ++i)
             if (text_lens[i]) std::memcpy(ht.data() + dp[i].text_offset, texts[i], text_lens[i]);
-        if ((rc = dmalloc_s(&dt.p, tb)) || (rc = dmalloc_s(&dq.p, m))) return rc;
-        if (tb) HIP_TRY_S(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
-        if (m) HIP_TRY_S(hipMemcpy(dq.p, query, m, hipMemcpyHostToDevice));
+        if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dq.p, m))) return rc;
+        if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
+        if (m) HIP_TRY(hipMemcpy(dq.p, query, m, hipMemcpyHostToDevice));
         if ((rc = sa_scorer_run(s.get(), dt.p, dq.p, nullptr))) return rc;
         if ((rc = sa_scorer_fetch(s.get(), sc.data(), nullptr))) return rc;
     }

@@ -1,0 +1,304 @@
+// The wave program of the score-only kernels (sa_score.hip): score_kernel (linear gap) and
+// score_affine_kernel (gap open / gap extend) are both score_wave, without and with AFFINE.
+//
+// The kernels are persistent with one wave per workgroup. A wave draws the next pair of the work
+// order (sa_score_plan.cpp: most cells first) with one atomicAdd and runs the pair's strips of 64 R
+// rows one after another; no wave ever waits for another wave. Lane l owns rows
+// 64R s + R l + 1 .. + R of strip s and computes, at step t, its R cells of column t - l + 1; H of the
+// row above its first row and the text letter come from lane l - 1 by a DPP shift, everything else
+// stays in registers. The strip's top row H[64R s][1..n] is read from the wave's own row buffer in
+// 64-column bodies (one coalesced access per lane per 64 steps, shifted to lane 0 one lane per step)
+// and its bottom row is collected from lane 63 the same way and written back in place: the writes
+// trail the reads by at least 63 columns. The linear recurrence is the reference's
+// (alignSequenceCPU.cpp:175-192, :259-273) in int32; the local result is the first maximum in
+// row-major order, taken as the maximum of the key (H, ~row, ~col) over rows, lanes and strips.
+//
+// AFFINE is Gotoh's three-state recurrence, a gap of k cells costing gap_open + (k - 1) gap_extend:
+//
+//   E[i][j] = max(E[i][j-1] - ge, H[i][j-1] - go)      gap run along the row
+//   F[i][j] = max(F[i-1][j] - ge, H[i-1][j] - go)      gap run along the column
+//   H[i][j] = max(H[i-1][j-1] + S[p[i-1]][t[j-1]], E[i][j], F[i][j])      local: max(0, .)
+//
+// Per row a lane also keeps E[row][column - 1]; F runs down the lane's R rows inside a step, and the
+// lane above hands down H and F of its bottom row (two DPP shifts where the linear kernel has one).
+// The boundary row then holds (H, F) of the strip's bottom row, two ints per column, read and
+// written as one 8-byte access under the same in-place rule. The borders need no minus infinity:
+// E[i][0] := H[i][0] - go + ge and F[0][j] := H[0][j] - go + ge make the first step of a run yield
+// H - go from both branches.
+// DESIGN.md §3.4 has the resource usage of the instances, the rule for R and the step costs the
+// planner uses.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "sa_hip.h"
+#include "sa_wave.h"
+
+namespace sa {
+
+struct ScorePair {
+    uint64_t text_off, pattern_off;
+    uint32_t n, m;
+};
+static_assert(sizeof(ScorePair) == 24, "the planner counts 24 bytes per descriptor");
+
+struct ScoreArgs {
+    const int8_t *text, *pattern;
+    const ScorePair *pairs;
+    const int32_t *order;   // work order: pair indices, most cells first
+    const int32_t *table;   // A x A scores, [pattern][text]
+    int32_t *rows;          // one boundary row per wave: row_stride ints (affine: row_stride (H, F) pairs)
+    sa_score_result *out;
+    uint32_t *ctrl;         // [0] the next position of the work order, [1] bad-input flag
+    int32_t np, A, gap, key_rowbits;  // gap: the linear penalty, or the affine gap-open penalty
+    uint64_t row_stride;
+};
+
+struct ScoreAffineArgs {
+    ScoreArgs s;
+    int32_t gap_extend;
+};
+
+// `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
+// registers); `gap_extend` is read only by AFFINE.
+template <bool AFFINE, int R, bool LOCAL, bool SMALL>
+__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab)
+{
+    using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
+    const int lane = threadIdx.x;
+    const int A = a.A, g = a.gap, ge = gap_extend;
+    if (!SMALL)
+    {
+        for (int e = lane; e < A * A; e += kWave) tab[e] = a.table[e];
+        __syncthreads();
+    }
+    Col *const rowbuf = (Col *)a.rows + (uint64_t)blockIdx.x * a.row_stride;
+    const int kb = a.key_rowbits;
+    const uint32_t kmask = (1u << kb) - 1u;
+    bool bad = false;
+    for (;;)
+    {
+        int w = 0;
+        if (lane == 0) w = (int)atomicAdd(&a.ctrl[0], 1u);
+        w = uniform(w);
+        if (w >= a.np) break;
+        const int pi = uniform(a.order[w]);
+        const ScorePair pd = a.pairs[pi];
+        const int n = uniform((int)pd.n), m = uniform((int)pd.m);
+        if (n == 0 || m == 0)
+        {
+            // H[m][n] of an empty side is one run of max(n, m) gaps (alignSequenceCPU.cpp:232-236, :247-248)
+            if (lane == 0)
+            {
+                const int k = max(n, m);
+                sa_score_result r;
+                if constexpr (AFFINE) r.score = LOCAL || k == 0 ? 0 : -(g + (k - 1) * ge);
+                else r.score = LOCAL ? 0 : -g * k;
+                r.status = SA_OK;
+                r.end_text = LOCAL ? 0 : (uint64_t)n;
+                r.end_pattern = LOCAL ? 0 : (uint64_t)m;
+                a.out[pi] = r;
+            }
+            continue;
+        }
+        const int8_t *const text = a.text + pd.text_off;
+        const int8_t *const pattern = a.pattern + pd.pattern_off;
+        const int nstrips = (m + 64 * R - 1) / (64 * R);
+        const int nbodies = (n + 63 + 63) / 64;  // steps 0 .. n + 62
+        int hl[R];  // H[row][column - 1] of the lane's rows; after a strip, H[row][n]
+        uint64_t lanekey = 0;
+        for (int s = 0; s < nstrips; ++s)
+        {
+            const int row1 = s * 64 * R + R * lane;  // rows row1 + 1 .. row1 + R
+            int s0[R], s1[R], s2[R], s3[R];  // S[pattern letter of the row][0..3] (SMALL)
+            int prow[R];               // A * pattern letter of the row (LDS table row)
+            int el[R];                 // AFFINE: E[row][column - 1]
+            int best[R], bestt[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+            {
+                int c = 0;
+                if (row1 + r < m)
+                {
+                    c = pattern[row1 + r];
+                    bad = bad || c < 0 || c >= A;
+                    c = min(max(c, 0), A - 1);
+                }
+                prow[r] = c * A;
+                if constexpr (SMALL)
+                {
+                    s0[r] = a.table[c * A];
+                    s1[r] = 1 < A ? a.table[c * A + 1] : 0;
+                    s2[r] = 2 < A ? a.table[c * A + 2] : 0;
+                    s3[r] = 3 < A ? a.table[c * A + 3] : 0;
+                }
+                // H[row][0], row = row1 + r + 1
+                if constexpr (AFFINE)
+                {
+                    hl[r] = LOCAL ? 0 : -(g + (row1 + r) * ge);
+                    el[r] = hl[r] - g + ge;  // stands for E[row][0] = -infinity
+                }
+                else hl[r] = LOCAL ? 0 : -(row1 + r + 1) * g;
+                best[r] = 0;
+                bestt[r] = 0;
+            }
+            int upprev;  // H[row1][column - 1]
+            if constexpr (AFFINE) upprev = LOCAL || row1 == 0 ? 0 : -(g + (row1 - 1) * ge);
+            else upprev = LOCAL ? 0 : -row1 * g;
+            int tl = 0, tfeed = 0, feed = 0, ofeed = 0;
+            int fb = 0;                  // AFFINE: F[row1 + R][column] of the lane's last step,
+            int feedf = 0, ofeedf = 0;   // and the F halves of the top-row feed and the bottom-row collection
+            auto step = [&](auto predc, const int t) {
+                constexpr bool PRED = decltype(predc)::value;
+                const int up = dpp_shr1(feed, hl[R - 1]);  // lane 0: the top row's next column
+                int upf = 0;
+                if constexpr (AFFINE) upf = dpp_shr1(feedf, fb);  // and its F
+                tl = dpp_shr1(tfeed, tl);                  // lane 0: the next text letter
+                feed = dpp_shl1(feed, feed);
+                if constexpr (AFFINE) feedf = dpp_shl1(feedf, feedf);
+                tfeed = dpp_shl1(tfeed, tfeed);
+                // ramp-up and ramp-down bodies: a lane outside columns 1..n keeps its state
+                const bool valid = !PRED || (unsigned)(t - lane) < (unsigned)n;
+                const bool b0 = (tl & 1) != 0, b1 = (tl & 2) != 0;
+                int d = upprev, u = up, uf = upf;
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                {
+                    int sv;
+                    if constexpr (SMALL)
+                    {
+                        const int x0 = s0[r], x1 = s1[r], x2 = s2[r], x3 = s3[r];
+                        sv = b1 ? (b0 ? x3 : x2) : (b0 ? x1 : x0);
+                    }
+                    else sv = tab[prow[r] + tl];
+                    int h, e = 0, f = 0;
+                    if constexpr (AFFINE)
+                    {
+                        e = max(el[r] - ge, hl[r] - g);
+                        f = max(uf - ge, u - g);
+                        h = max(d + sv, max(e, f));
+                    }
+                    else h = max(d + sv, max(hl[r] - g, u - g));
+                    if (LOCAL) h = max(h, 0);
+                    d = hl[r];
+                    if (PRED)
+                    {
+                        h = valid ? h : hl[r];
+                        if constexpr (AFFINE) e = valid ? e : el[r];
+                    }
+                    if (LOCAL)
+                    {
+                        // a row meets its columns in ascending order: strictly greater keeps the first
+                        const bool better = h > best[r];
+                        best[r] = better ? h : best[r];
+                        bestt[r] = better ? t : bestt[r];
+                    }
+                    hl[r] = h;
+                    u = h;
+                    if constexpr (AFFINE)
+                    {
+                        el[r] = e;
+                        uf = f;
+                    }
+                }
+                upprev = valid ? up : upprev;
+                // lane 63's bottom-row value enters, the rest move down
+                ofeed = dpp_shl1(hl[R - 1], ofeed);
+                if constexpr (AFFINE)
+                {
+                    fb = valid ? uf : fb;
+                    ofeedf = dpp_shl1(fb, ofeedf);
+                }
+            };
+            for (int b = 0; b < nbodies; ++b)
+            {
+                const int c0 = 64 * b + lane;  // text index of tfeed; feed holds column c0 + 1
+                tfeed = 0;
+                if (c0 < n)
+                {
+                    const int c = text[c0];
+                    bad = bad || c < 0 || c >= A;
+                    tfeed = min(max(c, 0), A - 1);
+                }
+                if constexpr (AFFINE)
+                {
+                    if (s == 0)
+                    {
+                        feed = LOCAL ? 0 : -(g + c0 * ge);  // H[0][c0 + 1]
+                        feedf = feed - g + ge;              // stands for F[0][c0 + 1] = -infinity
+                    }
+                    else
+                    {
+                        const int2 v = c0 < n ? rowbuf[c0] : make_int2(0, 0);
+                        feed = v.x;
+                        feedf = v.y;
+                    }
+                }
+                else
+                {
+                    if (s == 0) feed = LOCAL ? 0 : -(c0 + 1) * g;
+                    else feed = c0 < n ? rowbuf[c0] : 0;
+                }
+                if (b == 0 || 64 * b + 64 > n)
+                {
+#pragma unroll 2
+                    for (int k = 0; k < 64; ++k) step(std::true_type{}, 64 * b + k);
+                }
+                else
+                {
+#pragma unroll 4
+                    for (int k = 0; k < 64; ++k) step(std::false_type{}, 64 * b + k);
+                }
+                // the 64 values lane 63 produced in this body: columns 64 b - 62 .. 64 b + 1, all read before
+                if (s + 1 < nstrips)
+                {
+                    const int col = 64 * b - 62 + lane;
+                    if (col >= 1 && col <= n)
+                    {
+                        if constexpr (AFFINE) rowbuf[col - 1] = make_int2(ofeed, ofeedf);
+                        else rowbuf[col - 1] = ofeed;
+                    }
+                }
+            }
+            if (LOCAL)
+            {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                {
+                    const int row = row1 + r + 1, col = bestt[r] - lane + 1;
+                    const uint64_t key = ((uint64_t)(uint32_t)best[r] << (2 * kb)) |
+                                         ((uint64_t)(~(uint32_t)row & kmask) << kb) | (uint64_t)(~(uint32_t)col & kmask);
+                    if (row <= m && best[r] > 0 && key > lanekey) lanekey = key;
+                }
+            }
+        }
+        sa_score_result res;
+        res.status = SA_OK;
+        if (LOCAL)
+        {
+            const uint64_t key = wave_max_u64(lanekey);
+            const uint32_t H = (uint32_t)(key >> (2 * kb));
+            res.score = (int32_t)H;
+            res.end_pattern = H ? (uint64_t)(~(uint32_t)(key >> kb) & kmask) : 0;
+            res.end_text = H ? (uint64_t)(~(uint32_t)key & kmask) : 0;
+        }
+        else
+        {
+            const int last = m - 1 - (nstrips - 1) * 64 * R;  // row m inside the last strip
+            const int rm = last % R;
+            int v = hl[0];
+#pragma unroll
+            for (int r = 1; r < R; ++r) v = r == rm ? hl[r] : v;
+            res.score = __builtin_amdgcn_readlane(v, last / R);
+            res.end_text = (uint64_t)n;
+            res.end_pattern = (uint64_t)m;
+        }
+        if (lane == 0) a.out[pi] = res;
+    }
+    if (bad) __hip_atomic_store(&a.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+}  // namespace sa
