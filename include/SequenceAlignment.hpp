@@ -146,6 +146,13 @@ uint64_t scoreSequencesGPU(const Request *requests, uint64_t numRequests, int de
 uint64_t scoreSequencesGPUAffine(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
                                  int *scores);
 
+/// Extension: numRequests requests aligned on `device` under affine gap penalties
+/// (sa_align_pairs_affine: traced Gotoh fill and a traceback over the three states). Fills
+/// responses[i] as alignSequenceGPUBatch does; Request::gapPenalty is ignored. One scoring scheme for
+/// all requests, as above. Returns 0, or 1 with the message on stdout.
+uint64_t alignSequencesGPUAffine(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                 int gapOpen, int gapExtend);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

@@ -233,8 +233,8 @@ int sa_score_batch_affine(const sa_params *params, int32_t gap_open, int32_t gap
 int sa_scorer_create_affine(const sa_params *params, int32_t gap_open, int32_t gap_extend,
                             const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
 
-/* Linear gap penalty only: aligning the hits under affine gaps needs an affine traceback, which the
- * plans do not have (rank with sa_scorer_create_affine instead).
+/* Linear gap penalty (params->gap_penalty); sa_search_affine below is the same search under gap open /
+ * gap extend, scores and alignments alike.
  * Score `query` (the pattern) against num_texts texts and align the k best: ranked by score
  * descending, ties to the lower index; *num_hits = min(k, num_texts). scores (num_texts entries) may
  * be NULL. hit_index / hit_results: k entries. aligned_text / aligned_pattern: both NULL, or k host
@@ -245,6 +245,31 @@ int sa_search(const sa_params *params, const char *query, uint64_t query_len, co
               const uint64_t *text_lens, int64_t num_texts, int k, int device, sa_score_result *scores,
               int64_t *hit_index, sa_result *hit_results, char *const *aligned_text,
               char *const *aligned_pattern, int64_t *num_hits);
+
+/* ---- alignments under affine gap penalties ------------------------------------------------ */
+
+/* Align num_pairs host pairs on `device` under gap_open / gap_extend (recurrence of sa_score_batch_affine;
+ * tie rules and walk: DESIGN.md 3.5). results, aligned_text, aligned_pattern as sa_align_batch takes them
+ * (strings NULL/NULL: results only). With gap_open == gap_extend == g every output equals sa_align_pair's
+ * for gap_penalty g. Synchronous. The fill keeps four direction bits per cell of the pairs it has in
+ * flight: the pairs are processed in chunks whose directions fit 2 GiB (SA_TRACE_ARENA_BYTES), and a
+ * single pair above that is SA_ERR_UNSUPPORTED. */
+int sa_align_pairs_affine(const sa_params *params, int32_t gap_open, int32_t gap_extend,
+                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                          char *const *aligned_text, char *const *aligned_pattern);
+
+/* sa_search under gap_open / gap_extend: scores from the affine scorer, the k best aligned by the path
+ * above on the same device (texts and query uploaded once). Arguments and ranking as sa_search. */
+int sa_search_affine(const sa_params *params, int32_t gap_open, int32_t gap_extend, const char *query,
+                     uint64_t query_len, const char *const *texts, const uint64_t *text_lens, int64_t num_texts,
+                     int k, int device, sa_score_result *scores, int64_t *hit_index, sa_result *hit_results,
+                     char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits);
+
+/* For benches and tests only, not a stable part of the ABI (it may change or go without a new
+ * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine or sa_search_affine (k > 0): device
+ * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
+ * direction arena and the number of chunks. Each pointer may be NULL. */
+int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);
 
 /* ---- misc ------------------------------------------------------------------------------ */
 int sa_device_count(int *count);

@@ -97,6 +97,34 @@ bool sameScheme(const sa_params &a, const sa_params &b)
            a.alphabet == b.alphabet &&
            std::memcmp(a.score_matrix, b.score_matrix, sizeof(int) * a.alphabet_size * a.alphabet_size) == 0;
 }
+
+// Fresh Response buffers for a request of a batch call (the callee allocates, as alignSequenceGPU does)
+bool allocResponse(const SequenceAlignment::Request &rq, SequenceAlignment::Response &rs)
+{
+    const uint64_t cap = std::max<uint64_t>(1, std::max(2 * rq.textNumBytes, rq.textNumBytes + rq.patternNumBytes));
+    delete[] rs.alignedTextBytes;
+    delete[] rs.alignedPatternBytes;
+    rs.alignedTextBytes = rs.alignedPatternBytes = nullptr;
+    try
+    {
+        rs.alignedTextBytes = new char[cap];
+        rs.alignedPatternBytes = new char[cap];
+    }
+    catch (const std::bad_alloc &)
+    {
+        std::cout << SequenceAlignment::MEM_ERROR;
+        return false;
+    }
+    return true;
+}
+
+void storeResult(const sa_result &res, SequenceAlignment::Response &rs)
+{
+    rs.score = res.score;
+    rs.numAlignmentBytes = res.num_alignment_bytes;
+    rs.startInAlignedText = res.start_text;
+    rs.startInAlignedPattern = res.start_pattern;
+}
 }  // namespace
 
 uint64_t SequenceAlignment::alignSequenceGPUBatch(const Request *requests, Response *responses, uint64_t numRequests,
@@ -125,20 +153,7 @@ uint64_t SequenceAlignment::alignSequenceGPUBatch(const Request *requests, Respo
             const Request &rq = requests[group[q]];
             Response &rs = responses[group[q]];
             pairs[q] = sa_host_pair{rq.textBytes, rq.textNumBytes, rq.patternBytes, rq.patternNumBytes};
-            const uint64_t cap = std::max<uint64_t>(1, std::max(2 * rq.textNumBytes, rq.textNumBytes + rq.patternNumBytes));
-            delete[] rs.alignedTextBytes;
-            delete[] rs.alignedPatternBytes;
-            rs.alignedTextBytes = rs.alignedPatternBytes = nullptr;
-            try
-            {
-                rs.alignedTextBytes = new char[cap];
-                rs.alignedPatternBytes = new char[cap];
-            }
-            catch (const std::bad_alloc &)
-            {
-                std::cout << SequenceAlignment::MEM_ERROR;
-                return 1;
-            }
+            if (!allocResponse(rq, rs)) return 1;
             at[q] = rs.alignedTextBytes;
             ap[q] = rs.alignedPatternBytes;
         }
@@ -151,11 +166,7 @@ uint64_t SequenceAlignment::alignSequenceGPUBatch(const Request *requests, Respo
         }
         for (size_t q = 0; q < group.size(); ++q)
         {
-            Response &rs = responses[group[q]];
-            rs.score = res[q].score;
-            rs.numAlignmentBytes = res[q].num_alignment_bytes;
-            rs.startInAlignedText = res[q].start_text;
-            rs.startInAlignedPattern = res[q].start_pattern;
+            storeResult(res[q], responses[group[q]]);
             done[group[q]] = true;
         }
     }
@@ -221,4 +232,42 @@ uint64_t SequenceAlignment::scoreSequencesGPUAffine(const Request *requests, uin
 {
     const int gap[2] = {gapOpen, gapExtend};
     return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUAffine");
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Response *responses, uint64_t numRequests,
+                                                    int device, int gapOpen, int gapExtend)
+{
+    if (numRequests == 0) return 0;
+    std::vector<sa_params> params(numRequests);
+    std::vector<sa_host_pair> pairs(numRequests);
+    std::vector<char *> at(numRequests), ap(numRequests);
+    for (uint64_t i = 0; i < numRequests; ++i)
+    {
+        if (!toParams(requests[i], &params[i]))
+        {
+            std::cout << "error: only --global and --local alignments are implemented\n";
+            return 1;
+        }
+        params[i].gap_penalty = 0;
+        if (!sameScheme(params[0], params[i]))
+        {
+            std::cout << "error: alignSequencesGPUAffine needs one scoring scheme for all requests\n";
+            return 1;
+        }
+        pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
+                                requests[i].patternNumBytes};
+        if (!allocResponse(requests[i], responses[i])) return 1;
+        at[i] = responses[i].alignedTextBytes;
+        ap[i] = responses[i].alignedPatternBytes;
+    }
+    std::vector<sa_result> res(numRequests);
+    const int rc = sa_align_pairs_affine(&params[0], gapOpen, gapExtend, pairs.data(), (int64_t)numRequests, device,
+                                         res.data(), at.data(), ap.data());
+    if (rc != SA_OK)
+    {
+        std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
+        return 1;
+    }
+    for (uint64_t i = 0; i < numRequests; ++i) storeResult(res[i], responses[i]);
+    return 0;
 }

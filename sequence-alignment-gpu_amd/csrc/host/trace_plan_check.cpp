@@ -1,0 +1,94 @@
+// bin/sa_trace_plan_check: the planner of the affine alignment path (sa_trace_plan.cpp) as a
+// stand-alone program. No GPU, no ROCm: it plans the pair shapes on its command line and prints the
+// plan as one JSON object (tests/test_trace_plan.py).
+//   sa_trace_plan_check --mode global|local|<int> --alphabet A --gap G --gap-extend E --cus N
+//                       [--budget BYTES] [--match M --mismatch X] NxM[xCOUNT] ...
+// --gap is the gap-open penalty. Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
+// NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
+// A planning error prints {"error": code, "message": text}.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sa_trace_plan.h"
+
+using namespace sa;
+
+int main(int argc, char **argv)
+{
+    sa_params P;
+    std::memset(&P, 0, sizeof(P));
+    P.alphabet_size = 4;
+    int cus = 256, match = 5, mismatch = -4, go = 11, ge = 2;
+    uint64_t budget = trace_arena_budget();
+    std::vector<sa_pair> pairs;
+    for (int i = 1; i < argc; ++i)
+    {
+        const std::string a = argv[i];
+        auto value = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
+        if (a == "--mode")
+        {
+            const std::string v = value();
+            P.mode = v == "global" ? SA_GLOBAL : v == "local" ? SA_LOCAL : std::atoi(v.c_str());
+        }
+        else if (a == "--alphabet") P.alphabet_size = std::atoi(value());
+        else if (a == "--gap") go = std::atoi(value());
+        else if (a == "--gap-extend") ge = std::atoi(value());
+        else if (a == "--cus") cus = std::atoi(value());
+        else if (a == "--budget") budget = std::strtoull(value(), nullptr, 10);
+        else if (a == "--match") match = std::atoi(value());
+        else if (a == "--mismatch") mismatch = std::atoi(value());
+        else
+        {
+            unsigned long long n = 0, m = 0, count = 1;
+            if (std::sscanf(a.c_str(), "%llux%llux%llu", &n, &m, &count) < 2)
+            {
+                std::fprintf(stderr, "sa_trace_plan_check: bad argument %s\n", a.c_str());
+                return 2;
+            }
+            for (unsigned long long k = 0; k < count; ++k)
+            {
+                sa_pair pr;
+                pr.text_offset = pairs.empty() ? 0 : pairs.back().text_offset + pairs.back().text_len;
+                pr.text_len = n;
+                pr.pattern_offset = pairs.empty() ? 0 : pairs.back().pattern_offset + pairs.back().pattern_len;
+                pr.pattern_len = m;
+                pairs.push_back(pr);
+            }
+        }
+    }
+    const int a = std::min(std::max(P.alphabet_size, 1), 64);
+    std::vector<int32_t> S((size_t)a * a, mismatch);
+    for (int c = 0; c < a; ++c) S[(size_t)c * a + c] = match;
+    P.score_matrix = S.data();
+
+    TracePlan pl;
+    std::string err;
+    const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err);
+    if (rc != SA_OK)
+    {
+        std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+        return 0;
+    }
+    std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"gap_extend\": %d, \"R\": %d, \"grid\": %d, \"num_pairs\": %lld, "
+                "\"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, "
+                "\"num_chunks\": %lld, \"chunk_begin\": [",
+                pl.score.mode, pl.score.A, pl.score.gap, pl.score.gap_extend, pl.score.R, pl.score.grid,
+                (long long)pl.score.num_pairs, (unsigned long long)pl.budget, (unsigned long long)pl.arena_bytes,
+                (unsigned long long)pl.total_dir_bytes, (unsigned long long)pl.string_bytes, (long long)pl.num_chunks());
+    for (size_t i = 0; i < pl.chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)pl.chunk_begin[i]);
+    // the lists of a large batch are long: the first 64 entries
+    std::printf("], \"order\": [");
+    for (size_t i = 0; i < pl.score.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.score.order[i]);
+    std::printf("], \"pairs\": [");
+    for (size_t i = 0; i < pairs.size() && i < 64; ++i)
+        std::printf("%s{\"strips\": %llu, \"steps\": %llu, \"dir_bytes\": %llu, \"dir_off\": %llu, \"slot_off\": %llu}", i ? ", " : "",
+                    (unsigned long long)(pl.dir_bytes[i] ? trace_strips(pairs[i].pattern_len) : 0),
+                    (unsigned long long)(pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
+                    (unsigned long long)pl.dir_bytes[i], (unsigned long long)pl.dir_off[i], (unsigned long long)pl.slot_off[i]);
+    std::printf("]}\n");
+    return 0;
+}

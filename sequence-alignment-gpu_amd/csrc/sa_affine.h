@@ -1,0 +1,18 @@
+// The affine alignment path inside the library (sa_affine_walk.hip): what sa_align_pairs_affine and
+// sa_search_affine (sa_score.hip) share. Host only.
+#pragma once
+#include <stdint.h>
+
+#include "sa_hip.h"
+
+namespace sa {
+
+// Aligns `np` pairs addressed in the device arenas d_text / d_pattern (alphabet indices) on `device`
+// under gap_open / gap_extend: the traced Gotoh fill and the walk, chunk by chunk of the work order
+// (sa_trace_plan.h), on the null stream; synchronous. results: np entries. aligned_text /
+// aligned_pattern: both null, or np host buffers of at least text_len + pattern_len bytes each.
+int align_affine_device(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
+                        int device, const void *d_text, const void *d_pattern, sa_result *results,
+                        char *const *aligned_text, char *const *aligned_pattern);
+
+}  // namespace sa

@@ -1,0 +1,410 @@
+// Alignments under affine gap penalties (sa_hip.h: sa_align_pairs_affine; sa_search_affine in
+// sa_score.hip): align_affine_kernel<LOCAL, SMALL>, the traced instance of the affine wave program
+// (sa_score_wave.h, TRACE: four direction bits per cell), walk_affine_kernel, the traceback over the
+// three Gotoh states, and the host side that runs both chunk by chunk of the work order. What is run
+// is decided in sa_trace_plan.cpp (host only, no HIP). DESIGN.md §3.5 has the nibble, the walk and
+// its tie rules.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sa_affine.h"
+#include "sa_hip.h"
+#include "sa_host.h"
+#include "sa_score_wave.h"
+#include "sa_trace_plan.h"
+
+namespace sa {
+
+struct AlignAffineArgs {
+    ScoreAffineArgs sa;
+    TraceArgs tr;
+};
+
+template <bool LOCAL, bool SMALL>
+__global__ __launch_bounds__(64) void align_affine_kernel(AlignAffineArgs a)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, kTraceRows, LOCAL, SMALL, true>(a.sa.s, a.sa.gap_extend, tab, a.tr);
+}
+
+struct WalkArgs {
+    const int8_t *text, *pattern;
+    const ScorePair *pairs;
+    const int32_t *order;             // the chunk's part of the work order: workgroup w walks pair order[w]
+    const sa_score_result *scores;    // the fill's score and end cell of every pair
+    const uint32_t *dirs;             // the chunk's direction arena
+    const uint64_t *dir_off;          // per pair, in words
+    const uint64_t *slot_off;         // per pair: its text_len + pattern_len bytes in each string arena
+    char *out_text, *out_pattern;     // both null: results only, no letters are loaded or written
+    const char *alphabet;             // A letters and the gap letter
+    sa_result *results;
+    int32_t A, local;
+};
+
+// One wave per pair; the walk of DESIGN.md §3.5: oracle_align's loop (oracle/sa_oracle.c) with a
+// state in {H, E, F}. The position, the state and the counters are wave-uniform. The direction word
+// of cell (i, j) lies at step j - 1 + lane of lane ((i - 1) % 512) / 8 of strip (i - 1) / 512, and a
+// move stays in that lane column or goes to the lane before it, to the same or an earlier step. So
+// the wave fetches 64 consecutive steps of the current lane column in one load (lane k: step t - k)
+// and reads them with v_readlane until the path leaves the column or the window: about
+// m / 8 + (m + n) / 64 dependent loads per alignment. The letters are not loaded on the path either:
+// lane (len % 64) notes the cell and the direction of each emission, and every 64 emissions the wave
+// loads the letters and writes 64 bytes per side, backwards from the end of the pair's slot.
+// The loop makes at most n + m moves whatever the direction words hold; a walk that has not ended by
+// then reports SA_ERR_HIP.
+__global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
+{
+    const int lane = threadIdx.x;
+    const int pi = uniform(a.order[blockIdx.x]);
+    const ScorePair pd = a.pairs[pi];
+    const int n = uniform((int)pd.n), m = uniform((int)pd.m);
+    const sa_score_result sr = a.scores[pi];
+    const int8_t *const text = a.text + pd.text_off;
+    const int8_t *const pattern = a.pattern + pd.pattern_off;
+    const uint64_t slot = uniform64(a.slot_off[pi]);
+    char *const ot_end = a.out_text + slot + (uint64_t)n + (uint64_t)m;  // one past the slot's last byte
+    char *const op_end = a.out_pattern + slot + (uint64_t)n + (uint64_t)m;
+    const uint32_t *const dirs = a.dirs + uniform64(a.dir_off[pi]);
+    const uint32_t strip_words = (uint32_t)((n + 126) / 64) * (64u * 64u);
+    const bool local = a.local != 0;
+    const int A = a.A;
+
+    int i = local ? min(uniform((int)sr.end_pattern), m) : m;
+    int j = local ? min(uniform((int)sr.end_text), n) : n;
+    int ti = j - 1, pj = i - 1;  // the reference's text and pattern indices
+    int state = kDirDiag;        // H; kDirLeft: inside a run of E, kDirTop: of F
+    int len = 0;
+    bool ended = false;
+    int cur = -1, t0 = 0;        // the window: lane column (i - 1) / 8 and its newest step
+    uint32_t win = 0;
+    int ri = 0, rj = 0, rd = 0;  // lane len % 64: the cell and the direction of emission len
+
+    // emissions base .. base + count - 1, one per lane, to bytes end - 1 - (base + lane)
+    const bool strings = a.out_text != nullptr;
+    auto flush = [&](int base, int count) {
+        if (strings && lane < count)
+        {
+            const bool tt = rd == kDirDiag || rd == kDirLeft, tp = rd == kDirDiag || rd == kDirTop;
+            const int ct = tt ? min(max((int)text[rj - 1], 0), A - 1) : A;
+            const int cp = tp ? min(max((int)pattern[ri - 1], 0), A - 1) : A;
+            ot_end[-1 - (int64_t)(base + lane)] = a.alphabet[ct];
+            op_end[-1 - (int64_t)(base + lane)] = a.alphabet[cp];
+        }
+    };
+
+    const int max_moves = n + m;
+    for (int it = 0;; ++it)
+    {
+        if (local ? (i == 0 || j == 0) : (i == 0 && j == 0))
+        {
+            ended = true;
+            break;
+        }
+        if (it >= max_moves) break;
+        int d, next = kDirDiag;
+        if (j == 0) d = kDirTop;        // global: column 0 forces TOP,
+        else if (i == 0) d = kDirLeft;  // row 0 forces LEFT, whatever the state
+        else
+        {
+            const int col = (i - 1) >> 3, l = col & 63;
+            const int t = j - 1 + l;
+            if (col != cur || t0 - t >= 64)
+            {
+                const int step = t - lane;
+                win = step >= 0 ? dirs[(uint64_t)(col >> 6) * strip_words + ((uint32_t)step * 64u + (uint32_t)l)] : 0u;
+                cur = col;
+                t0 = t;
+            }
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)win, t0 - t);
+            const int nib = (int)(word >> (4 * ((i - 1) & 7))) & 15;
+            d = state == kDirDiag ? (nib & 3) : state;
+            if (d == kDirStop)  // only a local H cell holds it
+            {
+                ended = local;
+                break;
+            }
+            if (d == kDirLeft) next = nib & kDirEExt ? kDirLeft : kDirDiag;
+            if (d == kDirTop) next = nib & kDirFExt ? kDirTop : kDirDiag;
+        }
+        if (lane == (len & 63))
+        {
+            ri = i;
+            rj = j;
+            rd = d;
+        }
+        ++len;
+        const int tt = d == kDirDiag || d == kDirLeft, tp = d == kDirDiag || d == kDirTop;
+        j -= tt;
+        i -= tp;
+        state = next;
+        if ((len & 63) == 0) flush(len - 64, 64);
+        if (local && (i == 0 || j == 0))  // the reference leaves before the decrement
+        {
+            ended = true;
+            break;
+        }
+        ti = ti - tt > 0 ? ti - tt : 0;
+        pj = pj - tp > 0 ? pj - tp : 0;
+    }
+    flush(len & ~63, len & 63);
+    if (lane == 0)
+    {
+        sa_result r;
+        r.score = sr.score;
+        r.status = ended ? SA_OK : SA_ERR_HIP;
+        r.num_alignment_bytes = (uint64_t)len;
+        r.start_text = (uint64_t)(int64_t)ti;
+        r.start_pattern = (uint64_t)(int64_t)pj;
+        a.results[pi] = r;
+    }
+}
+
+}  // namespace sa
+
+// ==================================================================================================
+// host side
+// ==================================================================================================
+using namespace sa;
+
+namespace {
+
+struct AffineStats {
+    double fill_ms = 0, walk_ms = 0;
+    uint64_t arena_bytes = 0;
+    int32_t chunks = 0;
+};
+thread_local AffineStats g_stats;
+
+// every device buffer and event of one call, released on every return path
+struct Workspace {
+    std::vector<void *> bufs;
+    std::vector<hipEvent_t> events;
+    ~Workspace()
+    {
+        for (void *b : bufs) (void)hipFree(b);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    }
+    template <typename T>
+    int alloc(T **p, size_t bytes)
+    {
+        if (int rc = dmalloc(p, bytes)) return rc;
+        bufs.push_back(*p);
+        return SA_OK;
+    }
+};
+
+void launch_align(const AlignAffineArgs &a, bool local, bool small, int grid, hipStream_t st)
+{
+    if (local)
+    {
+        if (small) hipLaunchKernelGGL((align_affine_kernel<true, true>), dim3(grid), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((align_affine_kernel<true, false>), dim3(grid), dim3(64), 0, st, a);
+    }
+    else
+    {
+        if (small) hipLaunchKernelGGL((align_affine_kernel<false, true>), dim3(grid), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((align_affine_kernel<false, false>), dim3(grid), dim3(64), 0, st, a);
+    }
+}
+
+}  // namespace
+
+int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa_pair *pairs, int64_t np, int device,
+                            const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
+                            char *const *aligned_pattern)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
+        return fail(SA_ERR_INVALID, "affine aligner: null argument");
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    TracePlan pl;
+    std::string err;
+    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err))
+        return fail(rc, err);
+    if (!P->alphabet) return fail(SA_ERR_INVALID, "affine aligner: params->alphabet is null");
+    g_stats = AffineStats();
+    g_stats.arena_bytes = pl.arena_bytes;
+    g_stats.chunks = (int32_t)pl.num_chunks();
+    if (np == 0) return SA_OK;
+    if ((!d_text || !d_pattern) && pl.score.input_bytes) return fail(SA_ERR_INVALID, "affine aligner: null arena");
+    const int A = pl.score.A;
+
+    std::vector<ScorePair> hpairs((size_t)np);
+    std::vector<uint64_t> dir_words((size_t)np);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        hpairs[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
+        dir_words[p] = pl.dir_off[p] / 4;
+    }
+    Workspace ws;
+    ScorePair *d_pairs;
+    int32_t *d_order, *d_table, *d_rows;
+    sa_score_result *d_scores;
+    uint32_t *d_ctrl, *d_dirs;
+    uint64_t *d_dir_off, *d_slot_off;
+    char *d_ot = nullptr, *d_op = nullptr, *d_alpha;
+    sa_result *d_results;
+    int rc;
+    if ((rc = ws.alloc(&d_pairs, (size_t)np * sizeof(ScorePair))) || (rc = ws.alloc(&d_order, (size_t)np * 4)) ||
+        (rc = ws.alloc(&d_table, 32 * 32 * 4)) || (rc = ws.alloc(&d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) ||
+        (rc = ws.alloc(&d_scores, (size_t)np * sizeof(sa_score_result))) || (rc = ws.alloc(&d_ctrl, 256)) ||
+        (rc = ws.alloc(&d_dirs, pl.arena_bytes)) || (rc = ws.alloc(&d_dir_off, (size_t)np * 8)) ||
+        (rc = ws.alloc(&d_slot_off, (size_t)np * 8)) || (rc = ws.alloc(&d_alpha, 64)) ||
+        (rc = ws.alloc(&d_results, (size_t)np * sizeof(sa_result))))
+        return rc;
+    const bool strings = aligned_text != nullptr;
+    if (strings && ((rc = ws.alloc(&d_ot, pl.string_bytes)) || (rc = ws.alloc(&d_op, pl.string_bytes)))) return rc;
+    HIP_TRY(hipMemcpy(d_pairs, hpairs.data(), (size_t)np * sizeof(ScorePair), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_order, pl.score.order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dir_off, dir_words.data(), (size_t)np * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_slot_off, pl.slot_off.data(), (size_t)np * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_alpha, P->alphabet, (size_t)A + 1, hipMemcpyHostToDevice));
+
+    hipStream_t st = nullptr;
+    const int64_t nchunks = pl.num_chunks();
+    ws.events.reserve((size_t)nchunks * 3);
+    for (int64_t e = 0; e < nchunks * 3; ++e)
+    {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        ws.events.push_back(ev);
+    }
+    HIP_TRY(hipMemsetAsync(d_ctrl, 0, 256, st));
+    AlignAffineArgs fa;
+    ScoreArgs &s = fa.sa.s;
+    s.text = (const int8_t *)d_text;
+    s.pattern = (const int8_t *)d_pattern;
+    s.pairs = d_pairs;
+    s.table = d_table;
+    s.rows = d_rows;
+    s.out = d_scores;
+    s.ctrl = d_ctrl;
+    s.A = A;
+    s.gap = go;
+    s.key_rowbits = pl.score.key_rowbits;
+    s.row_stride = pl.score.row_stride;
+    fa.sa.gap_extend = ge;
+    fa.tr.dirs = d_dirs;
+    fa.tr.dir_off = d_dir_off;
+    WalkArgs wa;
+    wa.text = s.text;
+    wa.pattern = s.pattern;
+    wa.pairs = d_pairs;
+    wa.scores = d_scores;
+    wa.dirs = d_dirs;
+    wa.dir_off = d_dir_off;
+    wa.slot_off = d_slot_off;
+    wa.out_text = d_ot;
+    wa.out_pattern = d_op;
+    wa.alphabet = d_alpha;
+    wa.results = d_results;
+    wa.A = A;
+    wa.local = pl.score.mode == SA_LOCAL;
+    uint32_t ctrl[2] = {0, 0};
+    // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
+    // copies into `results` and `ctrl` pending when this function returns
+    auto enqueue = [&]() -> int {
+        for (int64_t c = 0; c < nchunks; ++c)
+        {
+            // one traced fill and one walk per chunk; the next chunk's fill reuses the arena after the walk
+            const int64_t begin = pl.chunk_begin[c], count = pl.chunk_begin[c + 1] - begin;
+            if (c) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 4, st));  // the work counter; the bad-input flag stays
+            s.order = d_order + begin;
+            s.np = (int32_t)count;
+            wa.order = s.order;
+            HIP_TRY(hipEventRecord(ws.events[3 * c], st));
+            launch_align(fa, wa.local != 0, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
+            hipLaunchKernelGGL(walk_affine_kernel, dim3((unsigned)count), dim3(64), 0, st, wa);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ws.events[3 * c + 2], st));
+        }
+        HIP_TRY(hipMemcpyAsync(ctrl, d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(results, d_results, (size_t)np * sizeof(sa_result), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SA_OK;
+    };
+    if ((rc = enqueue()))
+    {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    for (int64_t c = 0; c < nchunks; ++c)
+    {
+        float f = 0, w = 0;
+        HIP_TRY(hipEventElapsedTime(&f, ws.events[3 * c], ws.events[3 * c + 1]));
+        HIP_TRY(hipEventElapsedTime(&w, ws.events[3 * c + 1], ws.events[3 * c + 2]));
+        g_stats.fill_ms += f;
+        g_stats.walk_ms += w;
+    }
+    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+    for (int64_t p = 0; p < np; ++p)
+        if (results[p].status != SA_OK)
+            return fail(SA_ERR_HIP, "affine walk of pair " + std::to_string(p) + " did not end within text_len + pattern_len moves");
+    if (strings && pl.string_bytes)
+    {
+        std::vector<char> ht(pl.string_bytes), hp(pl.string_bytes);
+        HIP_TRY(hipMemcpy(ht.data(), d_ot, pl.string_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hp.data(), d_op, pl.string_bytes, hipMemcpyDeviceToHost));
+        for (int64_t p = 0; p < np; ++p)
+        {
+            // written backwards from the end of the slot: the forward string is the slot's tail
+            const uint64_t cap = pairs[p].text_len + pairs[p].pattern_len;
+            const uint64_t L = std::min<uint64_t>(results[p].num_alignment_bytes, cap);
+            if (!L) continue;
+            std::memcpy(aligned_text[p], ht.data() + pl.slot_off[p] + cap - L, L);
+            std::memcpy(aligned_pattern[p], hp.data() + pl.slot_off[p] + cap - L, L);
+        }
+    }
+    return SA_OK;
+}
+
+extern "C" {
+
+int sa_align_pairs_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_host_pair *pairs, int64_t np,
+                          int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
+        return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
+    std::vector<sa_pair> dp((size_t)np);
+    uint64_t tb = 0, pb = 0;
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
+            return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null sequence");
+        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
+        tb += pairs[p].text_len;
+        pb += pairs[p].pattern_len;
+    }
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    std::vector<char> ht(tb), hp(pb);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
+        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
+    }
+    DevBuf<char> dt, dpat;
+    int rc;
+    if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
+    if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
+    if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
+    return align_affine_device(P, gap_open, gap_extend, dp.data(), np, device, dt.p, dpat.p, results, aligned_text, aligned_pattern);
+}
+
+int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks)
+{
+    if (fill_ms) *fill_ms = g_stats.fill_ms;
+    if (walk_ms) *walk_ms = g_stats.walk_ms;
+    if (arena_bytes) *arena_bytes = g_stats.arena_bytes;
+    if (num_chunks) *num_chunks = g_stats.chunks;
+    return SA_OK;
+}
+
+}  // extern "C"

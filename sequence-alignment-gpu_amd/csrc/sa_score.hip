@@ -1,4 +1,4 @@
-// Score-only path (sa_hip.h: sa_score_batch*, sa_scorer_*, sa_search): the score of every pair and
+// Score-only path (sa_hip.h: sa_score_batch*, sa_scorer_*, sa_search*): the score of every pair and
 // the cell it is read from, without direction planes, strip descriptors, records or a traceback.
 // Here are the two kernels, score_kernel<R, LOCAL, SMALL> (linear gap) and
 // score_affine_kernel<R, LOCAL, SMALL> (gap open / gap extend), both the one wave program of
@@ -14,6 +14,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "sa_affine.h"
 #include "sa_hip.h"
 #include "sa_host.h"
 #include "sa_score_plan.h"
@@ -251,9 +252,44 @@ int sa_score_batch_affine(const sa_params *P, int32_t gap_open, int32_t gap_exte
     return score_batch(P, &gapm, pairs, np, device, out);
 }
 
-int sa_search(const sa_params *P, const char *query, uint64_t m, const char *const *texts, const uint64_t *text_lens,
-              int64_t nt, int k, int device, sa_score_result *scores, int64_t *hit_index, sa_result *hit_results,
-              char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits)
+}  // extern "C"
+
+// The hits of a linear search through a plan: the texts and the query are already on the device.
+static int align_hits_linear(const sa_params *P, const std::vector<sa_pair> &hp, int device, const void *d_text,
+                             const void *d_query, sa_result *hit_results, char *const *aligned_text,
+                             char *const *aligned_pattern)
+{
+    const int64_t nh = (int64_t)hp.size();
+    int rc;
+    sa_plan *plan = nullptr;
+    if ((rc = sa_plan_create(P, hp.data(), nh, device, &plan))) return rc;
+    std::unique_ptr<sa_plan, int (*)(sa_plan *)> hold(plan, sa_plan_destroy);
+    if ((rc = sa_plan_fill(plan, d_text, d_query, nullptr))) return rc;
+    if ((rc = sa_plan_traceback(plan, nullptr))) return rc;
+    const uint64_t ob = sa_plan_output_bytes(plan);
+    std::vector<char> tbuf(std::max<uint64_t>(ob, 1)), pbuf(std::max<uint64_t>(ob, 1));
+    std::vector<uint64_t> offs((size_t)nh);
+    const bool strings = aligned_text != nullptr;
+    if ((rc = sa_plan_fetch_all(plan, hit_results, strings ? tbuf.data() : nullptr, strings ? pbuf.data() : nullptr,
+                                tbuf.size(), offs.data(), nullptr)))
+        return rc;
+    for (int64_t h = 0; h < nh; ++h)
+    {
+        const uint64_t L = std::min<uint64_t>(hit_results[h].num_alignment_bytes, hp[h].text_len + hp[h].pattern_len);
+        if (strings && L)
+        {
+            std::memcpy(aligned_text[h], tbuf.data() + offs[h], L);
+            std::memcpy(aligned_pattern[h], pbuf.data() + offs[h], L);
+        }
+    }
+    return SA_OK;
+}
+
+// sa_search and sa_search_affine: `gapm` null is the linear search. They differ in the scorer they
+// create and in the aligner of the hits.
+static int search(const sa_params *P, const ScoreGap *gapm, const char *query, uint64_t m, const char *const *texts,
+                  const uint64_t *text_lens, int64_t nt, int k, int device, sa_score_result *scores, int64_t *hit_index,
+                  sa_result *hit_results, char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits)
 {
     if (!P || nt < 0 || k < 0 || (m && !query) || (nt > 0 && (!texts || !text_lens)) || !num_hits ||
         (k > 0 && (!hit_index || !hit_results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
@@ -275,7 +311,7 @@ int sa_search(const sa_params *P, const char *query, uint64_t m, const char *con
     int rc;
     {
         sa_scorer *raw = nullptr;
-        if ((rc = sa_scorer_create(P, dp.data(), nt, device, &raw))) return rc;
+        if ((rc = create_scorer(P, gapm, dp.data(), nt, device, &raw))) return rc;
         std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
         std::vector<char> ht(tb);
         for (int64_t i = 0; i < nt; ++i)
@@ -295,33 +331,36 @@ int sa_search(const sa_params *P, const char *query, uint64_t m, const char *con
     std::partial_sort(rank.begin(), rank.begin() + nh, rank.end(), [&](int64_t x, int64_t y) {
         return sc[x].score != sc[y].score ? sc[x].score > sc[y].score : x < y;
     });
-    // the hits through a plan: the texts are already on the device
+    // the hits: the texts and the query are already on the device
     std::vector<sa_pair> hp((size_t)nh);
     for (int64_t h = 0; h < nh; ++h) hp[h] = dp[rank[h]];
-    sa_plan *plan = nullptr;
-    if ((rc = sa_plan_create(P, hp.data(), nh, device, &plan))) return rc;
-    std::unique_ptr<sa_plan, int (*)(sa_plan *)> hold(plan, sa_plan_destroy);
-    if ((rc = sa_plan_fill(plan, dt.p, dq.p, nullptr))) return rc;
-    if ((rc = sa_plan_traceback(plan, nullptr))) return rc;
-    const uint64_t ob = sa_plan_output_bytes(plan);
-    std::vector<char> tbuf(std::max<uint64_t>(ob, 1)), pbuf(std::max<uint64_t>(ob, 1));
-    std::vector<uint64_t> offs((size_t)nh);
-    const bool strings = aligned_text != nullptr;
-    if ((rc = sa_plan_fetch_all(plan, hit_results, strings ? tbuf.data() : nullptr, strings ? pbuf.data() : nullptr,
-                                tbuf.size(), offs.data(), nullptr)))
-        return rc;
-    for (int64_t h = 0; h < nh; ++h)
-    {
-        hit_index[h] = rank[h];
-        const uint64_t L = std::min<uint64_t>(hit_results[h].num_alignment_bytes, hp[h].text_len + m);
-        if (strings && L)
-        {
-            std::memcpy(aligned_text[h], tbuf.data() + offs[h], L);
-            std::memcpy(aligned_pattern[h], pbuf.data() + offs[h], L);
-        }
-    }
+    rc = gapm ? align_affine_device(P, gapm->open, gapm->extend, hp.data(), nh, device, dt.p, dq.p, hit_results, aligned_text,
+                                    aligned_pattern)
+              : align_hits_linear(P, hp, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern);
+    if (rc) return rc;
+    for (int64_t h = 0; h < nh; ++h) hit_index[h] = rank[h];
     *num_hits = nh;
     return SA_OK;
+}
+
+extern "C" {
+
+int sa_search(const sa_params *P, const char *query, uint64_t m, const char *const *texts, const uint64_t *text_lens,
+              int64_t nt, int k, int device, sa_score_result *scores, int64_t *hit_index, sa_result *hit_results,
+              char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits)
+{
+    return search(P, nullptr, query, m, texts, text_lens, nt, k, device, scores, hit_index, hit_results, aligned_text,
+                  aligned_pattern, num_hits);
+}
+
+int sa_search_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const char *query, uint64_t m,
+                     const char *const *texts, const uint64_t *text_lens, int64_t nt, int k, int device,
+                     sa_score_result *scores, int64_t *hit_index, sa_result *hit_results, char *const *aligned_text,
+                     char *const *aligned_pattern, int64_t *num_hits)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return search(P, &gapm, query, m, texts, text_lens, nt, k, device, scores, hit_index, hit_results, aligned_text,
+                  aligned_pattern, num_hits);
 }
 
 }  // extern "C"

@@ -27,6 +27,12 @@
 // H - go from both branches.
 // DESIGN.md §3.4 has the resource usage of the instances, the rule for R and the step costs the
 // planner uses.
+//
+// TRACE (AFFINE, R = 8: align_affine_kernel, sa_affine_walk.hip) also records, per cell, where H came
+// from and whether E and F extend a run: a nibble per row, so a lane's eight rows are one dword per
+// step, stored at dirs[(strip * steps + t) * 64 + lane] of the pair's directions, steps = 64 nbodies.
+// Every step stores, the predicated ones too; the words of lanes outside columns 1..n and the nibbles
+// of rows past m are never read. DESIGN.md §3.5 has the nibble and the walk that reads it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,11 +68,22 @@ struct ScoreAffineArgs {
     int32_t gap_extend;
 };
 
+// TRACE: the direction arena of the launch and each pair's first word in it
+struct TraceArgs {
+    uint32_t *dirs = nullptr;
+    const uint64_t *dir_off = nullptr;  // per pair, in words
+};
+
+// direction nibble of a cell: bits 0-1 the source of H (the reference's codes), bit 2 E extends,
+// bit 3 F extends
+enum { kDirLeft = 0, kDirDiag = 1, kDirTop = 2, kDirStop = 3, kDirEExt = 4, kDirFExt = 8 };
+
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
-// registers); `gap_extend` is read only by AFFINE.
-template <bool AFFINE, int R, bool LOCAL, bool SMALL>
-__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab)
+// registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
+template <bool AFFINE, int R, bool LOCAL, bool SMALL, bool TRACE = false>
+__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs())
 {
+    static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
     const int lane = threadIdx.x;
     const int A = a.A, g = a.gap, ge = gap_extend;
@@ -110,6 +127,8 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         const int nbodies = (n + 63 + 63) / 64;  // steps 0 .. n + 62
         int hl[R];  // H[row][column - 1] of the lane's rows; after a strip, H[row][n]
         uint64_t lanekey = 0;
+        uint32_t *dlane = nullptr;  // TRACE: the lane's word of step 0 of the pair's first strip
+        if constexpr (TRACE) dlane = tr.dirs + uniform64(tr.dir_off[pi]) + lane;
         for (int s = 0; s < nstrips; ++s)
         {
             const int row1 = s * 64 * R + R * lane;  // rows row1 + 1 .. row1 + R
@@ -151,6 +170,8 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             int tl = 0, tfeed = 0, feed = 0, ofeed = 0;
             int fb = 0;                  // AFFINE: F[row1 + R][column] of the lane's last step,
             int feedf = 0, ofeedf = 0;   // and the F halves of the top-row feed and the bottom-row collection
+            uint32_t *dstrip = nullptr;  // TRACE: the lane's word of step 0 of this strip
+            if constexpr (TRACE) dstrip = dlane + (uint64_t)s * (uint64_t)nbodies * (64 * 64);
             auto step = [&](auto predc, const int t) {
                 constexpr bool PRED = decltype(predc)::value;
                 const int up = dpp_shr1(feed, hl[R - 1]);  // lane 0: the top row's next column
@@ -164,6 +185,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 const bool valid = !PRED || (unsigned)(t - lane) < (unsigned)n;
                 const bool b0 = (tl & 1) != 0, b1 = (tl & 2) != 0;
                 int d = upprev, u = up, uf = upf;
+                uint32_t word = 0;  // TRACE: the direction nibbles of the lane's rows
 #pragma unroll
                 for (int r = 0; r < R; ++r)
                 {
@@ -180,6 +202,16 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                         e = max(el[r] - ge, hl[r] - g);
                         f = max(uf - ge, u - g);
                         h = max(d + sv, max(e, f));
+                        if constexpr (TRACE)
+                        {
+                            // the reference's tie rule with left := E, up := F; a run extends only when
+                            // extending is strictly better than opening
+                            uint32_t nib = d + sv > max(e, f) ? kDirDiag : e >= f ? kDirLeft : kDirTop;
+                            if (LOCAL) nib = h <= 0 ? kDirStop : nib;
+                            nib |= el[r] - ge > hl[r] - g ? kDirEExt : 0;
+                            nib |= uf - ge > u - g ? kDirFExt : 0;
+                            word |= nib << (4 * r);
+                        }
                     }
                     else h = max(d + sv, max(hl[r] - g, u - g));
                     if (LOCAL) h = max(h, 0);
@@ -212,6 +244,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     fb = valid ? uf : fb;
                     ofeedf = dpp_shl1(fb, ofeedf);
                 }
+                if constexpr (TRACE) dstrip[(uint32_t)t * 64u] = word;
             };
             for (int b = 0; b < nbodies; ++b)
             {

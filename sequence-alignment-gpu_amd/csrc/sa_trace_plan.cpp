@@ -1,0 +1,75 @@
+// The planner of the affine alignment path (sa_trace_plan.h): validation through the score planner,
+// direction bytes and string slots per pair, and the chunks of the work order. Host only, no HIP.
+#include "sa_trace_plan.h"
+
+#include <algorithm>
+#include <cstdlib>
+
+namespace sa {
+
+uint64_t trace_arena_budget()
+{
+    static const uint64_t b = [] {
+        const char *e = std::getenv("SA_TRACE_ARENA_BYTES");
+        const unsigned long long v = e ? std::strtoull(e, nullptr, 10) : 0;
+        return v ? (uint64_t)v : kTraceArenaDefault;
+    }();
+    return b;
+}
+
+int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
+                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err)
+{
+    if (!out)
+    {
+        *err = "aligner: null argument";
+        return SA_ERR_INVALID;
+    }
+    TracePlan &pl = *out;
+    pl = TracePlan();
+    // the limits and the work order are the affine scorer's; the traced instances exist at R = 8 only
+    const ScoreGap gapm = {gap_open, gap_extend};
+    ScoreKnobs k8 = kn;
+    k8.rows_per_lane = kTraceRows;
+    // SA_SCORE_WAVES is tuned for the untraced kernels: here it may lower the grid, not raise it past
+    // what the traced instances' registers admit
+    k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
+    if (int rc = make_score_plan(P, pairs, np, num_cu, k8, &pl.score, err, &gapm)) return rc;
+    pl.budget = budget;
+    pl.dir_bytes.resize((size_t)np);
+    pl.dir_off.resize((size_t)np);
+    pl.slot_off.resize((size_t)np);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
+        pl.dir_bytes[p] = trace_dir_bytes(n, m);
+        pl.total_dir_bytes += pl.dir_bytes[p];
+        pl.slot_off[p] = pl.string_bytes;
+        pl.string_bytes += n + m;
+        if (pl.dir_bytes[p] > budget)
+        {
+            *err = "pair " + std::to_string(p) + " needs " + std::to_string(pl.dir_bytes[p]) +
+                   " direction bytes, the arena budget is " + std::to_string(budget) + " (SA_TRACE_ARENA_BYTES)";
+            return SA_ERR_UNSUPPORTED;
+        }
+    }
+    // consecutive chunks of the work order, each as long as its directions fit the budget
+    pl.chunk_begin.push_back(0);
+    uint64_t used = 0;
+    for (int64_t w = 0; w < np; ++w)
+    {
+        const int32_t p = pl.score.order[w];
+        if (used + pl.dir_bytes[p] > budget)
+        {
+            pl.chunk_begin.push_back(w);
+            used = 0;
+        }
+        pl.dir_off[p] = used;
+        used += pl.dir_bytes[p];
+        pl.arena_bytes = std::max(pl.arena_bytes, used);
+    }
+    if (np > 0) pl.chunk_begin.push_back(np);
+    return SA_OK;
+}
+
+}  // namespace sa

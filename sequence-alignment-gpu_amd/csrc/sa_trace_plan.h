@@ -1,0 +1,59 @@
+// The planner of the affine alignment path (sa_align_pairs_affine, sa_search_affine): what the traced
+// Gotoh fill and its traceback need before the first HIP call, as one pure function of (params, gap
+// open, gap extend, pair shapes, CU count, knobs, arena budget). No HIP here: sa_trace_plan.cpp builds
+// into libsa_hip.so and, with the plain host compiler, into bin/sa_trace_plan_check
+// (csrc/host/trace_plan_check.cpp), which tests/test_trace_plan.py runs without a GPU. DESIGN.md §3.5
+// has the direction words, the walk and the chunking.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "sa_hip.h"
+#include "sa_score_plan.h"
+
+namespace sa {
+
+// The traced fill runs strips of 64 lanes x 8 rows and writes one dword (eight direction nibbles) per
+// lane and step: a strip is 512 rows, a step of a strip 256 bytes.
+constexpr int kTraceRows = 8;
+constexpr uint64_t kTraceStripRows = 64 * kTraceRows;
+constexpr uint64_t kTraceStepBytes = 64 * 4;
+constexpr uint64_t kTraceArenaDefault = 2ull << 30;
+// Resident waves per SIMD the grid is sized for: the traced instances take 154 to 226 VGPRs
+// (DESIGN.md §3.5), two waves of the SIMD's 512 in three of the four.
+constexpr int kTraceWavesPerSimd = 2;
+
+// SA_TRACE_ARENA_BYTES: the budget of the direction arena, read once per process.
+uint64_t trace_arena_budget();
+
+// Strips, steps and direction bytes of an m-row, n-column pair: ceil(m / 512) strips of
+// 64 nbodies steps, nbodies = (n + 126) / 64 rounded down as in score_wave (steps 0 .. n + 62 in whole
+// 64-step bodies). A pair with an empty side has no cells and no directions.
+inline uint64_t trace_strips(uint64_t m) { return (m + kTraceStripRows - 1) / kTraceStripRows; }
+inline uint64_t trace_steps(uint64_t n) { return 64 * ((n + 126) / 64); }
+inline uint64_t trace_dir_bytes(uint64_t n, uint64_t m)
+{
+    return n == 0 || m == 0 ? 0 : trace_strips(m) * trace_steps(n) * kTraceStepBytes;
+}
+
+struct TracePlan {
+    ScorePlan score;                  // validation, work order, key bits, grid and boundary rows (R = 8, affine)
+    uint64_t budget = 0;              // direction bytes one chunk may hold
+    std::vector<uint64_t> dir_bytes;  // per pair
+    std::vector<uint64_t> dir_off;    // per pair: byte offset of its directions in its chunk's arena
+    std::vector<uint64_t> slot_off;   // per pair: byte offset of its text_len + pattern_len string slot
+    std::vector<int64_t> chunk_begin; // chunk c is positions chunk_begin[c] .. chunk_begin[c + 1] - 1 of score.order
+    uint64_t arena_bytes = 0;         // direction bytes of the largest chunk: the arena's size
+    uint64_t total_dir_bytes = 0;     // of all pairs
+    uint64_t string_bytes = 0;        // of each of the two string arenas
+    int64_t num_chunks() const { return (int64_t)chunk_begin.size() - 1; }
+};
+
+// Plans `np` pairs. Returns SA_OK, or the SA_ERR_* code with its message in *err: make_score_plan's
+// for the affine gap model, or SA_ERR_UNSUPPORTED for a pair whose directions exceed `budget`.
+int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
+                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err);
+
+}  // namespace sa

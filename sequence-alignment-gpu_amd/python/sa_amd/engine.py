@@ -27,7 +27,7 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_plan_output_bytes", "sa_plan_fetch_all", "sa_align_batch", "sa_batch_deal", "sa_build_id",
            "sa_batch_last_stats", "sa_plan_fill_kind", "sa_score_batch", "sa_scorer_create", "sa_scorer_run",
            "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search", "sa_score_batch_affine",
-           "sa_scorer_create_affine")
+           "sa_scorer_create_affine", "sa_align_pairs_affine", "sa_search_affine", "sa_affine_last_stats")
 
 
 class SaParams(ctypes.Structure):
@@ -110,6 +110,12 @@ def _load():
     L.sa_scorer_destroy.argtypes = [P]
     L.sa_search.argtypes = [ctypes.POINTER(SaParams), P, U64, P, P, ctypes.c_int64, I, I, P, P, P, P, P,
                             ctypes.POINTER(ctypes.c_int64)]
+    L.sa_align_pairs_affine.argtypes = [ctypes.POINTER(SaParams), ctypes.c_int32, ctypes.c_int32, P, ctypes.c_int64, I,
+                                        ctypes.POINTER(SaResult), P, P]
+    L.sa_search_affine.argtypes = [ctypes.POINTER(SaParams), ctypes.c_int32, ctypes.c_int32, P, U64, P, P, ctypes.c_int64,
+                                   I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int64)]
+    L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                       ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_int32)]
     for name in EXPORTS:
         getattr(L, name)
     check_build_id(L)
@@ -204,6 +210,27 @@ def batch_last_stats() -> dict:
 def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
                 num_gpus: int = 1, alphabet: bytes | None = None, strings: bool = True) -> list[dict]:
     """sa_align_batch: independent pairs from host memory over devices 0..num_gpus-1 (synchronous)."""
+    return _align_host_pairs(mode, texts, patterns, S, gap, None, num_gpus, 0, alphabet, strings)
+
+
+def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
+                       gap_extend: int, device: int = 0, strings: bool = True) -> list[dict]:
+    """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
+    gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
+    ones. With gap_open == gap_extend == g every value is align_pair's for gap g."""
+    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings)
+
+
+def affine_last_stats() -> dict:
+    """sa_affine_last_stats: the calling thread's last affine alignment call (device ms of the traced
+    fills and of the walks, direction-arena bytes, chunks)."""
+    f, w, b, c = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0), ctypes.c_int32(0)
+    _check(lib.sa_affine_last_stats(ctypes.byref(f), ctypes.byref(w), ctypes.byref(b), ctypes.byref(c)))
+    return {"fill_ms": f.value, "walk_ms": w.value, "arena_bytes": b.value, "num_chunks": c.value}
+
+
+def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings) -> list[dict]:
+    """align_batch (gap_extend None) and align_pairs_affine: one packing of the host pairs and buffers."""
     p, S_keep, alpha_keep = _params(mode, S, gap, alphabet, 0)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
@@ -214,7 +241,10 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     at = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_t]) if strings else None
     ap = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_p]) if strings else None
     res = (SaResult * max(1, n))()
-    _check(lib.sa_align_batch(ctypes.byref(p), hp, n, num_gpus, res, at, ap))
+    if gap_extend is None:
+        _check(lib.sa_align_batch(ctypes.byref(p), hp, n, num_gpus, res, at, ap))
+    else:
+        _check(lib.sa_align_pairs_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, res, at, ap))
     out = []
     for i, r in enumerate(res[:n]):
         d = {"score": r.score, "num_bytes": r.num_alignment_bytes, "start_text": r.start_text,
@@ -374,11 +404,13 @@ class Scorer:
 
 
 def search(mode: int, query: np.ndarray, texts: list[np.ndarray], S: np.ndarray, gap: int, k: int,
-           device: int = 0, strings: bool = True) -> tuple[np.ndarray, list[dict]]:
+           device: int = 0, strings: bool = True, gap_extend: int | None = None) -> tuple[np.ndarray, list[dict]]:
     """sa_search: `query` (the pattern) against every text. Returns (scores, hits): scores is a
     SCORE_DTYPE array over the texts; hits holds the min(k, len(texts)) best (score descending, ties
     to the lower index), each {"index", "score", "num_bytes", "start_text", "start_pattern"} and, with
-    strings, "aligned_text" / "aligned_pattern", as align_pair gives them for that pair."""
+    strings, "aligned_text" / "aligned_pattern", as align_pair gives them for that pair. With
+    `gap_extend`, sa_search_affine: `gap` is the gap-open penalty, and the hits are aligned under the
+    gap model they were ranked by, as align_pairs_affine gives them."""
     p, S_keep, alpha_keep = _params(mode, S, gap, None, 0)
     q = np.ascontiguousarray(query, dtype=np.int8)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
@@ -395,8 +427,12 @@ def search(mode: int, query: np.ndarray, texts: list[np.ndarray], S: np.ndarray,
     at = (ctypes.c_void_p * kk)(*[ctypes.addressof(b) for b in bufs_t]) if strings else None
     ap = (ctypes.c_void_p * kk)(*[ctypes.addressof(b) for b in bufs_p]) if strings else None
     nh = ctypes.c_int64(0)
-    _check(lib.sa_search(ctypes.byref(p), q.ctypes.data, len(q), tp, tl.ctypes.data, n, k, device, scores.ctypes.data,
-                         idx.ctypes.data, res, at, ap, ctypes.byref(nh)))
+    if gap_extend is None:
+        _check(lib.sa_search(ctypes.byref(p), q.ctypes.data, len(q), tp, tl.ctypes.data, n, k, device, scores.ctypes.data,
+                             idx.ctypes.data, res, at, ap, ctypes.byref(nh)))
+    else:
+        _check(lib.sa_search_affine(ctypes.byref(p), gap, gap_extend, q.ctypes.data, len(q), tp, tl.ctypes.data, n, k,
+                                    device, scores.ctypes.data, idx.ctypes.data, res, at, ap, ctypes.byref(nh)))
     hits = []
     for h in range(nh.value):
         r = res[h]

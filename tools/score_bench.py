@@ -17,8 +17,16 @@ alternated round by round in the same process, then the forced rows-per-lane swe
 scorer. The report holds the measured affine / linear ratio of the medians next to the ratio of the
 planner's step-cost model. The plan path is not run.
 
+With --gap-extend E --hits K the search workload alone: the affine Scorer.run beside search(k=K,
+gap_extend=E) end to end, the device time of its traced fill and of its walk, and the
+linear search(k=K) of the same data. With --hits K alone, the linear search(k=K) alone; --tree DIR
+takes the package and library from another built checkout, which is how the parent commit's figure of
+DESIGN.md 3.5 was taken.
+
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
     python3 tools/score_bench.py --gap-extend 2 [--gap-open 11] --out profiles/r10/score_affine_bench.json
+    python3 tools/score_bench.py --gap-extend 2 --hits 100 --out profiles/r12/score_affine_hits.json
+    python3 tools/score_bench.py --hits 100 --tree ../parent --out profiles/r12/parent_linear_search.json
 """
 from __future__ import annotations
 
@@ -39,13 +47,14 @@ def blosum50():
         return np.array(json.load(f)["blosum50"], dtype=np.int32).reshape(23, 23)
 
 
-def workloads(small: bool):
+def workloads(small: bool, search_only: bool = False):
     from sa_amd import synthetic
-    npairs, side = (256, 2048) if small else (4096, 2048)
-    ta = synthetic.random_sequence(1, npairs * side, 4)
-    pa = synthetic.mutate(ta, 2, 4, npairs * side)
-    yield {"name": "batch", "mode": 0, "S": synthetic.blast_matrix(), "gap": 5, "text": ta, "pattern": pa,
-           "pairs": [(k * side, side, k * side, side) for k in range(npairs)]}
+    if not search_only:
+        npairs, side = (256, 2048) if small else (4096, 2048)
+        ta = synthetic.random_sequence(1, npairs * side, 4)
+        pa = synthetic.mutate(ta, 2, 4, npairs * side)
+        yield {"name": "batch", "mode": 0, "S": synthetic.blast_matrix(), "gap": 5, "text": ta, "pattern": pa,
+               "pairs": [(k * side, side, k * side, side) for k in range(npairs)]}
     ntexts = 2000 if small else 20000
     rng = np.random.default_rng(9)
     lens = rng.integers(64, 2049, ntexts)
@@ -114,6 +123,60 @@ def affine_rows(args, engine, w, dt, dp) -> dict:
     return row
 
 
+def hits_row(args, engine, w, dt, dp) -> dict:
+    """--hits K on the search workload: the affine Scorer.run alone (device events), and
+    search(k=K, gap_extend=) end to end (wall clock, from host arrays to host strings) with the device
+    time of its traced fill and of its walk (sa_affine_last_stats), beside the linear search(k=K) of the
+    same data; alternated round by round after a warm-up. Without --gap-extend the linear search alone
+    (with --tree: that of another checkout's library, e.g. the parent commit's)."""
+    import time
+    texts = [w["text"][o:o + n] for o, n, _, _ in w["pairs"]]
+    q = w["pattern"]
+    if args.gap_extend is None:
+        run = lambda: engine.search(w["mode"], q, texts, w["S"], w["gap"], args.hits)  # noqa: E731
+        _, hits = run()
+        ms = []
+        for _ in range(args.rounds):
+            t0 = time.perf_counter()
+            run()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return {"name": w["name"] + "_hits_linear", "pairs": len(w["pairs"]), "hits": len(hits), "linear_gap": w["gap"],
+                "hit_cells": sum(len(texts[h["index"]]) * len(q) for h in hits), "library_build_id": engine.lib.sa_build_id().decode(),
+                "search_linear_end_to_end": stats(ms)}
+    aff = engine.Scorer(w["mode"], w["S"], args.gap_open, w["pairs"], gap_extend=args.gap_extend)
+    run_a = lambda: aff.run(dt.data_ptr(), dp.data_ptr())  # noqa: E731
+
+    def wall(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    search_a = lambda: engine.search(w["mode"], q, texts, w["S"], args.gap_open, args.hits, gap_extend=args.gap_extend)  # noqa: E731
+    search_l = lambda: engine.search(w["mode"], q, texts, w["S"], w["gap"], args.hits)  # noqa: E731
+    run_a()
+    a_scores = aff.results()["score"].copy()
+    scores, hits = search_a()
+    assert (scores["score"] == a_scores).all(), "search and scorer scores differ"
+    assert all(h["score"] == int(a_scores[h["index"]]) for h in hits), "a hit's alignment score is not its rank score"
+    search_l()
+    t_run, t_sa, t_sl, t_fill, t_walk = [], [], [], [], []
+    st = {}
+    for _ in range(args.rounds):
+        t_run.append(timed(run_a, lambda: aff.results()))
+        t_sa.append(wall(search_a)[0])
+        st = engine.affine_last_stats()
+        t_fill.append(st["fill_ms"])
+        t_walk.append(st["walk_ms"])
+        t_sl.append(wall(search_l)[0])
+    aff.close()
+    hit_cells = sum(len(texts[h["index"]]) * len(q) for h in hits)
+    return {"name": w["name"] + "_hits", "pairs": len(w["pairs"]), "hits": len(hits), "gap_open": args.gap_open,
+            "gap_extend": args.gap_extend, "linear_gap": w["gap"], "hit_cells": hit_cells,
+            "direction_arena_bytes": st.get("arena_bytes"), "chunks": st.get("num_chunks"),
+            "affine_scorer_run": stats(t_run), "traced_fill_of_hits": stats(t_fill), "walk_of_hits": stats(t_walk),
+            "search_affine_end_to_end": stats(t_sa), "search_linear_end_to_end": stats(t_sl)}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "score_bench.json"))
@@ -121,15 +184,27 @@ def main() -> int:
     ap.add_argument("--small", action="store_true", help="a sixteenth of the batch, a tenth of the texts")
     ap.add_argument("--gap-extend", type=int, default=None, help="compare the affine scorer with the linear one")
     ap.add_argument("--gap-open", type=int, default=11, help="gap-open penalty of the affine scorer")
+    ap.add_argument("--hits", type=int, default=None,
+                    help="time search(k=HITS) on the search workload; with --gap-extend also its traced fill and its walk")
+    ap.add_argument("--tree", default=None,
+                    help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
+    if args.tree:
+        sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
     if not torch.cuda.is_available():
         print("score_bench: no GPU", file=sys.stderr)
         return 1
     from sa_amd import engine
-    report = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "workloads": []}
-    for w in workloads(args.small):
+    report = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "library": "another checkout (--tree)" if args.tree else "this tree",
+              "workloads": []}
+    for w in workloads(args.small, search_only=args.hits is not None):
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        if args.hits is not None:
+            row = hits_row(args, engine, w, dt, dp)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if args.gap_extend is not None:
             row = affine_rows(args, engine, w, dt, dp)
             report["workloads"].append(row)
