@@ -28,7 +28,8 @@ enum programArgs
 {
     CPU, GPU,                     // device
     DNA, PROTEIN,                 // sequence type
-    GLOBAL, LOCAL, SEMI_GLOBAL,   // algorithm (SEMI_GLOBAL is declared by the reference, never implemented)
+    GLOBAL, LOCAL, SEMI_GLOBAL,   // algorithm (SEMI_GLOBAL is declared by the reference, never implemented there;
+                                  // here scoreSequencesGPU, scoreSequencesGPUAffine and alignSequencesGPUAffine take it)
     SCORE_MATRIX,                 // next argument: score matrix file
     GAP_PENALTY,                  // next argument: gap penalty
 };
@@ -137,7 +138,9 @@ uint64_t alignSequenceGPUBatch(const Request *requests, Response *responses, uin
 /// Extension: Response::score of numRequests requests on `device`, without alignments (sa_score_batch:
 /// no direction matrix, no traceback). All requests must share one scoring scheme (alignment type,
 /// alphabet, score matrix, gap penalty). scores: numRequests entries. Returns 0, or 1 with the
-/// message on stdout.
+/// message on stdout. Request::alignmentType may also be SEMI_GLOBAL (sa_hip.h: SA_FIT, the whole
+/// pattern inside the text, the text free at both ends), here and in the two functions below; every
+/// other entry point and the CLI keep rejecting it.
 uint64_t scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores);
 
 /// Extension: the same under affine gap penalties (sa_score_batch_affine, Gotoh): a gap of k letters

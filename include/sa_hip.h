@@ -29,8 +29,28 @@ extern "C" {
 
 #define SA_ABI_VERSION 1
 
-/* Request::alignmentType (SequenceAlignment.hpp:78; GLOBAL/LOCAL of programArgs :17). */
-enum sa_mode { SA_GLOBAL = 0, SA_LOCAL = 1 };
+/* Request::alignmentType (SequenceAlignment.hpp:78; GLOBAL/LOCAL/SEMI_GLOBAL of programArgs :17).
+ *
+ * SA_FIT (semi-global, "fit"): the whole pattern p (m letters) inside the text t (n letters), the
+ * text free at both ends. The reference declares SEMI_GLOBAL and never implements it, so there is
+ * nothing to be bit-exact with; this is the definition. The recurrences are those of the other
+ * modes (linear, or Gotoh's under sa_score_batch_affine below).
+ *   borders: H[0][j] = 0 for every j; H[i][0] as in global mode, -i gap_penalty or
+ *            -(gap_open + (i - 1) gap_extend); F[0][j] follows from H[0][j] = 0
+ *   result:  score = max over j in 1..n of H[m][j]; end_pattern = m; end_text = the smallest such j
+ *            (column 0 is left out: it is never strictly better than column 1)
+ *   walk:    from (m, end_text) in state H with the tie rules of the other modes, until row 0; row 0
+ *            forces no LEFT moves, column 0 with i > 0 forces TOP
+ *   strings: start_text = the column the walk reached row 0 in = the 0-based index of the window's
+ *            first text letter, start_pattern = 0; aligned_text without its gap letters is
+ *            t[start_text : end_text], aligned_pattern without them is p
+ *   empty:   m == 0 scores 0 at (0, 0) with an empty alignment; n == 0 < m scores -m gap_penalty or
+ *            -(gap_open + (m - 1) gap_extend) at (m, 0): the pattern against m gap letters
+ * SA_FIT is taken by sa_score_batch, sa_scorer_create, sa_score_batch_affine,
+ * sa_scorer_create_affine, sa_align_pairs_affine, sa_search and sa_search_affine; sa_search aligns
+ * its fit hits as sa_align_pairs_affine does with gap_open = gap_extend = gap_penalty (the linear
+ * recurrence). sa_plan_create, sa_align_pair and sa_align_batch answer SA_ERR_UNSUPPORTED. */
+enum sa_mode { SA_GLOBAL = 0, SA_LOCAL = 1, SA_FIT = 2 };
 
 enum sa_status {
     SA_OK = 0,
@@ -43,7 +63,8 @@ enum sa_status {
 
 /* Scoring scheme of a Request (SequenceAlignment.hpp:71-99). */
 typedef struct sa_params {
-    int32_t mode;                 /* SA_GLOBAL (Needleman-Wunsch) or SA_LOCAL (Smith-Waterman)  */
+    int32_t mode;                 /* SA_GLOBAL (Needleman-Wunsch), SA_LOCAL (Smith-Waterman) or
+                                     SA_FIT (score-only and affine functions only, see sa_mode)  */
     int32_t alphabet_size;        /* Request::alphabetSize, 1..32 (4 DNA, 23 protein)           */
     int32_t gap_penalty;          /* Request::gapPenalty (linear gap, subtracted per gap cell)  */
     int32_t rows_per_lane;        /* 0 = automatic; else 1,2,4,8,16,32 (tuning knob)            */
@@ -195,7 +216,8 @@ typedef struct sa_score_result {
     int32_t status;        /* SA_OK or this pair's error                                */
     uint64_t end_text;     /* column j of the scored cell (global: text_len)            */
     uint64_t end_pattern;  /* row i of the scored cell (global: pattern_len); local: the
-                              first maximum in row-major order, (0,0) when the score is 0 */
+                              first maximum in row-major order, (0,0) when the score is 0;
+                              fit: (pattern_len, leftmost best column of that row)        */
 } sa_score_result;
 typedef struct sa_scorer sa_scorer;
 
@@ -240,7 +262,9 @@ int sa_scorer_create_affine(const sa_params *params, int32_t gap_open, int32_t g
  * be NULL. hit_index / hit_results: k entries. aligned_text / aligned_pattern: both NULL, or k host
  * buffers each of at least (its hit's text_len + query_len) bytes; buffers sized for the longest text
  * always do. The hits are aligned through a plan on the same device: their results and strings are
- * what sa_align_pair returns for the pair. k = 0 gives scores only. Synchronous. */
+ * what sa_align_pair returns for the pair. k = 0 gives scores only. Synchronous.
+ * In mode SA_FIT the plans cannot align: the hits go through sa_align_pairs_affine's path with
+ * gap_open = gap_extend = gap_penalty, which is the linear recurrence (see sa_mode). */
 int sa_search(const sa_params *params, const char *query, uint64_t query_len, const char *const *texts,
               const uint64_t *text_lens, int64_t num_texts, int k, int device, sa_score_result *scores,
               int64_t *hit_index, sa_result *hit_results, char *const *aligned_text,

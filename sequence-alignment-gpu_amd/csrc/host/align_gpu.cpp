@@ -27,10 +27,12 @@ int deviceFromEnv()
     return e ? std::atoi(e) : 0;
 }
 
-bool toParams(const SequenceAlignment::Request &request, sa_params *p)
+// `fit`: the caller is one of the functions that take SEMI_GLOBAL (the score-only and affine ones)
+bool toParams(const SequenceAlignment::Request &request, sa_params *p, bool fit = false)
 {
     if (request.alignmentType == SequenceAlignment::programArgs::GLOBAL) p->mode = SA_GLOBAL;
     else if (request.alignmentType == SequenceAlignment::programArgs::LOCAL) p->mode = SA_LOCAL;
+    else if (fit && request.alignmentType == SequenceAlignment::programArgs::SEMI_GLOBAL) p->mode = SA_FIT;
     else return false;
     p->alphabet_size = request.alphabetSize;
     p->gap_penalty = request.gapPenalty;
@@ -195,9 +197,9 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
     std::vector<sa_host_pair> pairs(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
-        if (!toParams(requests[i], &params[i]))
+        if (!toParams(requests[i], &params[i], true))
         {
-            std::cout << "error: only --global and --local alignments are implemented\n";
+            std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
             return 1;
         }
         if (gap) params[i].gap_penalty = 0;
@@ -243,9 +245,9 @@ uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Res
     std::vector<char *> at(numRequests), ap(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
-        if (!toParams(requests[i], &params[i]))
+        if (!toParams(requests[i], &params[i], true))
         {
-            std::cout << "error: only --global and --local alignments are implemented\n";
+            std::cout << "error: alignSequencesGPUAffine takes global, local and semi-global alignments\n";
             return 1;
         }
         params[i].gap_penalty = 0;

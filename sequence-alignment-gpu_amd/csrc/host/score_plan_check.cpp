@@ -1,7 +1,7 @@
 // bin/sa_score_plan_check: the score-only planner (sa_score_plan.cpp) as a stand-alone program. No
 // GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
 // the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
-//   sa_score_plan_check --mode global|local|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
+//   sa_score_plan_check --mode global|local|fit|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
 //                       [--gap-extend E] [--match M --mismatch X] NxM[xCOUNT] ...
 // With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
@@ -34,7 +34,7 @@ int main(int argc, char **argv)
         if (a == "--mode")
         {
             const std::string v = value();
-            P.mode = v == "global" ? SA_GLOBAL : v == "local" ? SA_LOCAL : std::atoi(v.c_str());
+            P.mode = v == "global" ? SA_GLOBAL : v == "local" ? SA_LOCAL : v == "fit" ? SA_FIT : std::atoi(v.c_str());
         }
         else if (a == "--alphabet") P.alphabet_size = std::atoi(value());
         else if (a == "--gap") P.gap_penalty = std::atoi(value());

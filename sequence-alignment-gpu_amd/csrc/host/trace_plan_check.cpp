@@ -1,7 +1,7 @@
 // bin/sa_trace_plan_check: the planner of the affine alignment path (sa_trace_plan.cpp) as a
 // stand-alone program. No GPU, no ROCm: it plans the pair shapes on its command line and prints the
 // plan as one JSON object (tests/test_trace_plan.py).
-//   sa_trace_plan_check --mode global|local|<int> --alphabet A --gap G --gap-extend E --cus N
+//   sa_trace_plan_check --mode global|local|fit|<int> --alphabet A --gap G --gap-extend E --cus N
 //                       [--budget BYTES] [--match M --mismatch X] NxM[xCOUNT] ...
 // --gap is the gap-open penalty. Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
@@ -32,7 +32,7 @@ int main(int argc, char **argv)
         if (a == "--mode")
         {
             const std::string v = value();
-            P.mode = v == "global" ? SA_GLOBAL : v == "local" ? SA_LOCAL : std::atoi(v.c_str());
+            P.mode = v == "global" ? SA_GLOBAL : v == "local" ? SA_LOCAL : v == "fit" ? SA_FIT : std::atoi(v.c_str());
         }
         else if (a == "--alphabet") P.alphabet_size = std::atoi(value());
         else if (a == "--gap") go = std::atoi(value());

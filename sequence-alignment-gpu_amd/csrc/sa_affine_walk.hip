@@ -1,5 +1,5 @@
 // Alignments under affine gap penalties (sa_hip.h: sa_align_pairs_affine; sa_search_affine in
-// sa_score.hip): align_affine_kernel<LOCAL, SMALL>, the traced instance of the affine wave program
+// sa_score.hip): align_affine_kernel<MODE, SMALL>, the traced instance of the affine wave program
 // (sa_score_wave.h, TRACE: four direction bits per cell), walk_affine_kernel, the traceback over the
 // three Gotoh states, and the host side that runs both chunk by chunk of the work order. What is run
 // is decided in sa_trace_plan.cpp (host only, no HIP). DESIGN.md §3.5 has the nibble, the walk and
@@ -24,11 +24,11 @@ struct AlignAffineArgs {
     TraceArgs tr;
 };
 
-template <bool LOCAL, bool SMALL>
+template <int MODE, bool SMALL>
 __global__ __launch_bounds__(64) void align_affine_kernel(AlignAffineArgs a)
 {
     __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, LOCAL, SMALL, true>(a.sa.s, a.sa.gap_extend, tab, a.tr);
+    score_wave<true, kTraceRows, MODE, SMALL, true>(a.sa.s, a.sa.gap_extend, tab, a.tr);
 }
 
 struct WalkArgs {
@@ -42,7 +42,7 @@ struct WalkArgs {
     char *out_text, *out_pattern;     // both null: results only, no letters are loaded or written
     const char *alphabet;             // A letters and the gap letter
     sa_result *results;
-    int32_t A, local;
+    int32_t A, mode;                  // mode: one of sa_mode
 };
 
 // One wave per pair; the walk of DESIGN.md §3.5: oracle_align's loop (oracle/sa_oracle.c) with a
@@ -56,6 +56,9 @@ struct WalkArgs {
 // loads the letters and writes 64 bytes per side, backwards from the end of the pair's slot.
 // The loop makes at most n + m moves whatever the direction words hold; a walk that has not ended by
 // then reports SA_ERR_HIP.
+// SA_FIT starts at (m, end_text) as a local walk starts at its best cell, moves as a global one
+// (column 0 forces TOP) and ends at row 0, where nothing forces LEFT: start_text is the column it
+// arrives in, the 0-based index of the window's first text letter, and start_pattern is 0.
 __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
 {
     const int lane = threadIdx.x;
@@ -70,11 +73,11 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     char *const op_end = a.out_pattern + slot + (uint64_t)n + (uint64_t)m;
     const uint32_t *const dirs = a.dirs + uniform64(a.dir_off[pi]);
     const uint32_t strip_words = (uint32_t)((n + 126) / 64) * (64u * 64u);
-    const bool local = a.local != 0;
+    const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT;
     const int A = a.A;
 
     int i = local ? min(uniform((int)sr.end_pattern), m) : m;
-    int j = local ? min(uniform((int)sr.end_text), n) : n;
+    int j = local || fit ? min(uniform((int)sr.end_text), n) : n;
     int ti = j - 1, pj = i - 1;  // the reference's text and pattern indices
     int state = kDirDiag;        // H; kDirLeft: inside a run of E, kDirTop: of F
     int len = 0;
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     const int max_moves = n + m;
     for (int it = 0;; ++it)
     {
-        if (local ? (i == 0 || j == 0) : (i == 0 && j == 0))
+        if (local ? (i == 0 || j == 0) : fit ? i == 0 : (i == 0 && j == 0))
         {
             ended = true;
             break;
@@ -151,6 +154,11 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
         pj = pj - tp > 0 ? pj - tp : 0;
     }
     flush(len & ~63, len & 63);
+    if (fit)  // no quirks: the column the walk reached row 0 in
+    {
+        ti = j;
+        pj = 0;
+    }
     if (lane == 0)
     {
         sa_result r;
@@ -197,17 +205,22 @@ struct Workspace {
     }
 };
 
-void launch_align(const AlignAffineArgs &a, bool local, bool small, int grid, hipStream_t st)
+void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st)
 {
-    if (local)
+    if (mode == SA_LOCAL)
     {
-        if (small) hipLaunchKernelGGL((align_affine_kernel<true, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((align_affine_kernel<true, false>), dim3(grid), dim3(64), 0, st, a);
+        if (small) hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, a);
+    }
+    else if (mode == SA_FIT)
+    {
+        if (small) hipLaunchKernelGGL((align_affine_kernel<SA_FIT, true>), dim3(grid), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((align_affine_kernel<SA_FIT, false>), dim3(grid), dim3(64), 0, st, a);
     }
     else
     {
-        if (small) hipLaunchKernelGGL((align_affine_kernel<false, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((align_affine_kernel<false, false>), dim3(grid), dim3(64), 0, st, a);
+        if (small) hipLaunchKernelGGL((align_affine_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((align_affine_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, a);
     }
 }
 
@@ -304,7 +317,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     wa.alphabet = d_alpha;
     wa.results = d_results;
     wa.A = A;
-    wa.local = pl.score.mode == SA_LOCAL;
+    wa.mode = pl.score.mode;
     uint32_t ctrl[2] = {0, 0};
     // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
     // copies into `results` and `ctrl` pending when this function returns
@@ -318,7 +331,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
             s.np = (int32_t)count;
             wa.order = s.order;
             HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            launch_align(fa, wa.local != 0, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st);
+            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
             hipLaunchKernelGGL(walk_affine_kernel, dim3((unsigned)count), dim3(64), 0, st, wa);

@@ -14,6 +14,12 @@
 
 namespace sa {
 
+// What sa_plan_create, sa_align_pair and sa_align_batch answer to mode SA_FIT (SA_ERR_UNSUPPORTED):
+// the plans have no fit mode, the score-only and traced wave paths do.
+constexpr const char *kFitUnsupported =
+    "SA_FIT is not implemented in the plans: use sa_score_batch, sa_scorer_create, sa_score_batch_affine, "
+    "sa_scorer_create_affine, sa_align_pairs_affine, sa_search or sa_search_affine";
+
 // Environment knobs, read once per process (the first time the engine needs one) and never again:
 // every field is a tuning or debugging switch; the defaults are the measured best settings.
 struct Knobs {

@@ -1,7 +1,7 @@
 // Score-only path (sa_hip.h: sa_score_batch*, sa_scorer_*, sa_search*): the score of every pair and
 // the cell it is read from, without direction planes, strip descriptors, records or a traceback.
-// Here are the two kernels, score_kernel<R, LOCAL, SMALL> (linear gap) and
-// score_affine_kernel<R, LOCAL, SMALL> (gap open / gap extend), both the one wave program of
+// Here are the two kernels, score_kernel<R, MODE, SMALL> (linear gap) and
+// score_affine_kernel<R, MODE, SMALL> (gap open / gap extend), MODE one of sa_mode, both the one wave program of
 // sa_score_wave.h, their launcher, and the host side of both. What a scorer runs is decided in
 // sa_score_plan.cpp (host-only, no HIP).
 #include <hip/hip_runtime.h>
@@ -22,18 +22,18 @@
 
 namespace sa {
 
-template <int R, bool LOCAL, bool SMALL>
+template <int R, int MODE, bool SMALL>
 __global__ __launch_bounds__(64) void score_kernel(ScoreArgs a)
 {
     __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<false, R, LOCAL, SMALL>(a, 0, tab);
+    score_wave<false, R, MODE, SMALL>(a, 0, tab);
 }
 
-template <int R, bool LOCAL, bool SMALL>
+template <int R, int MODE, bool SMALL>
 __global__ __launch_bounds__(64) void score_affine_kernel(ScoreAffineArgs aa)
 {
     __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, LOCAL, SMALL>(aa.s, aa.gap_extend, tab);
+    score_wave<true, R, MODE, SMALL>(aa.s, aa.gap_extend, tab);
 }
 
 }  // namespace sa
@@ -46,22 +46,27 @@ using namespace sa;
 namespace {
 
 // score_kernel or, with AFFINE, score_affine_kernel on `grid` one-wave workgroups: the one place that
-// picks <R, LOCAL, SMALL>. R is 1, 2, 4 or 8; a.gap is the linear penalty or the gap-open penalty.
+// picks <R, MODE, SMALL>. R is 1, 2, 4 or 8; mode is one of sa_mode (the planner has checked it);
+// a.gap is the linear penalty or the gap-open penalty.
 template <bool AFFINE>
-void launch_score(const ScoreArgs &a, int gap_extend, int R, bool local, bool small, int grid, hipStream_t st)
+void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st)
 {
     const ScoreAffineArgs aa = {a, gap_extend};
-    auto launch = [&](auto rc, auto localc, auto smallc) {
-        constexpr int RR = decltype(rc)::value;
-        constexpr bool LOCAL = decltype(localc)::value, SMALL = decltype(smallc)::value;
-        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, LOCAL, SMALL>), dim3(grid), dim3(64), 0, st, aa);
-        else hipLaunchKernelGGL((score_kernel<RR, LOCAL, SMALL>), dim3(grid), dim3(64), 0, st, a);
+    auto launch = [&](auto rc, auto modec, auto smallc) {
+        constexpr int RR = decltype(rc)::value, MODE = decltype(modec)::value;
+        constexpr bool SMALL = decltype(smallc)::value;
+        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, aa);
+        else hipLaunchKernelGGL((score_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, a);
     };
     auto with_r = [&](auto rc) {
         const std::true_type yes;
         const std::false_type no;
-        if (local) small ? launch(rc, yes, yes) : launch(rc, yes, no);
-        else small ? launch(rc, no, yes) : launch(rc, no, no);
+        const std::integral_constant<int, SA_GLOBAL> global;
+        const std::integral_constant<int, SA_LOCAL> local;
+        const std::integral_constant<int, SA_FIT> fit;
+        if (mode == SA_LOCAL) small ? launch(rc, local, yes) : launch(rc, local, no);
+        else if (mode == SA_FIT) small ? launch(rc, fit, yes) : launch(rc, fit, no);
+        else small ? launch(rc, global, yes) : launch(rc, global, no);
     };
     switch (R)
     {
@@ -208,9 +213,9 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     a.gap = s->gap;
     a.key_rowbits = s->key_rowbits;
     a.row_stride = s->row_stride;
-    const bool local = s->mode == SA_LOCAL, small = s->A <= 4;
-    if (s->affine) launch_score<true>(a, s->gap_extend, s->R, local, small, s->grid, st);
-    else launch_score<false>(a, 0, s->R, local, small, s->grid, st);
+    const bool small = s->A <= 4;
+    if (s->affine) launch_score<true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st);
+    else launch_score<false>(a, 0, s->R, s->mode, small, s->grid, st);
     HIP_TRY(hipGetLastError());
     return SA_OK;
 }
@@ -334,9 +339,13 @@ static int search(const sa_params *P, const ScoreGap *gapm, const char *query, u
     // the hits: the texts and the query are already on the device
     std::vector<sa_pair> hp((size_t)nh);
     for (int64_t h = 0; h < nh; ++h) hp[h] = dp[rank[h]];
-    rc = gapm ? align_affine_device(P, gapm->open, gapm->extend, hp.data(), nh, device, dt.p, dq.p, hit_results, aligned_text,
-                                    aligned_pattern)
-              : align_hits_linear(P, hp, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern);
+    // the plans have no fit mode: a linear fit search aligns through the traced path with
+    // gap_open = gap_extend = gap_penalty, which is the linear recurrence
+    const ScoreGap lin = {P->gap_penalty, P->gap_penalty};
+    const ScoreGap *const hg = gapm ? gapm : P->mode == SA_FIT ? &lin : nullptr;
+    rc = hg ? align_affine_device(P, hg->open, hg->extend, hp.data(), nh, device, dt.p, dq.p, hit_results, aligned_text,
+                                  aligned_pattern)
+            : align_hits_linear(P, hp, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern);
     if (rc) return rc;
     for (int64_t h = 0; h < nh; ++h) hit_index[h] = rank[h];
     *num_hits = nh;

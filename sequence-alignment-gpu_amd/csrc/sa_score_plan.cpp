@@ -45,7 +45,8 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
     const int A = P->alphabet_size;
     if (A < 1 || A > 32) return fail(SA_ERR_INVALID, "alphabet_size must be 1..32");
-    if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL) return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL or SA_LOCAL");
+    if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL && P->mode != SA_FIT)
+        return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL, SA_LOCAL or SA_FIT");
     if (np > INT32_MAX) return fail(SA_ERR_UNSUPPORTED, "more than 2^31-1 pairs");
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
@@ -105,11 +106,15 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
 
     // ---- rows per lane: a strip of 64R rows over n columns takes n + 63 steps of
     // kScoreStepBase + R * kScoreStepRow* instructions; the cheapest total wins, ties to the
-    // smaller R (fewer registers, more resident waves); the affine kernel has its own counts ----
+    // smaller R (fewer registers, more resident waves); the affine kernel has its own counts. A fit
+    // step is a global step plus the best of row m: kScoreFitStepBest + (R - 1) * kScoreFitStepSelect,
+    // the same in both kernels ----
     static const int kR[4] = {1, 2, 4, 8};
-    const int step_base = affine ? kScoreAffineStepBase : kScoreStepBase;
-    const int step_row = P->mode == SA_LOCAL ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
-                                             : (affine ? kScoreAffineStepRowGlobal : kScoreStepRowGlobal);
+    const bool fit = P->mode == SA_FIT;
+    const int step_base = (affine ? kScoreAffineStepBase : kScoreStepBase) + (fit ? kScoreFitStepBest - kScoreFitStepSelect : 0);
+    const int step_row = (P->mode == SA_LOCAL ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
+                                              : (affine ? kScoreAffineStepRowGlobal : kScoreStepRowGlobal)) +
+                         (fit ? kScoreFitStepSelect : 0);
     int best = 0;
     for (int k = 0; k < 4; ++k)
     {

@@ -34,6 +34,13 @@ constexpr int kScoreStepRowLocal = 10;
 constexpr int kScoreAffineStepBase = 18;
 constexpr int kScoreAffineStepRowGlobal = 10;
 constexpr int kScoreAffineStepRowLocal = 14;
+// A fit instance (SA_FIT) is the global one of its kernel plus, per step, the best of row m:
+// kScoreFitStepBest for the running best (the compare, the selects of the value and its step, the
+// step number) and kScoreFitStepSelect for each of the R - 1 conditional moves that pick the lane's
+// row among its R. Counted in the steady loops of both kernels: 5, 5 to 6, 7 to 8 and 10.5 to 13
+// instructions per step above the global instance at R = 1, 2, 4, 8.
+constexpr int kScoreFitStepBest = 5;
+constexpr int kScoreFitStepSelect = 1;
 
 // The affine gap model of a scorer: a gap of k cells costs open + (k - 1) * extend. With it,
 // sa_params.gap_penalty is ignored.

@@ -25,6 +25,17 @@
 // written as one 8-byte access under the same in-place rule. The borders need no minus infinity:
 // E[i][0] := H[i][0] - go + ge and F[0][j] := H[0][j] - go + ge make the first step of a run yield
 // H - go from both branches.
+//
+// MODE is SA_GLOBAL, SA_LOCAL or SA_FIT. SA_FIT (semi-global: the whole pattern inside the text, the
+// text free at both ends; sa_hip.h has the definition) is the global program with three changes, all
+// under `if constexpr (FIT)`: the top row fed to strip 0 is H[0][j] = 0 (its F stand-in derived from
+// it as above; column 0 stays global, -i g or -(go + (i - 1) ge)); the result is the leftmost maximum
+// of H[m][1..n]; and an empty pattern scores 0 at (0, 0), an empty text one run of m gaps at (m, 0).
+// Row m lies in one lane of the last strip (lane flm, its row frm), so there is no key and no merge
+// over lanes: every lane selects its row frm once per step and keeps one running best (value and
+// step; strictly greater keeps the first column), started below any score at every strip, and lane
+// flm's pair after the last strip is the result. A lane outside columns 1..n (ramp-up: it still holds
+// H[row][0]; ramp-down: H[row][n]) registers nothing, so column 0 is never reported.
 // DESIGN.md §3.4 has the resource usage of the instances, the rule for R and the step costs the
 // planner uses.
 //
@@ -80,10 +91,12 @@ enum { kDirLeft = 0, kDirDiag = 1, kDirTop = 2, kDirStop = 3, kDirEExt = 4, kDir
 
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
 // registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
-template <bool AFFINE, int R, bool LOCAL, bool SMALL, bool TRACE = false>
+template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false>
 __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs())
 {
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
+    static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
+    constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
     using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
     const int lane = threadIdx.x;
     const int A = a.A, g = a.gap, ge = gap_extend;
@@ -110,12 +123,12 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             // H[m][n] of an empty side is one run of max(n, m) gaps (alignSequenceCPU.cpp:232-236, :247-248)
             if (lane == 0)
             {
-                const int k = max(n, m);
+                const int k = FIT ? m : max(n, m);  // FIT: the text is free, only the pattern costs
                 sa_score_result r;
                 if constexpr (AFFINE) r.score = LOCAL || k == 0 ? 0 : -(g + (k - 1) * ge);
                 else r.score = LOCAL ? 0 : -g * k;
                 r.status = SA_OK;
-                r.end_text = LOCAL ? 0 : (uint64_t)n;
+                r.end_text = LOCAL || (FIT && m == 0) ? 0 : (uint64_t)n;
                 r.end_pattern = LOCAL ? 0 : (uint64_t)m;
                 a.out[pi] = r;
             }
@@ -127,6 +140,11 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         const int nbodies = (n + 63 + 63) / 64;  // steps 0 .. n + 62
         int hl[R];  // H[row][column - 1] of the lane's rows; after a strip, H[row][n]
         uint64_t lanekey = 0;
+        // FIT: row m is row `frm` of lane `flm` of the last strip; fbest is the first maximum of the
+        // lane's row frm over the strip's columns and fbestt the step it was met at
+        const int flast = m - 1 - (nstrips - 1) * 64 * R;
+        const int frm = flast % R, flm = flast / R;
+        int fbest = INT32_MIN, fbestt = 0;
         uint32_t *dlane = nullptr;  // TRACE: the lane's word of step 0 of the pair's first strip
         if constexpr (TRACE) dlane = tr.dirs + uniform64(tr.dir_off[pi]) + lane;
         for (int s = 0; s < nstrips; ++s)
@@ -163,6 +181,11 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 else hl[r] = LOCAL ? 0 : -(row1 + r + 1) * g;
                 best[r] = 0;
                 bestt[r] = 0;
+            }
+            if constexpr (FIT)
+            {
+                fbest = INT32_MIN;  // below any score: a row of negative values still has a first maximum
+                fbestt = 0;
             }
             int upprev;  // H[row1][column - 1]
             if constexpr (AFFINE) upprev = LOCAL || row1 == 0 ? 0 : -(g + (row1 - 1) * ge);
@@ -236,6 +259,17 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                         uf = f;
                     }
                 }
+                if constexpr (FIT)
+                {
+                    // one value per lane and step instead of the local instances' R: the lane's row frm.
+                    // A lane outside columns 1..n still (or again) holds H[row][0] (or H[row][n]): no column
+                    int v = hl[0];
+#pragma unroll
+                    for (int r = 1; r < R; ++r) v = r == frm ? hl[r] : v;
+                    const bool better = valid && v > fbest;
+                    fbest = better ? v : fbest;
+                    fbestt = better ? t : fbestt;
+                }
                 upprev = valid ? up : upprev;
                 // lane 63's bottom-row value enters, the rest move down
                 ofeed = dpp_shl1(hl[R - 1], ofeed);
@@ -260,7 +294,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 {
                     if (s == 0)
                     {
-                        feed = LOCAL ? 0 : -(g + c0 * ge);  // H[0][c0 + 1]
+                        feed = LOCAL || FIT ? 0 : -(g + c0 * ge);  // H[0][c0 + 1]
                         feedf = feed - g + ge;              // stands for F[0][c0 + 1] = -infinity
                     }
                     else
@@ -272,7 +306,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 }
                 else
                 {
-                    if (s == 0) feed = LOCAL ? 0 : -(c0 + 1) * g;
+                    if (s == 0) feed = LOCAL || FIT ? 0 : -(c0 + 1) * g;
                     else feed = c0 < n ? rowbuf[c0] : 0;
                 }
                 if (b == 0 || 64 * b + 64 > n)
@@ -317,6 +351,13 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             res.score = (int32_t)H;
             res.end_pattern = H ? (uint64_t)(~(uint32_t)(key >> kb) & kmask) : 0;
             res.end_text = H ? (uint64_t)(~(uint32_t)key & kmask) : 0;
+        }
+        else if constexpr (FIT)
+        {
+            // the last strip's values of lane flm; every row has columns 1..n, so the lane met one
+            res.score = __builtin_amdgcn_readlane(fbest, flm);
+            res.end_text = (uint64_t)(__builtin_amdgcn_readlane(fbestt, flm) - flm + 1);
+            res.end_pattern = (uint64_t)m;
         }
         else
         {

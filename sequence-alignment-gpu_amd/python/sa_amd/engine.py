@@ -14,6 +14,10 @@ PKG_ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 LIB_PATH = os.environ.get("SA_HIP_LIB", os.path.join(PKG_ROOT, "lib", "libsa_hip.so"))
 
 SA_GLOBAL, SA_LOCAL = 0, 1
+# sa_mode SA_FIT (semi-global): the whole pattern inside the text, the text free at both ends. Taken by
+# score_batch, Scorer, align_pairs_affine and search; Plan, align_pair and align_batch answer
+# SA_ERR_UNSUPPORTED.
+FIT = SA_FIT = 2
 STATUS = {0: "SA_OK", 1: "SA_ERR_INVALID", 2: "SA_ERR_NOMEM", 3: "SA_ERR_HIP", 4: "SA_ERR_UNSUPPORTED",
           5: "SA_ERR_TIMEOUT"}
 

@@ -23,7 +23,17 @@ linear search(k=K) of the same data. With --hits K alone, the linear search(k=K)
 takes the package and library from another built checkout, which is how the parent commit's figure of
 DESIGN.md 3.5 was taken.
 
+With --mode fit the fit scorers (sa_hip.h: SA_FIT): a read-mapping workload, 40000 DNA reads of 140
+to 160 letters, each a mutated piece of its own text window of 450 to 750 letters. The fit, global and
+local scorers run on the same pairs, alternated round by round in one process after a warm-up, once
+under the linear gap 5 and once under gap open 11 / gap extend 2. The report holds each median with its
+min and max, the fit / global and fit / local ratios of the medians beside the ratios of the planner's
+step-cost model, and whether the fit median is within the local median plus the local scorer's own
+min-max spread. Then search(k = --hits, default 100) in fit and in local mode on the search workload
+under 11 / 2, with the device times of the traced fill and of the walk.
+
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+    python3 tools/score_bench.py --mode fit [--small] --out profiles/r13/score_fit_bench.json
     python3 tools/score_bench.py --gap-extend 2 [--gap-open 11] --out profiles/r10/score_affine_bench.json
     python3 tools/score_bench.py --gap-extend 2 --hits 100 --out profiles/r12/score_affine_hits.json
     python3 tools/score_bench.py --hits 100 --tree ../parent --out profiles/r12/parent_linear_search.json
@@ -79,10 +89,100 @@ def stats(ms: list[float]) -> dict:
             "runs": len(ms)}
 
 
-def model_cost(pairs, R: int, local: bool, affine: bool) -> int:
-    """The planner's instruction count of a workload (sa_score_plan.h: kScoreStep*, kScoreAffineStep*)."""
+def model_cost(pairs, R: int, local: bool, affine: bool, fit: bool = False) -> int:
+    """The planner's instruction count of a workload (sa_score_plan.h: kScoreStep*, kScoreAffineStep*,
+    kScoreFitStep*)."""
     base, row = (18, 14 if local else 10) if affine else (14, 10 if local else 6)
-    return sum((n + 63) * -(-m // (64 * R)) * (base + R * row) for _, n, _, m in pairs if n and m)
+    step = base + R * row + (5 + (R - 1) if fit else 0)
+    return sum((n + 63) * -(-m // (64 * R)) * step for _, n, _, m in pairs if n and m)
+
+
+def mapping_workload(small: bool) -> dict:
+    """DNA reads of 140..160 letters, each a mutated piece of its own text window of 450..750 letters."""
+    from sa_amd import synthetic
+    npairs = 4000 if small else 40000
+    rng = np.random.default_rng(13)
+    nl, ml = rng.integers(450, 751, npairs), rng.integers(140, 161, npairs)
+    to, po = np.concatenate([[0], np.cumsum(nl)]), np.concatenate([[0], np.cumsum(ml)])
+    text = synthetic.random_sequence(5, int(to[-1]), 4)
+    at = rng.integers(0, nl - ml + 1)
+    src = np.concatenate([text[to[k] + at[k]:to[k] + at[k] + ml[k]] for k in range(npairs)])
+    pattern = synthetic.mutate(src, 6, 4, int(po[-1]))
+    return {"name": "mapping", "S": synthetic.blast_matrix(), "text": text, "pattern": pattern,
+            "pairs": [(int(to[k]), int(nl[k]), int(po[k]), int(ml[k])) for k in range(npairs)]}
+
+
+MODES = {"global": 0, "local": 1, "fit": 2}
+
+
+def fit_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
+    """The fit, global and local scorers of one gap model on the mapping workload, alternated."""
+    cells = sum(p[1] * p[3] for p in w["pairs"])
+    affine = gap_extend is not None
+    sc = {k: engine.Scorer(m, w["S"], gap, w["pairs"], gap_extend=gap_extend) for k, m in MODES.items()}
+    row = {"name": w["name"] + ("_affine" if affine else "_linear"), "pairs": len(w["pairs"]), "cells": cells, "gap": gap,
+           "gap_extend": gap_extend, "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for k, s in sc.items():  # warm-up
+        s.run(dt.data_ptr(), dp.data_ptr())
+        res[k] = s.results()
+    assert (res["global"]["score"] <= res["fit"]["score"]).all() and (res["fit"]["score"] <= res["local"]["score"]).all()
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            ms[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    for k, s in sc.items():
+        row[k + "_run"] = stats(ms[k])
+        row[k + "_gcups"] = round(cells / statistics.median(ms[k]) / 1e6, 1)
+        s.close()
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = max(ms["local"]) - min(ms["local"])
+    model = {k: model_cost(w["pairs"], row["scorers"][k]["rows_per_lane"], k == "local", affine, k == "fit") for k in sc}
+    row["fit_over_global"] = round(med["fit"] / med["global"], 3)
+    row["model_fit_over_global"] = round(model["fit"] / model["global"], 3)
+    row["fit_over_local"] = round(med["fit"] / med["local"], 3)
+    row["model_fit_over_local"] = round(model["fit"] / model["local"], 3)
+    row["local_spread_ms"] = round(spread, 3)
+    row["fit_within_local_plus_spread"] = bool(med["fit"] <= med["local"] + spread)
+    sweep = {}
+    for R in (1, 2, 4, 8):
+        s = engine.Scorer(2, w["S"], gap, w["pairs"], rows_per_lane=R, gap_extend=gap_extend)
+        s.run(dt.data_ptr(), dp.data_ptr())
+        assert s.results().tolist() == res["fit"].tolist(), f"fit R = {R} results differ"
+        t = [timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()) for _ in range(max(3, args.rounds))]
+        sweep[str(R)] = dict(stats(t), num_waves=s.info()["num_waves"], model=model_cost(w["pairs"], R, False, affine, True))
+        s.close()
+    row["fit_rows_per_lane_sweep"] = sweep
+    return row
+
+
+def fit_hits_row(args, engine, w) -> dict:
+    """search(k) in fit and in local mode on the search workload under gap open / gap extend: end to
+    end (wall clock) with the device time of the traced fill and of the walk of the hits."""
+    import time
+    texts = [w["text"][o:o + n] for o, n, _, _ in w["pairs"]]
+    q, k, ge = w["pattern"], args.hits or 100, args.gap_extend if args.gap_extend is not None else 2
+    row = {"name": w["name"] + "_fit_hits", "pairs": len(w["pairs"]), "hits": k, "gap_open": args.gap_open, "gap_extend": ge}
+    runs = {name: (lambda m=m: engine.search(m, q, texts, w["S"], args.gap_open, k, gap_extend=ge)) for name, m in
+            (("fit", 2), ("local", 1))}
+    out = {name: {"wall": [], "fill": [], "walk": []} for name in runs}
+    for name, run in runs.items():
+        _, hits = run()
+        row[name + "_hit_cells"] = sum(len(texts[h["index"]]) * len(q) for h in hits)
+    for _ in range(args.rounds):
+        for name, run in runs.items():
+            t0 = time.perf_counter()
+            run()
+            out[name]["wall"].append((time.perf_counter() - t0) * 1e3)
+            st = engine.affine_last_stats()
+            out[name]["fill"].append(st["fill_ms"])
+            out[name]["walk"].append(st["walk_ms"])
+            row[name + "_direction_arena_bytes"] = st["arena_bytes"]
+    for name in runs:
+        row[name + "_traced_fill_of_hits"] = stats(out[name]["fill"])
+        row[name + "_walk_of_hits"] = stats(out[name]["walk"])
+        row[name + "_search_end_to_end"] = stats(out[name]["wall"])
+    return row
 
 
 def affine_rows(args, engine, w, dt, dp) -> dict:
@@ -179,16 +279,20 @@ def hits_row(args, engine, w, dt, dp) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "score_bench.json"))
+    ap.add_argument("--out", default=None, help="profiles/r09/score_bench.json; --mode fit: profiles/r13/score_fit_bench.json")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--small", action="store_true", help="a sixteenth of the batch, a tenth of the texts")
     ap.add_argument("--gap-extend", type=int, default=None, help="compare the affine scorer with the linear one")
     ap.add_argument("--gap-open", type=int, default=11, help="gap-open penalty of the affine scorer")
     ap.add_argument("--hits", type=int, default=None,
                     help="time search(k=HITS) on the search workload; with --gap-extend also its traced fill and its walk")
+    ap.add_argument("--mode", choices=["fit"], default=None,
+                    help="fit: the fit scorers against the global and local ones on a read-mapping workload")
     ap.add_argument("--tree", default=None,
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", *(("r13", "score_fit_bench.json") if args.mode == "fit" else ("r09", "score_bench.json")))
     if args.tree:
         sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
@@ -198,7 +302,18 @@ def main() -> int:
     from sa_amd import engine
     report = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "library": "another checkout (--tree)" if args.tree else "this tree",
               "workloads": []}
-    for w in workloads(args.small, search_only=args.hits is not None):
+    if args.mode == "fit":
+        w = mapping_workload(args.small)
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        for gap, ge in ((5, None), (args.gap_open, args.gap_extend if args.gap_extend is not None else 2)):
+            row = fit_rows(args, engine, w, dt, dp, gap, ge)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+        del dt, dp
+        row = fit_hits_row(args, engine, next(workloads(args.small, search_only=True)))
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
+    for w in ([] if args.mode else workloads(args.small, search_only=args.hits is not None)):
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
         if args.hits is not None:
             row = hits_row(args, engine, w, dt, dp)
