@@ -156,6 +156,17 @@ uint64_t scoreSequencesGPUAffine(const Request *requests, uint64_t numRequests, 
 uint64_t alignSequencesGPUAffine(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                  int gapOpen, int gapExtend);
 
+/// Extension: the two functions above inside a diagonal band of half-width `band` >= 0
+/// (sa_score_batch_banded, sa_align_pairs_banded; sa_hip.h has the definition): cell (i, j) counts iff
+/// min(0, n - m) - band <= j - i <= max(0, n - m) + band, n text and m pattern letters. Global and
+/// local alignments only; a caller with a linear gap passes its penalty as gapOpen and gapExtend. With
+/// band >= max(n, m) every value equals the unbanded function's. Returns 0, or 1 with the message on
+/// stdout.
+uint64_t scoreSequencesGPUBanded(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                 int band, int *scores);
+uint64_t alignSequencesGPUBanded(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                 int gapOpen, int gapExtend, int band);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

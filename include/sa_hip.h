@@ -289,8 +289,41 @@ int sa_search_affine(const sa_params *params, int32_t gap_open, int32_t gap_exte
                      int k, int device, sa_score_result *scores, int64_t *hit_index, sa_result *hit_results,
                      char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits);
 
+/* ---- banded alignment: scores and alignments inside a diagonal band -------------------------- */
+
+/* For a pair with n text letters, m pattern letters and band half-width w >= 0 let d = n - m,
+ * lo = min(0, d) - w and hi = max(0, d) + w. Cell (i, j), 0 <= i <= m, 0 <= j <= n, border cells
+ * included, is in band iff lo <= j - i <= hi. (0, 0) and (m, n) are always in band, and every row has
+ * an in-band cell in columns 1..n.
+ * The recurrence is Gotoh's as sa_score_batch_affine states it, with one addition: H, E and F of every
+ * out-of-band cell are minus infinity. Nothing else changes: the borders of in-band border cells, the
+ * tie rules, the local clamp, the local result (the first maximum in row-major order,
+ * now over in-band cells; 0 at (0, 0) without a positive one) and the empty-side results.
+ * gap_open == gap_extend == g is the linear recurrence of gap penalty g: a caller with a linear gap
+ * passes its gap_penalty twice. The band is exact, cell by cell: no result depends on rows_per_lane,
+ * on the grid or on how the engine rounds its work. With w >= max(n, m) every cell is in band and
+ * every output equals that of the unbanded function (sa_score_batch_affine, sa_scorer_create_affine,
+ * sa_align_pairs_affine).
+ * One half-width serves all pairs of a call. Modes: SA_GLOBAL and SA_LOCAL; SA_FIT with a band is
+ * SA_ERR_UNSUPPORTED (a fit band needs a diagonal of its own). band < 0 is SA_ERR_INVALID. The score
+ * limit is half that of the unbanded functions: (max|S| + G)(n + m) + G (n + m) must stay below 2^29,
+ * G = max(|gap_open|, |gap_extend|) (SA_ERR_UNSUPPORTED). The search functions take no
+ * band: texts of unrelated lengths share no diagonal.
+ * The scorer is an ordinary sa_scorer (run, fetch, info, destroy). sa_align_pairs_banded keeps
+ * direction bits for the band only, about (2 w + |d| + 575) * 256 bytes per 512 rows (DESIGN.md 8
+ * has the exact sum): the chunks are cut by these bytes and a pair is refused only when its band
+ * exceeds SA_TRACE_ARENA_BYTES.
+ * sa_affine_last_stats reports the call. */
+int sa_score_batch_banded(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t band,
+                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_score_result *out);
+int sa_scorer_create_banded(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t band,
+                            const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_align_pairs_banded(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t band,
+                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                          char *const *aligned_text, char *const *aligned_pattern);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
- * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine or sa_search_affine (k > 0): device
+ * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

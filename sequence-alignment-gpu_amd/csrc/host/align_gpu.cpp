@@ -187,10 +187,11 @@ uint64_t SequenceAlignment::alignSequenceGPUFillMicros(const Request &request, R
 
 namespace
 {
-// scoreSequencesGPU and scoreSequencesGPUAffine: `gap` null is the requests' linear gapPenalty, else
-// {gap open, gap extend} and gapPenalty is ignored
+// scoreSequencesGPU, scoreSequencesGPUAffine and scoreSequencesGPUBanded: `gap` null is the requests'
+// linear gapPenalty, else {gap open, gap extend} and gapPenalty is ignored; `band` non-null is the
+// band's half-width
 uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
-                       int *scores, const char *name)
+                       int *scores, const char *name, const int *band = nullptr)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -212,8 +213,9 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
                                 requests[i].patternNumBytes};
     }
     std::vector<sa_score_result> res(numRequests);
-    const int rc = gap ? sa_score_batch_affine(&params[0], gap[0], gap[1], pairs.data(), (int64_t)numRequests, device, res.data())
-                       : sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
+    const int rc = band ? sa_score_batch_banded(&params[0], gap[0], gap[1], *band, pairs.data(), (int64_t)numRequests, device, res.data())
+                   : gap ? sa_score_batch_affine(&params[0], gap[0], gap[1], pairs.data(), (int64_t)numRequests, device, res.data())
+                         : sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
     if (rc != SA_OK)
     {
         std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
@@ -222,6 +224,10 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
     for (uint64_t i = 0; i < numRequests; ++i) scores[i] = res[i].score;
     return 0;
 }
+
+// alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded
+uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
+                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name);
 }  // namespace
 
 uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
@@ -236,8 +242,29 @@ uint64_t SequenceAlignment::scoreSequencesGPUAffine(const Request *requests, uin
     return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUAffine");
 }
 
+uint64_t SequenceAlignment::scoreSequencesGPUBanded(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                    int gapExtend, int band, int *scores)
+{
+    const int gap[2] = {gapOpen, gapExtend};
+    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUBanded", &band);
+}
+
 uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Response *responses, uint64_t numRequests,
                                                     int device, int gapOpen, int gapExtend)
+{
+    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUAffine");
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUBanded(const Request *requests, Response *responses, uint64_t numRequests,
+                                                    int device, int gapOpen, int gapExtend, int band)
+{
+    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, &band, "alignSequencesGPUBanded");
+}
+
+namespace
+{
+uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
+                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -247,13 +274,13 @@ uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Res
     {
         if (!toParams(requests[i], &params[i], true))
         {
-            std::cout << "error: alignSequencesGPUAffine takes global, local and semi-global alignments\n";
+            std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
             return 1;
         }
         params[i].gap_penalty = 0;
         if (!sameScheme(params[0], params[i]))
         {
-            std::cout << "error: alignSequencesGPUAffine needs one scoring scheme for all requests\n";
+            std::cout << "error: " << name << " needs one scoring scheme for all requests\n";
             return 1;
         }
         pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
@@ -263,8 +290,10 @@ uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Res
         ap[i] = responses[i].alignedPatternBytes;
     }
     std::vector<sa_result> res(numRequests);
-    const int rc = sa_align_pairs_affine(&params[0], gapOpen, gapExtend, pairs.data(), (int64_t)numRequests, device,
-                                         res.data(), at.data(), ap.data());
+    const int rc = band ? sa_align_pairs_banded(&params[0], gapOpen, gapExtend, *band, pairs.data(), (int64_t)numRequests, device,
+                                                res.data(), at.data(), ap.data())
+                        : sa_align_pairs_affine(&params[0], gapOpen, gapExtend, pairs.data(), (int64_t)numRequests, device,
+                                                res.data(), at.data(), ap.data());
     if (rc != SA_OK)
     {
         std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
@@ -273,3 +302,4 @@ uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Res
     for (uint64_t i = 0; i < numRequests; ++i) storeResult(res[i], responses[i]);
     return 0;
 }
+}  // namespace

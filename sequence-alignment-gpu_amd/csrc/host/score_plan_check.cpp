@@ -2,8 +2,11 @@
 // GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
 // the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
 //   sa_score_plan_check --mode global|local|fit|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
-//                       [--gap-extend E] [--match M --mismatch X] NxM[xCOUNT] ...
-// With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty.
+//                       [--gap-extend E] [--band W] [--match M --mismatch X] NxM[xCOUNT] ...
+// With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty. With --band W
+// it is the banded scorer's (sa_hip.h), and the plan also prints band_cells and, for the first 8
+// pairs, "bands": lo, hi, the pair's band cells and the [jmin, jmax, b0, b1] window of every strip at
+// the plan's R.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -24,7 +27,8 @@ int main(int argc, char **argv)
     P.alphabet_size = 4;
     P.gap_penalty = 5;
     int cus = 256, match = 5, mismatch = -4;
-    bool affine = false;
+    bool affine = false, banded = false;
+    int32_t band = 0;
     ScoreGap gapm = {0, 0};
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
@@ -42,6 +46,11 @@ int main(int argc, char **argv)
         {
             affine = true;
             gapm.extend = std::atoi(value());
+        }
+        else if (a == "--band")
+        {
+            banded = true;
+            band = std::atoi(value());
         }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
@@ -74,7 +83,8 @@ int main(int argc, char **argv)
     gapm.open = P.gap_penalty;
     ScorePlan pl;
     std::string err;
-    const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr);
+    const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr,
+                                   banded ? &band : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -90,6 +100,25 @@ int main(int argc, char **argv)
                 pl.affine ? "true" : "false", pl.gap_extend);
     // the order of a large batch is long: the first 64 entries
     for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
-    std::printf("]}\n");
+    std::printf("]");
+    if (banded)
+    {
+        std::printf(", \"band\": %d, \"band_cells\": %llu, \"bands\": [", pl.band, (unsigned long long)pl.band_cells);
+        for (size_t i = 0; i < pairs.size() && i < 8; ++i)
+        {
+            const int64_t n = (int64_t)pairs[i].text_len, m = (int64_t)pairs[i].pattern_len, rows = 64 * pl.R;
+            const Band bd = band_of(n, m, band);
+            std::printf("%s{\"lo\": %d, \"hi\": %d, \"cells\": %llu, \"windows\": [", i ? ", " : "", bd.lo, bd.hi,
+                        (unsigned long long)band_cells((uint64_t)n, (uint64_t)m, bd));
+            for (int64_t s = 0; n && m && s < (m + rows - 1) / rows; ++s)
+            {
+                const BandWindow bw = band_window(n, m, rows, s, bd);
+                std::printf("%s[%d, %d, %d, %d]", s ? ", " : "", bw.jmin, bw.jmax, bw.b0, bw.b1);
+            }
+            std::printf("]}");
+        }
+        std::printf("]");
+    }
+    std::printf("}\n");
     return 0;
 }

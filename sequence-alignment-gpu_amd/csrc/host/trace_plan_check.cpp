@@ -2,8 +2,10 @@
 // stand-alone program. No GPU, no ROCm: it plans the pair shapes on its command line and prints the
 // plan as one JSON object (tests/test_trace_plan.py).
 //   sa_trace_plan_check --mode global|local|fit|<int> --alphabet A --gap G --gap-extend E --cus N
-//                       [--budget BYTES] [--match M --mismatch X] NxM[xCOUNT] ...
-// --gap is the gap-open penalty. Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
+//                       [--budget BYTES] [--band W] [--match M --mismatch X] NxM[xCOUNT] ...
+// --gap is the gap-open penalty. With --band W the plan is the banded aligner's (sa_hip.h): dir_bytes
+// are the band's, "steps" is the sum of the strips' window steps, and each pair also lists the
+// [b0, b1] bodies of its strips' windows (the first 64 strips). Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -24,6 +26,8 @@ int main(int argc, char **argv)
     P.alphabet_size = 4;
     int cus = 256, match = 5, mismatch = -4, go = 11, ge = 2;
     uint64_t budget = trace_arena_budget();
+    bool banded = false;
+    int32_t band = 0;
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
     {
@@ -39,6 +43,11 @@ int main(int argc, char **argv)
         else if (a == "--gap-extend") ge = std::atoi(value());
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--budget") budget = std::strtoull(value(), nullptr, 10);
+        else if (a == "--band")
+        {
+            banded = true;
+            band = std::atoi(value());
+        }
         else if (a == "--match") match = std::atoi(value());
         else if (a == "--mismatch") mismatch = std::atoi(value());
         else
@@ -67,7 +76,8 @@ int main(int argc, char **argv)
 
     TracePlan pl;
     std::string err;
-    const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err);
+    const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err,
+                                   banded ? &band : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -85,10 +95,26 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < pl.score.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.score.order[i]);
     std::printf("], \"pairs\": [");
     for (size_t i = 0; i < pairs.size() && i < 64; ++i)
-        std::printf("%s{\"strips\": %llu, \"steps\": %llu, \"dir_bytes\": %llu, \"dir_off\": %llu, \"slot_off\": %llu}", i ? ", " : "",
-                    (unsigned long long)(pl.dir_bytes[i] ? trace_strips(pairs[i].pattern_len) : 0),
-                    (unsigned long long)(pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
+    {
+        const uint64_t strips = pl.dir_bytes[i] ? trace_strips(pairs[i].pattern_len) : 0;
+        std::printf("%s{\"strips\": %llu, \"steps\": %llu, \"dir_bytes\": %llu, \"dir_off\": %llu, \"slot_off\": %llu", i ? ", " : "",
+                    (unsigned long long)strips,
+                    (unsigned long long)(banded ? pl.dir_bytes[i] / kTraceStepBytes : pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
                     (unsigned long long)pl.dir_bytes[i], (unsigned long long)pl.dir_off[i], (unsigned long long)pl.slot_off[i]);
+        if (banded)
+        {
+            const int64_t n = (int64_t)pairs[i].text_len, m = (int64_t)pairs[i].pattern_len;
+            const Band bd = band_of(n, m, band);
+            std::printf(", \"windows\": [");
+            for (uint64_t s = 0; s < strips && s < 64; ++s)
+            {
+                const BandWindow bw = band_window(n, m, (int64_t)kTraceStripRows, (int64_t)s, bd);
+                std::printf("%s[%d, %d]", s ? ", " : "", bw.b0, bw.b1);
+            }
+            std::printf("]");
+        }
+        std::printf("}");
+    }
     std::printf("]}\n");
     return 0;
 }

@@ -31,6 +31,20 @@ __global__ __launch_bounds__(64) void align_affine_kernel(AlignAffineArgs a)
     score_wave<true, kTraceRows, MODE, SMALL, true>(a.sa.s, a.sa.gap_extend, tab, a.tr);
 }
 
+// align_affine_kernel inside a diagonal band of half-width `band` (sa_hip.h; sa_score_wave.h: BAND):
+// a strip stores direction words for the steps of its window only
+struct AlignBandArgs {
+    AlignAffineArgs a;
+    int32_t band;
+};
+
+template <int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void align_band_kernel(AlignBandArgs ba)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, kTraceRows, MODE, SMALL, true, true>(ba.a.sa.s, ba.a.sa.gap_extend, tab, ba.a.tr, ba.band);
+}
+
 struct WalkArgs {
     const int8_t *text, *pattern;
     const ScorePair *pairs;
@@ -43,6 +57,7 @@ struct WalkArgs {
     const char *alphabet;             // A letters and the gap letter
     sa_result *results;
     int32_t A, mode;                  // mode: one of sa_mode
+    int32_t band;                     // the half-width of a banded fill, or -1
 };
 
 // One wave per pair; the walk of DESIGN.md §3.5: oracle_align's loop (oracle/sa_oracle.c) with a
@@ -59,6 +74,15 @@ struct WalkArgs {
 // SA_FIT starts at (m, end_text) as a local walk starts at its best cell, moves as a global one
 // (column 0 forces TOP) and ends at row 0, where nothing forces LEFT: start_text is the column it
 // arrives in, the 0-based index of the window's first text letter, and start_pattern is 0.
+// After a banded fill (band >= 0) the words of strip s are those of its window's steps, 64 b0(s) ..
+// 64 b1(s) - 1, and the strips follow one another (trace_band_strip_words): the walk keeps the strip it
+// is in, that strip's first word and first step, counts up to the start cell's strip once and steps
+// back one strip at a time from there, as its rows only fall. A move to an out-of-band cell ends the
+// walk with SA_ERR_HIP. It cannot happen: H of an in-band cell takes E (F) only when that is a real
+// score, which needs a real H or E to the left (H or F above), that is, an in-band cell there; the
+// sentinel-derived values lose every maximum under the planner's limit (sa_score_wave.h, BAND).
+// BANDED is a template flag so that the unbanded walk pays for none of this.
+template <bool BANDED>
 __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
 {
     const int lane = threadIdx.x;
@@ -75,6 +99,11 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     const uint32_t strip_words = (uint32_t)((n + 126) / 64) * (64u * 64u);
     const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT;
     const int A = a.A;
+    constexpr bool banded = BANDED;
+    const Band bd = band_of(n, m, banded ? a.band : 0);
+    int bstrip = -1, bstep0 = 0;  // banded: the strip whose base is held, and its window's first step
+    int bsteps = INT32_MAX;       // and the number of its steps: no word is read outside the window
+    uint64_t bbase = 0;           // its first word
 
     int i = local ? min(uniform((int)sr.end_pattern), m) : m;
     int j = local || fit ? min(uniform((int)sr.end_text), n) : n;
@@ -117,8 +146,19 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
             const int t = j - 1 + l;
             if (col != cur || t0 - t >= 64)
             {
-                const int step = t - lane;
-                win = step >= 0 ? dirs[(uint64_t)(col >> 6) * strip_words + ((uint32_t)step * 64u + (uint32_t)l)] : 0u;
+                const int strip = col >> 6;
+                if (banded && strip != bstrip)
+                {
+                    if (bstrip < 0)
+                        for (bstrip = 0; bstrip < strip; ++bstrip) bbase += trace_band_strip_words(n, m, bstrip, bd);
+                    for (; bstrip > strip; --bstrip) bbase -= trace_band_strip_words(n, m, bstrip - 1, bd);
+                    const BandWindow bw = band_window(n, m, (int64_t)kTraceStripRows, strip, bd);
+                    bstep0 = 64 * bw.b0;
+                    bsteps = 64 * (bw.b1 - bw.b0);
+                }
+                const int step = t - lane - bstep0;
+                const uint64_t sbase = banded ? bbase : (uint64_t)strip * strip_words;
+                win = step >= 0 && (!banded || step < bsteps) ? dirs[sbase + ((uint32_t)step * 64u + (uint32_t)l)] : 0u;
                 cur = col;
                 t0 = t;
             }
@@ -145,6 +185,7 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
         i -= tp;
         state = next;
         if ((len & 63) == 0) flush(len - 64, 64);
+        if (banded && (uint32_t)(j - i - bd.lo) > (uint32_t)(bd.hi - bd.lo)) break;  // out of band: not ended
         if (local && (i == 0 || j == 0))  // the reference leaves before the decrement
         {
             ended = true;
@@ -205,9 +246,23 @@ struct Workspace {
     }
 };
 
-void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st)
+void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st, int band)
 {
-    if (mode == SA_LOCAL)
+    if (band >= 0)  // the planner admits global and local
+    {
+        const AlignBandArgs ba = {a, band};
+        if (mode == SA_LOCAL)
+        {
+            if (small) hipLaunchKernelGGL((align_band_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, ba);
+            else hipLaunchKernelGGL((align_band_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, ba);
+        }
+        else
+        {
+            if (small) hipLaunchKernelGGL((align_band_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, ba);
+            else hipLaunchKernelGGL((align_band_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, ba);
+        }
+    }
+    else if (mode == SA_LOCAL)
     {
         if (small) hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, a);
         else hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, a);
@@ -228,7 +283,7 @@ void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipS
 
 int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa_pair *pairs, int64_t np, int device,
                             const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
-                            char *const *aligned_pattern)
+                            char *const *aligned_pattern, const int32_t *band)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "affine aligner: null argument");
@@ -236,7 +291,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     TracePlan pl;
     std::string err;
-    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err))
+    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err, band))
         return fail(rc, err);
     if (!P->alphabet) return fail(SA_ERR_INVALID, "affine aligner: params->alphabet is null");
     g_stats = AffineStats();
@@ -318,6 +373,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     wa.results = d_results;
     wa.A = A;
     wa.mode = pl.score.mode;
+    wa.band = pl.score.band;
     uint32_t ctrl[2] = {0, 0};
     // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
     // copies into `results` and `ctrl` pending when this function returns
@@ -331,10 +387,11 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
             s.np = (int32_t)count;
             wa.order = s.order;
             HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st);
+            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, wa.band);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
-            hipLaunchKernelGGL(walk_affine_kernel, dim3((unsigned)count), dim3(64), 0, st, wa);
+            if (wa.band >= 0) hipLaunchKernelGGL(walk_affine_kernel<true>, dim3((unsigned)count), dim3(64), 0, st, wa);
+            else hipLaunchKernelGGL(walk_affine_kernel<false>, dim3((unsigned)count), dim3(64), 0, st, wa);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 2], st));
         }
@@ -378,10 +435,30 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     return SA_OK;
 }
 
+static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
+                            const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
+                            char *const *aligned_text, char *const *aligned_pattern);
+
 extern "C" {
 
 int sa_align_pairs_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_host_pair *pairs, int64_t np,
                           int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern);
+}
+
+int sa_align_pairs_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_host_pair *pairs,
+                          int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    return align_host_pairs(P, gap_open, gap_extend, &band, pairs, np, device, results, aligned_text, aligned_pattern);
+}
+
+}  // extern "C"
+
+// sa_align_pairs_affine and, with `band`, sa_align_pairs_banded: the host pairs packed into two arenas
+static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
+                            const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
+                            char *const *aligned_text, char *const *aligned_pattern)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
@@ -408,8 +485,11 @@ int sa_align_pairs_affine(const sa_params *P, int32_t gap_open, int32_t gap_exte
     if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
     if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
     if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
-    return align_affine_device(P, gap_open, gap_extend, dp.data(), np, device, dt.p, dpat.p, results, aligned_text, aligned_pattern);
+    return align_affine_device(P, gap_open, gap_extend, dp.data(), np, device, dt.p, dpat.p, results, aligned_text,
+                               aligned_pattern, band);
 }
+
+extern "C" {
 
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks)
 {

@@ -36,6 +36,19 @@ __global__ __launch_bounds__(64) void score_affine_kernel(ScoreAffineArgs aa)
     score_wave<true, R, MODE, SMALL>(aa.s, aa.gap_extend, tab);
 }
 
+// score_affine_kernel inside a diagonal band of half-width `band` (sa_hip.h; sa_score_wave.h: BAND)
+struct ScoreBandArgs {
+    ScoreAffineArgs sa;
+    int32_t band;
+};
+
+template <int R, int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void score_band_kernel(ScoreBandArgs ba)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, R, MODE, SMALL, false, true>(ba.sa.s, ba.sa.gap_extend, tab, TraceArgs(), ba.band);
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -47,15 +60,21 @@ namespace {
 
 // score_kernel or, with AFFINE, score_affine_kernel on `grid` one-wave workgroups: the one place that
 // picks <R, MODE, SMALL>. R is 1, 2, 4 or 8; mode is one of sa_mode (the planner has checked it);
-// a.gap is the linear penalty or the gap-open penalty.
-template <bool AFFINE>
-void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st)
+// a.gap is the linear penalty or the gap-open penalty. BAND (affine, global or local; band >= 0) is
+// score_band_kernel.
+template <bool AFFINE, bool BAND = false>
+void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st, int band = 0)
 {
     const ScoreAffineArgs aa = {a, gap_extend};
+    const ScoreBandArgs ba = {aa, band};
     auto launch = [&](auto rc, auto modec, auto smallc) {
         constexpr int RR = decltype(rc)::value, MODE = decltype(modec)::value;
         constexpr bool SMALL = decltype(smallc)::value;
-        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, aa);
+        if constexpr (BAND)
+        {
+            if constexpr (MODE != SA_FIT) hipLaunchKernelGGL((score_band_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ba);
+        }
+        else if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, aa);
         else hipLaunchKernelGGL((score_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, a);
     };
     auto with_r = [&](auto rc) {
@@ -102,8 +121,10 @@ void free_scorer(sa_scorer *s)
 
 }  // namespace
 
-// sa_scorer_create and sa_scorer_create_affine: `gapm` null is the linear scorer
-static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+// sa_scorer_create, sa_scorer_create_affine and sa_scorer_create_banded: `gapm` null is the linear
+// scorer, `band` non-null the banded one
+static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out,
+                         const int32_t *band = nullptr)
 {
     if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create: null argument");
     *out = nullptr;
@@ -112,7 +133,7 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm)) return fail(rc, err);
+    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm, band)) return fail(rc, err);
     std::vector<ScorePair> h((size_t)np);
     for (int64_t p = 0; p < np; ++p)
         h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
@@ -134,9 +155,9 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
     return SA_OK;
 }
 
-// sa_score_batch and sa_score_batch_affine
+// sa_score_batch, sa_score_batch_affine and sa_score_batch_banded
 static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_pair *pairs, int64_t np, int device,
-                       sa_score_result *out)
+                       sa_score_result *out, const int32_t *band = nullptr)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch: null argument");
     std::vector<sa_pair> dp((size_t)np);
@@ -152,7 +173,7 @@ static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_p
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     sa_scorer *raw = nullptr;
-    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw)) return rc;
+    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw, band)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
     std::vector<char> ht(tb), hp(pb);
     for (int64_t p = 0; p < np; ++p)
@@ -181,6 +202,13 @@ int sa_scorer_create_affine(const sa_params *P, int32_t gap_open, int32_t gap_ex
 {
     const ScoreGap gapm = {gap_open, gap_extend};
     return create_scorer(P, &gapm, pairs, np, device, out);
+}
+
+int sa_scorer_create_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_pair *pairs,
+                            int64_t np, int device, sa_scorer **out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return create_scorer(P, &gapm, pairs, np, device, out, &band);
 }
 
 int sa_scorer_destroy(sa_scorer *s)
@@ -214,7 +242,8 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     a.key_rowbits = s->key_rowbits;
     a.row_stride = s->row_stride;
     const bool small = s->A <= 4;
-    if (s->affine) launch_score<true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st);
+    if (s->band >= 0) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, s->band);
+    else if (s->affine) launch_score<true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st);
     else launch_score<false>(a, 0, s->R, s->mode, small, s->grid, st);
     HIP_TRY(hipGetLastError());
     return SA_OK;
@@ -255,6 +284,13 @@ int sa_score_batch_affine(const sa_params *P, int32_t gap_open, int32_t gap_exte
 {
     const ScoreGap gapm = {gap_open, gap_extend};
     return score_batch(P, &gapm, pairs, np, device, out);
+}
+
+int sa_score_batch_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_host_pair *pairs,
+                          int64_t np, int device, sa_score_result *out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return score_batch(P, &gapm, pairs, np, device, out, &band);
 }
 
 }  // extern "C"

@@ -39,7 +39,7 @@ int bitlen(uint64_t v)
 }  // namespace
 
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine)
+                    ScorePlan *out, std::string *err, const ScoreGap *affine, const int32_t *band)
 {
     auto fail = [&](int code, const char *msg) { *err = msg; return code; };
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
@@ -48,6 +48,12 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL && P->mode != SA_FIT)
         return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL, SA_LOCAL or SA_FIT");
     if (np > INT32_MAX) return fail(SA_ERR_UNSUPPORTED, "more than 2^31-1 pairs");
+    if (band)
+    {
+        if (!affine) return fail(SA_ERR_INVALID, "a band takes gap_open and gap_extend");
+        if (*band < 0) return fail(SA_ERR_INVALID, "band must be >= 0");
+        if (P->mode == SA_FIT) return fail(SA_ERR_UNSUPPORTED, "SA_FIT takes no band");
+    }
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
     if (R == 16 || R == 32) R = 8;  // a params struct shared with a plan: the scorer's tallest strip
@@ -78,6 +84,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
         const uint64_t span = n + m;
         const uint64_t bound = ((uint64_t)sabs + (uint64_t)std::llabs(g)) * span + (uint64_t)std::llabs(g) * span;
         if (bound >= (1ull << 30)) return fail(SA_ERR_UNSUPPORTED, "scores may exceed the int32 range");
+        if (band && bound >= kBandScoreLimit) return fail(SA_ERR_UNSUPPORTED, "scores may reach the band's sentinel");
         const uint64_t h = g >= 0 ? (uint64_t)std::max<int64_t>(smax, 0) * std::min(n, m)
                                   : ((uint64_t)sabs + (uint64_t)(-g)) * span;
         hmax_local = std::max(hmax_local, h);
@@ -93,6 +100,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     pl.gap = affine ? affine->open : (int)g;
     pl.affine = affine != nullptr;
     pl.gap_extend = affine ? affine->extend : 0;
+    pl.band = band ? *band : -1;
     pl.num_pairs = np;
     pl.num_cu = kn.max_cus > 0 ? std::min(num_cu, kn.max_cus) : num_cu;
 
@@ -100,13 +108,20 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     // pairs start first and the short ones fill the tail) ----
     pl.order.resize((size_t)np);
     std::iota(pl.order.begin(), pl.order.end(), 0);
-    std::stable_sort(pl.order.begin(), pl.order.end(), [&](int32_t a, int32_t b) {
-        return pairs[a].text_len * pairs[a].pattern_len > pairs[b].text_len * pairs[b].pattern_len;
-    });
+    std::vector<uint64_t> cells((size_t)np);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
+        cells[p] = band ? band_cells(n, m, band_of((int64_t)n, (int64_t)m, *band)) : n * m;
+        if (band) pl.band_cells += cells[p];
+    }
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](int32_t a, int32_t b) { return cells[a] > cells[b]; });
 
     // ---- rows per lane: a strip of 64R rows over n columns takes n + 63 steps of
     // kScoreStepBase + R * kScoreStepRow* instructions; the cheapest total wins, ties to the
-    // smaller R (fewer registers, more resident waves); the affine kernel has its own counts. A fit
+    // smaller R (fewer registers, more resident waves); the affine kernel has its own counts. A banded
+    // strip takes the steps of its window, jmax - jmin + 64 (n + 63 when the band admits every cell): a
+    // tall strip under a narrow band mostly steps through out-of-band cells, so R falls with the band. A fit
     // step is a global step plus the best of row m: kScoreFitStepBest + (R - 1) * kScoreFitStepSelect,
     // the same in both kernels ----
     static const int kR[4] = {1, 2, 4, 8};
@@ -124,7 +139,18 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
         {
             const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
             if (n == 0 || m == 0) continue;
-            c += (n + 63) * ((m + rows - 1) / rows) * per_step;
+            const uint64_t strips = (m + rows - 1) / rows;
+            if (!band)
+            {
+                c += (n + 63) * strips * per_step;
+                continue;
+            }
+            const Band bd = band_of((int64_t)n, (int64_t)m, *band);
+            for (uint64_t s = 0; s < strips; ++s)
+            {
+                const BandWindow bw = band_window((int64_t)n, (int64_t)m, (int64_t)rows, (int64_t)s, bd);
+                c += (uint64_t)(bw.jmax - bw.jmin + 64) * per_step;
+            }
         }
         pl.cost[k] = c;
         if (c < pl.cost[best]) best = k;
@@ -132,8 +158,17 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     pl.R = R ? R : kR[best];
     for (int64_t p = 0; p < np; ++p)
     {
-        const uint64_t rows = 64ull * pl.R;
-        pl.padded_cells += pairs[p].text_len * ((pairs[p].pattern_len + rows - 1) / rows) * rows;
+        const uint64_t rows = 64ull * pl.R, n = pairs[p].text_len, m = pairs[p].pattern_len, strips = (m + rows - 1) / rows;
+        if (!band || n == 0) pl.padded_cells += n * strips * rows;
+        else
+        {
+            const Band bd = band_of((int64_t)n, (int64_t)m, *band);
+            for (uint64_t s = 0; s < strips; ++s)
+            {
+                const BandWindow bw = band_window((int64_t)n, (int64_t)m, (int64_t)rows, (int64_t)s, bd);
+                pl.padded_cells += (uint64_t)(bw.jmax - bw.jmin + 1) * rows;
+            }
+        }
     }
 
     // ---- launch and workspace ----

@@ -6,6 +6,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -48,10 +49,61 @@ struct ScoreGap {
     int32_t open, extend;
 };
 
+#if defined(__HIPCC__)
+#define SA_BAND_FN __host__ __device__ inline
+#else
+#define SA_BAND_FN inline
+#endif
+
+// The diagonal band of a pair (sa_hip.h has the definition): cell (i, j) is in band iff
+// lo <= j - i <= hi. A half-width above max(n, m) admits every cell already and is cut to it, so
+// everything below stays inside 32 bits for the lengths the planner admits (n, m < 2^24).
+struct Band {
+    int32_t lo, hi;
+};
+SA_BAND_FN Band band_of(int64_t n, int64_t m, int64_t w)
+{
+    const int64_t d = n - m, big = n > m ? n : m, ww = w < big ? w : big;
+    return Band{(int32_t)((d < 0 ? d : 0) - ww), (int32_t)((d > 0 ? d : 0) + ww)};
+}
+// The window of strip s of `rows` rows (rows * s + 1 .. min(m, rows * (s + 1))): its in-band columns
+// jmin .. jmax, never empty. Lane 0 meets column jmin at step jmin - 1 and lane 63 column jmax at step
+// jmax + 62, so the strip runs the 64-step bodies b0 .. b1 - 1, and jmax - jmin + 64 of their steps
+// touch the band. With every cell in band that is 0 .. nbodies - 1 and n + 63, the unbanded strip.
+struct BandWindow {
+    int32_t jmin, jmax, b0, b1;
+};
+SA_BAND_FN BandWindow band_window(int64_t n, int64_t m, int64_t rows, int64_t s, Band bd)
+{
+    const int64_t first = rows * s + 1, last = m < rows * (s + 1) ? m : rows * (s + 1);
+    const int64_t jmin = first + bd.lo > 1 ? first + bd.lo : 1, jmax = last + bd.hi < n ? last + bd.hi : n;
+    return BandWindow{(int32_t)jmin, (int32_t)jmax, (int32_t)((jmin - 1) / 64), (int32_t)((jmax + 62) / 64 + 1)};
+}
+// Cells (i, j), 1 <= i <= m, 1 <= j <= n, inside the band: the sum over the rows of
+// min(n, i + hi) - max(1, i + lo) + 1, in closed form.
+inline uint64_t band_cells(uint64_t n_, uint64_t m_, Band bd)
+{
+    const int64_t n = (int64_t)n_, m = (int64_t)m_, lo = bd.lo, hi = bd.hi;
+    if (n == 0 || m == 0) return 0;
+    const int64_t k = std::min(std::max<int64_t>(n - hi, 0), m);  // rows whose last column is i + hi
+    const int64_t right = k * (k + 1) / 2 + k * hi + (m - k) * n;
+    const int64_t k2 = std::min(std::max<int64_t>(-lo, 0), m);    // rows whose first column is 1
+    const int64_t left = k2 + (m * (m + 1) / 2 - k2 * (k2 + 1) / 2) + (m - k2) * lo;
+    return (uint64_t)(right - left + m);
+}
+
+// The value of H, E and F of every out-of-band cell, and the limit of the banded planner: with
+// (max|S| + G)(n + m) + G (n + m) < kBandScoreLimit (G the larger of |gap open| and |gap extend|) no
+// score falls below -2^29 + G, and a value derived from the sentinel, at most two penalties above
+// it, stays below that and inside int32.
+constexpr int32_t kBandSentinel = -(1 << 30);
+constexpr uint64_t kBandScoreLimit = 1ull << 29;
+
 struct ScorePlan {
     int mode = 0, A = 0, gap = 0, R = 1, key_rowbits = 1;  // gap: the linear penalty, or gap open
     bool affine = false;           // score_affine_kernel: gap, gap_extend
     int gap_extend = 0;
+    int band = -1;                 // banded scorer (affine only): the half-width; -1: the whole rectangle
     int num_cu = 0, waves_per_simd = 0, grid = 0;
     int64_t num_pairs = 0;
     uint64_t max_text = 0;         // longest text
@@ -59,15 +111,19 @@ struct ScorePlan {
                                    // each, affine an (H, F) pair of ints each
     uint64_t input_bytes = 0;      // text and pattern letters of every pair (the caller's arenas)
     uint64_t device_bytes = 0;     // inputs, descriptors, results, row buffers, constants
-    uint64_t padded_cells = 0;     // sum of n * ceil(m / 64R) * 64R
+    uint64_t padded_cells = 0;     // sum of n * ceil(m / 64R) * 64R; banded: of each strip's in-band columns * 64R
+    uint64_t band_cells = 0;       // banded: cells inside the bands of all pairs
     uint64_t cost[4] = {0, 0, 0, 0};  // the model's cost of R = 1, 2, 4, 8 (instructions per wave)
-    std::vector<int32_t> order;    // pair indices, most cells first, ties by index
+    std::vector<int32_t> order;    // pair indices, most cells (banded: band cells) first, ties by index
 };
 
 // Plans `np` pairs for a device of `num_cu` compute units. Returns SA_OK, or the SA_ERR_* code with
 // its message in *err. `affine` null: the linear gap P->gap_penalty; else the affine gap model.
+// `band` non-null: the banded scorer of that half-width (affine only, global or local): a strip is
+// charged the steps of its window, the work order and padded_cells count band cells, and the score
+// limit is kBandScoreLimit.
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr);
+                    ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr, const int32_t *band = nullptr);
 
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).

@@ -44,6 +44,37 @@
 // step, stored at dirs[(strip * steps + t) * 64 + lane] of the pair's directions, steps = 64 nbodies.
 // Every step stores, the predicated ones too; the words of lanes outside columns 1..n and the nibbles
 // of rows past m are never read. DESIGN.md §3.5 has the nibble and the walk that reads it.
+//
+// BAND (AFFINE, global or local: score_band_kernel, align_band_kernel) keeps to the diagonal band of
+// sa_hip.h: cell (i, j) is in band iff lo <= j - i <= hi, and H, E and F of every other cell are
+// kBandSentinel. Everything banded is under `if constexpr (BAND)` or MASK; the other instances compile
+// to what they were. A strip runs only the bodies of its window (band_window, sa_score_plan.h), with
+// the step numbers and the lane skew of the whole strip, so a cell's step, its column and the local
+// key do not change.
+//  - Start. In body 0 a border cell (i, 0) is real down to row -lo and the sentinel below it. A window
+//    that starts at body b0 >= 1 has every lane's first cell left of the band, so hl, el and upprev
+//    start at the sentinel; only lane 0's upprev, the cell (64R s, 64 b0) of the row above the strip,
+//    can be the band's left edge, and is read from the row buffer under the mask.
+//  - Top row. A column of the row above the strip is taken from the row buffer (strip 0: from the
+//    border formula) only if it is in band for that row; any other column reads as the sentinel,
+//    whatever the buffer holds there from an earlier strip or from the pair this wave scored before.
+//  - Bottom row. The write-back covers the columns lane 63 met in the window's bodies, 64 b0 - 62 ..
+//    64 (b1 - 1) + 1. Inside a window the writes trail the reads by 63 columns as before. Between
+//    strips: the in-band columns of row 64R (s + 1) lie between the jmin and the jmax of strip s,
+//    whose window spans them (band_window takes jmax from the strip's last row), so strip s wrote
+//    each of them after strip s read it, and strip s + 1 trusts no other column. What strip s + 1
+//    writes lies at or left of columns it has read or masks.
+//  - Cells. A body whose diagonals all lie in the band (and whose columns all lie in 1..n) runs the
+//    plain step. Any other body runs the MASK step: after the recurrence and the local clamp an
+//    out-of-band cell becomes the sentinel in H, E and F, so it never exceeds a local best and hands
+//    exactly the sentinel on; a lane outside columns 1..n keeps its state as in the unbanded program.
+//  - Values. An in-band cell's diagonal neighbour is in band, so its H is a real score. Its E (F) is
+//    sentinel-derived only when the cell to its left (above) is out of band: the sentinel minus one
+//    penalty; the next cell's E (F) takes the real H - go instead. Under the planner's limit
+//    (kBandScoreLimit) such a value stays below every real score minus a penalty and inside int32, so
+//    it never wins a maximum, never ties, and no direction nibble that is read points out of band.
+//  - TRACE stores a word only for the steps the strip runs: the pair's directions are the strips'
+//    windows one after another, 64 (b1 - b0) steps of 64 words each (trace_band_dir_bytes).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +83,7 @@
 #include <type_traits>
 
 #include "sa_hip.h"
+#include "sa_score_plan.h"
 #include "sa_wave.h"
 
 namespace sa {
@@ -89,14 +121,21 @@ struct TraceArgs {
 // bit 3 F extends
 enum { kDirLeft = 0, kDirDiag = 1, kDirTop = 2, kDirStop = 3, kDirEExt = 4, kDirFExt = 8 };
 
+// the step of a banded body that cuts a band edge: predicated as std::true_type is, and masked
+struct MaskedStep : std::true_type {
+};
+
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
 // registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
-template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false>
-__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs())
+template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false>
+__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs(),
+                                           int band = 0)
 {
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
+    static_assert(!BAND || (AFFINE && MODE != SA_FIT), "banded instances: affine, global or local");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
+    constexpr int SENT = kBandSentinel;
     using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
     const int lane = threadIdx.x;
     const int A = a.A, g = a.gap, ge = gap_extend;
@@ -147,9 +186,22 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         int fbest = INT32_MIN, fbestt = 0;
         uint32_t *dlane = nullptr;  // TRACE: the lane's word of step 0 of the pair's first strip
         if constexpr (TRACE) dlane = tr.dirs + uniform64(tr.dir_off[pi]) + lane;
+        // BAND: cell (i, j) is in band iff (unsigned)(j - i - blo) <= bspan
+        int blo = 0;
+        uint32_t bspan = 0;
+        if constexpr (BAND)
+        {
+            const Band bd = band_of(n, m, band);
+            blo = bd.lo;
+            bspan = (uint32_t)(bd.hi - bd.lo);
+        }
         for (int s = 0; s < nstrips; ++s)
         {
             const int row1 = s * 64 * R + R * lane;  // rows row1 + 1 .. row1 + R
+            // the strip's bodies: all of them, or (BAND) its window's
+            BandWindow bw = {};
+            if constexpr (BAND) bw = band_window(n, m, 64 * R, s, Band{blo, blo + (int)bspan});
+            const int bfirst = BAND ? bw.b0 : 0, bend = BAND ? bw.b1 : nbodies;
             int s0[R], s1[R], s2[R], s3[R];  // S[pattern letter of the row][0..3] (SMALL)
             int prow[R];               // A * pattern letter of the row (LDS table row)
             int el[R];                 // AFFINE: E[row][column - 1]
@@ -179,6 +231,14 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     el[r] = hl[r] - g + ge;  // stands for E[row][0] = -infinity
                 }
                 else hl[r] = LOCAL ? 0 : -(row1 + r + 1) * g;
+                if constexpr (BAND)
+                {
+                    // a window past body 0 starts left of the band in every row; in body 0 the border
+                    // cell (row, 0) is in band down to row -lo
+                    const bool in = bfirst == 0 && row1 + r + 1 <= -blo;
+                    hl[r] = in ? hl[r] : SENT;
+                    el[r] = in ? el[r] : SENT;
+                }
                 best[r] = 0;
                 bestt[r] = 0;
             }
@@ -190,13 +250,30 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             int upprev;  // H[row1][column - 1]
             if constexpr (AFFINE) upprev = LOCAL || row1 == 0 ? 0 : -(g + (row1 - 1) * ge);
             else upprev = LOCAL ? 0 : -row1 * g;
+            if constexpr (BAND)
+            {
+                if (bfirst == 0) upprev = row1 <= -blo ? upprev : SENT;
+                else
+                {
+                    // the cell left of the window in the row above: out of band for every lane but 0,
+                    // whose row above is the previous strip's last and may have its band edge there
+                    const int col = 64 * bfirst;  // >= 64 and < n; the previous strip's window holds it
+                    const bool in = lane == 0 && (uint32_t)(col - row1 - blo) <= bspan;
+                    upprev = in ? rowbuf[col - 1].x : SENT;
+                }
+            }
             int tl = 0, tfeed = 0, feed = 0, ofeed = 0;
             int fb = 0;                  // AFFINE: F[row1 + R][column] of the lane's last step,
             int feedf = 0, ofeedf = 0;   // and the F halves of the top-row feed and the bottom-row collection
             uint32_t *dstrip = nullptr;  // TRACE: the lane's word of step 0 of this strip
-            if constexpr (TRACE) dstrip = dlane + (uint64_t)s * (uint64_t)nbodies * (64 * 64);
+            if constexpr (TRACE)
+            {
+                if constexpr (BAND) dstrip = dlane;  // advanced past each strip's window below
+                else dstrip = dlane + (uint64_t)s * (uint64_t)nbodies * (64 * 64);
+            }
             auto step = [&](auto predc, const int t) {
                 constexpr bool PRED = decltype(predc)::value;
+                constexpr bool MASK = BAND && std::is_same<decltype(predc), MaskedStep>::value;  // a body that cuts a band edge
                 const int up = dpp_shr1(feed, hl[R - 1]);  // lane 0: the top row's next column
                 int upf = 0;
                 if constexpr (AFFINE) upf = dpp_shr1(feedf, fb);  // and its F
@@ -209,6 +286,12 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 const bool b0 = (tl & 1) != 0, b1 = (tl & 2) != 0;
                 int d = upprev, u = up, uf = upf;
                 uint32_t word = 0;  // TRACE: the direction nibbles of the lane's rows
+                // MASK: row r's cell lies qq - r diagonals above the band's lower edge
+                int qq = 0;
+                if constexpr (BAND)  // outside the test of MASK: an unbanded instance's step captures nothing more
+                {
+                    if constexpr (MASK) qq = t - lane - row1 - blo;
+                }
 #pragma unroll
                 for (int r = 0; r < R; ++r)
                 {
@@ -239,6 +322,17 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     else h = max(d + sv, max(hl[r] - g, u - g));
                     if (LOCAL) h = max(h, 0);
                     d = hl[r];
+                    if constexpr (BAND)
+                    {
+                        if constexpr (MASK)
+                        {
+                            // an out-of-band cell is the sentinel in all three states, after the clamp
+                            const bool in = (uint32_t)(qq - r) <= bspan;
+                            h = in ? h : SENT;
+                            e = in ? e : SENT;
+                            f = in ? f : SENT;
+                        }
+                    }
                     if (PRED)
                     {
                         h = valid ? h : hl[r];
@@ -278,9 +372,10 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     fb = valid ? uf : fb;
                     ofeedf = dpp_shl1(fb, ofeedf);
                 }
-                if constexpr (TRACE) dstrip[(uint32_t)t * 64u] = word;
+                if constexpr (TRACE && BAND) dstrip[(uint32_t)(t - 64 * bfirst) * 64u] = word;
+                else if constexpr (TRACE) dstrip[(uint32_t)t * 64u] = word;
             };
-            for (int b = 0; b < nbodies; ++b)
+            for (int b = bfirst; b < bend; ++b)
             {
                 const int c0 = 64 * b + lane;  // text index of tfeed; feed holds column c0 + 1
                 tfeed = 0;
@@ -303,13 +398,42 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                         feed = v.x;
                         feedf = v.y;
                     }
+                    if constexpr (BAND)
+                    {
+                        // column c0 + 1 of the row above the strip: past the band's edge the row buffer
+                        // holds what an earlier strip or pair left there, and strip 0's border has no end
+                        const bool in = c0 < n && (uint32_t)(c0 + 1 - s * 64 * R - blo) <= bspan;
+                        feed = in ? feed : SENT;
+                        feedf = in ? feedf : SENT;
+                    }
                 }
                 else
                 {
                     if (s == 0) feed = LOCAL || FIT ? 0 : -(c0 + 1) * g;
                     else feed = c0 < n ? rowbuf[c0] : 0;
                 }
-                if (b == 0 || 64 * b + 64 > n)
+                // BAND: the body's diagonals j - i run from lane 63's last row at its first step to lane
+                // 0's first row at its last step; a body that holds one outside the band masks its cells
+                if constexpr (BAND)
+                {
+                    const int dmin = 64 * b - 64 * R * s - 64 * R - 62, dmax = 64 * b + 63 - 64 * R * s;
+                    if (dmin < blo || dmax > blo + (int)bspan)
+                    {
+#pragma unroll 2
+                        for (int k = 0; k < 64; ++k) step(MaskedStep{}, 64 * b + k);
+                    }
+                    else if (b == 0 || 64 * b + 64 > n)
+                    {
+#pragma unroll 2
+                        for (int k = 0; k < 64; ++k) step(std::true_type{}, 64 * b + k);
+                    }
+                    else
+                    {
+#pragma unroll 4
+                        for (int k = 0; k < 64; ++k) step(std::false_type{}, 64 * b + k);
+                    }
+                }
+                else if (b == 0 || 64 * b + 64 > n)
                 {
 #pragma unroll 2
                     for (int k = 0; k < 64; ++k) step(std::true_type{}, 64 * b + k);
@@ -330,6 +454,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     }
                 }
             }
+            if constexpr (TRACE && BAND) dlane += (uint64_t)(bend - bfirst) * (64 * 64);
             if (LOCAL)
             {
 #pragma unroll

@@ -38,6 +38,24 @@ inline uint64_t trace_dir_bytes(uint64_t n, uint64_t m)
     return n == 0 || m == 0 ? 0 : trace_strips(m) * trace_steps(n) * kTraceStepBytes;
 }
 
+// The same of a banded pair (sa_hip.h; band_of and band_window in sa_score_plan.h): a strip stores
+// only the steps of its window, 64 (b1 - b0) of them, and the strips' windows follow one another. The
+// planner sizes the pair with it, the traced fill advances by it strip after strip, and the walk
+// finds a strip's first word with it. With every cell in band it is trace_dir_bytes.
+SA_BAND_FN uint64_t trace_band_strip_words(int64_t n, int64_t m, int64_t s, Band bd)
+{
+    const BandWindow bw = band_window(n, m, (int64_t)kTraceStripRows, s, bd);
+    return (uint64_t)(bw.b1 - bw.b0) * (64 * 64);
+}
+inline uint64_t trace_band_dir_bytes(uint64_t n, uint64_t m, int64_t band)
+{
+    if (n == 0 || m == 0) return 0;
+    const Band bd = band_of((int64_t)n, (int64_t)m, band);
+    uint64_t words = 0;
+    for (uint64_t s = 0; s < trace_strips(m); ++s) words += trace_band_strip_words((int64_t)n, (int64_t)m, (int64_t)s, bd);
+    return words * 4;
+}
+
 struct TracePlan {
     ScorePlan score;                  // validation, work order, key bits, grid and boundary rows (R = 8, affine)
     uint64_t budget = 0;              // direction bytes one chunk may hold
@@ -53,7 +71,10 @@ struct TracePlan {
 
 // Plans `np` pairs. Returns SA_OK, or the SA_ERR_* code with its message in *err: make_score_plan's
 // for the affine gap model, or SA_ERR_UNSUPPORTED for a pair whose directions exceed `budget`.
+// `band` non-null: the banded aligner; a pair's directions are its band's (trace_band_dir_bytes), the
+// chunks are cut by them, and a pair is refused only when its band exceeds the budget.
 int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
-                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err);
+                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err,
+                    const int32_t *band = nullptr);
 
 }  // namespace sa

@@ -31,7 +31,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_plan_output_bytes", "sa_plan_fetch_all", "sa_align_batch", "sa_batch_deal", "sa_build_id",
            "sa_batch_last_stats", "sa_plan_fill_kind", "sa_score_batch", "sa_scorer_create", "sa_scorer_run",
            "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search", "sa_score_batch_affine",
-           "sa_scorer_create_affine", "sa_align_pairs_affine", "sa_search_affine", "sa_affine_last_stats")
+           "sa_scorer_create_affine", "sa_align_pairs_affine", "sa_search_affine", "sa_affine_last_stats",
+           "sa_score_batch_banded", "sa_scorer_create_banded", "sa_align_pairs_banded")
 
 
 class SaParams(ctypes.Structure):
@@ -118,6 +119,12 @@ def _load():
                                         ctypes.POINTER(SaResult), P, P]
     L.sa_search_affine.argtypes = [ctypes.POINTER(SaParams), ctypes.c_int32, ctypes.c_int32, P, U64, P, P, ctypes.c_int64,
                                    I, I, P, P, P, P, P, ctypes.POINTER(ctypes.c_int64)]
+    I32 = ctypes.c_int32
+    L.sa_score_batch_banded.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_banded.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                          ctypes.POINTER(P)]
+    L.sa_align_pairs_banded.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.c_int64, I,
+                                        ctypes.POINTER(SaResult), P, P]
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_int32)]
     for name in EXPORTS:
@@ -218,11 +225,12 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
-                       gap_extend: int, device: int = 0, strings: bool = True) -> list[dict]:
+                       gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
-    ones. With gap_open == gap_extend == g every value is align_pair's for gap g."""
-    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings)
+    ones. With gap_open == gap_extend == g every value is align_pair's for gap g. With `band`,
+    sa_align_pairs_banded: the alignment inside the diagonal band of that half-width (sa_hip.h)."""
+    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band)
 
 
 def affine_last_stats() -> dict:
@@ -233,8 +241,9 @@ def affine_last_stats() -> dict:
     return {"fill_ms": f.value, "walk_ms": w.value, "arena_bytes": b.value, "num_chunks": c.value}
 
 
-def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings) -> list[dict]:
-    """align_batch (gap_extend None) and align_pairs_affine: one packing of the host pairs and buffers."""
+def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings, band=None) -> list[dict]:
+    """align_batch (gap_extend None) and align_pairs_affine (with `band`, sa_align_pairs_banded): one
+    packing of the host pairs and buffers."""
     p, S_keep, alpha_keep = _params(mode, S, gap, alphabet, 0)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
@@ -247,8 +256,10 @@ def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, devic
     res = (SaResult * max(1, n))()
     if gap_extend is None:
         _check(lib.sa_align_batch(ctypes.byref(p), hp, n, num_gpus, res, at, ap))
-    else:
+    elif band is None:
         _check(lib.sa_align_pairs_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, res, at, ap))
+    else:
+        _check(lib.sa_align_pairs_banded(ctypes.byref(p), gap, gap_extend, band, hp, n, device, res, at, ap))
     out = []
     for i, r in enumerate(res[:n]):
         d = {"score": r.score, "num_bytes": r.num_alignment_bytes, "start_text": r.start_text,
@@ -349,17 +360,22 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
-                device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None) -> np.ndarray:
+                device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
-    the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend."""
+    the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
+    sa_score_batch_banded: the scores inside the diagonal band of that half-width (sa_hip.h); without
+    `gap_extend` the gap is linear, gap_open = gap_extend = gap."""
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
     n = len(ts)
     hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
     out = np.zeros(max(1, n), SCORE_DTYPE)
-    if gap_extend is None:
+    if band is not None:
+        _check(lib.sa_score_batch_banded(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, band, hp, n,
+                                         device, out.ctypes.data))
+    elif gap_extend is None:
         _check(lib.sa_score_batch(ctypes.byref(p), hp, n, device, out.ctypes.data))
     else:
         _check(lib.sa_score_batch_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, out.ctypes.data))
@@ -368,17 +384,21 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 class Scorer:
     """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback).
-    With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty."""
+    With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty. With
+    `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear)."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
-                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None):
+                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None):
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)
         self.pairs = pairs
         self.device = device
         h = ctypes.c_void_p()
-        if gap_extend is None:
+        if band is not None:
+            _check(lib.sa_scorer_create_banded(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, band,
+                                               arr, len(pairs), device, ctypes.byref(h)))
+        elif gap_extend is None:
             _check(lib.sa_scorer_create(ctypes.byref(self._p), arr, len(pairs), device, ctypes.byref(h)))
         else:
             _check(lib.sa_scorer_create_affine(ctypes.byref(self._p), gap, gap_extend, arr, len(pairs), device,

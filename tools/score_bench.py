@@ -33,6 +33,17 @@ min-max spread. Then search(k = --hits, default 100) in fit and in local mode on
 under 11 / 2, with the device times of the traced fill and of the walk.
 
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+With --band W [W ...] the banded scorer and aligner (sa_hip.h: sa_scorer_create_banded,
+sa_align_pairs_banded): related pairs of about 20000 DNA letters, each pattern its text with 5 %
+substitutions and 0.1 % deletions, under gap open / gap extend. Scorer.run of the unbanded affine scorer
+and of the banded one at each W, alternated round by round after a warm-up (device events; median, min
+and max), the measured banded / unbanded ratio of the medians beside the planner's (band steps over
+full steps, each at its planned rows per lane); then align_pairs_affine with and without the band on the
+first pairs (device time of the traced fill and of the walk, sa_affine_last_stats). On a subsample the
+unbanded alignments' paths are read back from their strings: no banded score may exceed the unbanded
+one, and where the path stays inside the band the two must be equal.
+
+    python3 tools/score_bench.py --band 64 500 [--small] --out profiles/r14/score_band_bench.json
     python3 tools/score_bench.py --mode fit [--small] --out profiles/r13/score_fit_bench.json
     python3 tools/score_bench.py --gap-extend 2 [--gap-open 11] --out profiles/r10/score_affine_bench.json
     python3 tools/score_bench.py --gap-extend 2 --hits 100 --out profiles/r12/score_affine_hits.json
@@ -113,6 +124,100 @@ def mapping_workload(small: bool) -> dict:
 
 
 MODES = {"global": 0, "local": 1, "fit": 2}
+
+
+def related_workload(small: bool) -> dict:
+    """Pairs of about 20000 DNA letters: each pattern is its text with 5 % substitutions and 0.1 %
+    deletions, so the optimal path stays within a few tens of cells of the band's two diagonals."""
+    from sa_amd import synthetic
+    npairs, side = (128, 20000) if small else (2048, 20000)
+    text = synthetic.random_sequence(21, npairs * side, 4)
+    pats = [synthetic.mutate(text[k * side:(k + 1) * side], 1000 + k, 4, None, p_del=0.001, p_ins=0.0, p_sub=0.05) for k in range(npairs)]
+    po = np.concatenate([[0], np.cumsum([len(x) for x in pats])])
+    return {"name": "related", "S": synthetic.blast_matrix(), "text": text, "pattern": np.concatenate(pats),
+            "pairs": [(k * side, side, int(po[k]), len(pats[k])) for k in range(npairs)]}
+
+
+def band_model_cost(pairs, R: int, band: int) -> int:
+    """The planner's instruction count of the banded global affine scorer (sa_score_plan.h: band_window):
+    a strip is charged jmax - jmin + 64 steps."""
+    step, rows, total = 18 + R * 10, 64 * R, 0
+    for _, n, _, m in pairs:
+        w = min(band, max(n, m))
+        lo, hi = min(0, n - m) - w, max(0, n - m) + w
+        for first in range(1, m + 1, rows):
+            total += (min(n, min(m, first + rows - 1) + hi) - max(1, first + lo) + 64) * step
+    return total
+
+
+def path_diagonals(res) -> tuple[int, int]:
+    """The lowest and highest j - i over the cells of a global alignment, read from its strings."""
+    d = lo = hi = 0
+    for a, b in zip(res["aligned_text"], res["aligned_pattern"]):
+        d += (a != "-") - (b != "-")
+        lo, hi = min(lo, d), max(hi, d)
+    return lo, hi
+
+
+def band_rows(args, engine, w, dt, dp) -> dict:
+    import time
+    go, ge, pairs = args.gap_open, args.gap_extend if args.gap_extend is not None else 2, w["pairs"]
+    cells = sum(p[1] * p[3] for p in pairs)
+    row = {"name": w["name"], "pairs": len(pairs), "cells": cells, "gap_open": go, "gap_extend": ge, "bands": {}}
+    sc = {"unbanded": engine.Scorer(0, w["S"], go, pairs, gap_extend=ge)}
+    for b in args.band:
+        sc[str(b)] = engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, band=b)
+    res, t = {}, {k: [] for k in sc}
+    for k, s in sc.items():  # warm-up, and the scores
+        s.run(dt.data_ptr(), dp.data_ptr())
+        res[k] = s.results()["score"].copy()
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            t[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    row["unbanded"] = dict(stats(t["unbanded"]), **sc["unbanded"].info(), gcups=round(cells / statistics.median(t["unbanded"]) / 1e6, 1))
+    full_model = model_cost(pairs, row["unbanded"]["rows_per_lane"], False, True)
+    # the subsample: unbanded alignments, their paths, and the banded scores against them
+    sub = list(range(0, len(pairs), max(1, len(pairs) // 16)))
+    texts = [w["text"][pairs[k][0]:pairs[k][0] + pairs[k][1]] for k in sub]
+    pats = [w["pattern"][pairs[k][2]:pairs[k][2] + pairs[k][3]] for k in sub]
+    full = engine.align_pairs_affine(0, texts, pats, w["S"], go, ge)
+    assert [f["score"] for f in full] == res["unbanded"][sub].tolist(), "the unbanded scorer and aligner differ"
+    diags = [path_diagonals(f) for f in full]
+    for b in args.band:
+        k = str(b)
+        info = sc[k].info()
+        assert (res[k] <= res["unbanded"]).all(), f"band {b}: a banded score exceeds the unbanded one"
+        free = [i for i, (pr, (dlo, dhi)) in enumerate(zip(sub, diags))
+                if min(0, pairs[pr][1] - pairs[pr][3]) - b <= dlo and dhi <= max(0, pairs[pr][1] - pairs[pr][3]) + b]
+        assert all(res[k][sub[i]] == full[i]["score"] for i in free), f"band {b}: scores differ where the band does not bind"
+        model = band_model_cost(pairs, info["rows_per_lane"], b)
+        row["bands"][k] = dict(stats(t[k]), **info, subsample=len(sub), subsample_band_does_not_bind=len(free),
+                               pairs_with_the_unbanded_score=int((res[k] == res["unbanded"]).sum()),
+                               banded_over_unbanded=round(statistics.median(t[k]) / statistics.median(t["unbanded"]), 4),
+                               model_banded_over_unbanded=round(model / full_model, 4))
+    for s in sc.values():
+        s.close()
+    # aligned runs on the first pairs: banded and unbanded alternated
+    nal = min(len(pairs), 16 if args.small else 64)
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in pairs[:nal]]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in pairs[:nal]]
+    al = {k: {"fill_ms": [], "walk_ms": [], "wall_ms": []} for k in ["unbanded"] + [str(b) for b in args.band]}
+    got = {}
+    for rnd in range(1 + max(3, args.rounds // 2)):
+        for k in al:
+            t0 = time.perf_counter()
+            got[k] = engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, band=None if k == "unbanded" else int(k))
+            wall = (time.perf_counter() - t0) * 1e3
+            st = engine.affine_last_stats()
+            if rnd:  # round 0 warms up
+                al[k]["fill_ms"].append(st["fill_ms"]), al[k]["walk_ms"].append(st["walk_ms"]), al[k]["wall_ms"].append(wall)
+            al[k]["arena_bytes"], al[k]["num_chunks"] = st["arena_bytes"], st["num_chunks"]
+    row["aligned"] = {"pairs": nal}
+    for k, v in al.items():
+        same = sum(g == f for g, f in zip(got[k], got["unbanded"]))
+        row["aligned"][k] = {"fill": stats(v["fill_ms"]), "walk": stats(v["walk_ms"]), "end_to_end_wall": stats(v["wall_ms"]),
+                             "arena_bytes": v["arena_bytes"], "num_chunks": v["num_chunks"], "alignments_equal_to_unbanded": same}
+    return row
 
 
 def fit_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
@@ -288,11 +393,14 @@ def main() -> int:
                     help="time search(k=HITS) on the search workload; with --gap-extend also its traced fill and its walk")
     ap.add_argument("--mode", choices=["fit"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload")
+    ap.add_argument("--band", type=int, nargs="+", default=None,
+                    help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--tree", default=None,
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", *(("r13", "score_fit_bench.json") if args.mode == "fit" else ("r09", "score_bench.json")))
+        args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
+                                                    ("r13", "score_fit_bench.json") if args.mode == "fit" else ("r09", "score_bench.json")))
     if args.tree:
         sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
@@ -302,7 +410,14 @@ def main() -> int:
     from sa_amd import engine
     report = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "library": "another checkout (--tree)" if args.tree else "this tree",
               "workloads": []}
-    if args.mode == "fit":
+    if args.band:
+        w = related_workload(args.small)
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        row = band_rows(args, engine, w, dt, dp)
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
+        del dt, dp
+    elif args.mode == "fit":
         w = mapping_workload(args.small)
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
         for gap, ge in ((5, None), (args.gap_open, args.gap_extend if args.gap_extend is not None else 2)):
@@ -313,7 +428,7 @@ def main() -> int:
         row = fit_hits_row(args, engine, next(workloads(args.small, search_only=True)))
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
-    for w in ([] if args.mode else workloads(args.small, search_only=args.hits is not None)):
+    for w in ([] if args.mode or args.band else workloads(args.small, search_only=args.hits is not None)):
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
         if args.hits is not None:
             row = hits_row(args, engine, w, dt, dp)
