@@ -167,6 +167,19 @@ uint64_t scoreSequencesGPUBanded(const Request *requests, uint64_t numRequests, 
 uint64_t alignSequencesGPUBanded(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                  int gapOpen, int gapExtend, int band);
 
+/// Extension: scores and alignments with free sequence ends (sa_hip.h: SA_ENDS_FREE; sa_score_batch_affine
+/// and sa_align_pairs_affine in mode SA_ENDS_FREE | freeEnds). freeEnds is any of SA_FREE_TEXT_BEGIN (1),
+/// SA_FREE_TEXT_END (2), SA_FREE_PATTERN_BEGIN (4) and SA_FREE_PATTERN_END (8) or'ed together: 15 is the
+/// overlap (dovetail) alignment, 3 the fit of the pattern inside the text, 0 global alignment.
+/// Request::alignmentType is ignored (programArgs is the reference's enum and has no such type), and so
+/// is Request::gapPenalty: a caller with a linear gap passes its penalty as gapOpen and gapExtend. One
+/// alphabet and score matrix for all requests. Response::startInAlignedText and startInAlignedPattern
+/// are the 0-based indices of the first aligned letters. Returns 0, or 1 with the message on stdout.
+uint64_t scoreSequencesGPUEndsFree(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                   int freeEnds, int *scores);
+uint64_t alignSequencesGPUEndsFree(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                   int gapOpen, int gapExtend, int freeEnds);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

@@ -49,8 +49,48 @@ extern "C" {
  * SA_FIT is taken by sa_score_batch, sa_scorer_create, sa_score_batch_affine,
  * sa_scorer_create_affine, sa_align_pairs_affine, sa_search and sa_search_affine; sa_search aligns
  * its fit hits as sa_align_pairs_affine does with gap_open = gap_extend = gap_penalty (the linear
- * recurrence). sa_plan_create, sa_align_pair and sa_align_batch answer SA_ERR_UNSUPPORTED. */
-enum sa_mode { SA_GLOBAL = 0, SA_LOCAL = 1, SA_FIT = 2 };
+ * recurrence). sa_plan_create, sa_align_pair and sa_align_batch answer SA_ERR_UNSUPPORTED.
+ *
+ * SA_ENDS_FREE (ends-free alignment): global alignment in which each of the four sequence ends may
+ * cost nothing. mode = SA_ENDS_FREE | any of the four flags below, 16..31; 3..15 and values from 32
+ * on are SA_ERR_INVALID. TB, TE, PB, PE stand for the flags. SA_OVERLAP (all four) is the overlap
+ * (dovetail) alignment of assembly and read merging; TB | PE asks whether the end of the text
+ * overlaps the start of the pattern; PB | PE is the text contained in the pattern. The recurrence is
+ * the linear one, or Gotoh's as sa_score_batch_affine states it; gap(k) is k gap_penalty, or
+ * gap_open + (k - 1) gap_extend.
+ *   borders:    H[0][0] = 0; H[0][j] = TB ? 0 : -gap(j); H[i][0] = PB ? 0 : -gap(i); E[i][0] and
+ *               F[0][j] are minus infinity
+ *   candidates: (m, n) always; (m, j), 0 <= j <= n, if TE; (i, n), 0 <= i <= m, if PE
+ *   result:     the maximum of H over the candidates; sa_score_result.end_pattern and end_text are
+ *               its cell. Ties: an interior candidate (i >= 1 and j >= 1) beats a border candidate;
+ *               among interior candidates the first in row-major order wins, so a last-column cell
+ *               (i < m, n) comes before every cell of row m, and within row m the leftmost wins; among
+ *               border candidates the first in row-major order wins
+ *   empty:      with n == 0 or m == 0 every candidate is a border cell and the rules above apply to
+ *               the border values (penalties may be negative: gap(k) need not grow with k)
+ *   walk:       from the result cell in state H with the tie rules of the other modes (DESIGN.md
+ *               3.5); it ends at (i, j) when i == 0 && (TB || j == 0) or j == 0 && (PB || i == 0);
+ *               otherwise column 0 forces TOP and row 0 forces LEFT
+ *   strings:    start_text = j and start_pattern = i of the cell the walk ended in, without quirks;
+ *               aligned_text without its gap letters is t[start_text : end_text], aligned_pattern
+ *               without them is p[start_pattern : end_pattern]
+ * Identities: SA_ENDS_FREE | TB | TE gives every output of SA_FIT. SA_ENDS_FREE alone gives every
+ * output of SA_GLOBAL, but for a pair with both sides empty, where global keeps the reference's
+ * (uint64)-1 starts and ends-free reports 0. Swapping text and pattern (the score matrix
+ * transposed) while swapping TB with PB and TE with PE gives the same score.
+ * The modes are taken by sa_score_batch, sa_scorer_create, sa_score_batch_affine,
+ * sa_scorer_create_affine, sa_align_pairs_affine, sa_search and sa_search_affine; sa_search aligns
+ * its hits as sa_align_pairs_affine does with gap_open = gap_extend = gap_penalty. The banded
+ * functions (a band with free ends needs a diagonal of its own), sa_plan_create, sa_align_pair and
+ * sa_align_batch answer SA_ERR_UNSUPPORTED. */
+enum sa_mode { SA_GLOBAL = 0, SA_LOCAL = 1, SA_FIT = 2, SA_ENDS_FREE = 16 };
+enum sa_free_end {
+    SA_FREE_TEXT_BEGIN = 1,    /* TB: H[0][j] = 0                             */
+    SA_FREE_TEXT_END = 2,      /* TE: the result may lie anywhere in row m    */
+    SA_FREE_PATTERN_BEGIN = 4, /* PB: H[i][0] = 0                             */
+    SA_FREE_PATTERN_END = 8,   /* PE: the result may lie anywhere in column n */
+    SA_OVERLAP = SA_ENDS_FREE | 15
+};
 
 enum sa_status {
     SA_OK = 0,
@@ -63,8 +103,9 @@ enum sa_status {
 
 /* Scoring scheme of a Request (SequenceAlignment.hpp:71-99). */
 typedef struct sa_params {
-    int32_t mode;                 /* SA_GLOBAL (Needleman-Wunsch), SA_LOCAL (Smith-Waterman) or
-                                     SA_FIT (score-only and affine functions only, see sa_mode)  */
+    int32_t mode;                 /* SA_GLOBAL (Needleman-Wunsch), SA_LOCAL (Smith-Waterman), or
+                                     SA_FIT or SA_ENDS_FREE | flags (score-only and affine
+                                     functions only, see sa_mode)                                */
     int32_t alphabet_size;        /* Request::alphabetSize, 1..32 (4 DNA, 23 protein)           */
     int32_t gap_penalty;          /* Request::gapPenalty (linear gap, subtracted per gap cell)  */
     int32_t rows_per_lane;        /* 0 = automatic; else 1,2,4,8,16,32 (tuning knob)            */
@@ -217,7 +258,8 @@ typedef struct sa_score_result {
     uint64_t end_text;     /* column j of the scored cell (global: text_len)            */
     uint64_t end_pattern;  /* row i of the scored cell (global: pattern_len); local: the
                               first maximum in row-major order, (0,0) when the score is 0;
-                              fit: (pattern_len, leftmost best column of that row)        */
+                              fit: (pattern_len, leftmost best column of that row);
+                              ends-free: the result cell (see sa_mode)                    */
 } sa_score_result;
 typedef struct sa_scorer sa_scorer;
 
@@ -305,7 +347,8 @@ int sa_search_affine(const sa_params *params, int32_t gap_open, int32_t gap_exte
  * every output equals that of the unbanded function (sa_score_batch_affine, sa_scorer_create_affine,
  * sa_align_pairs_affine).
  * One half-width serves all pairs of a call. Modes: SA_GLOBAL and SA_LOCAL; SA_FIT with a band is
- * SA_ERR_UNSUPPORTED (a fit band needs a diagonal of its own). band < 0 is SA_ERR_INVALID. The score
+ * SA_ERR_UNSUPPORTED (a fit band needs a diagonal of its own), and so is SA_ENDS_FREE with any flags.
+ * band < 0 is SA_ERR_INVALID. The score
  * limit is half that of the unbanded functions: (max|S| + G)(n + m) + G (n + m) must stay below 2^29,
  * G = max(|gap_open|, |gap_extend|) (SA_ERR_UNSUPPORTED). The search functions take no
  * band: texts of unrelated lengths share no diagonal.

@@ -27,10 +27,13 @@ int deviceFromEnv()
     return e ? std::atoi(e) : 0;
 }
 
-// `fit`: the caller is one of the functions that take SEMI_GLOBAL (the score-only and affine ones)
-bool toParams(const SequenceAlignment::Request &request, sa_params *p, bool fit = false)
+// `fit`: the caller is one of the functions that take SEMI_GLOBAL (the score-only and affine ones);
+// `ends`: the caller is one of the ends-free functions, the mode is SA_ENDS_FREE with these flags and
+// Request::alignmentType is ignored
+bool toParams(const SequenceAlignment::Request &request, sa_params *p, bool fit = false, const int *ends = nullptr)
 {
-    if (request.alignmentType == SequenceAlignment::programArgs::GLOBAL) p->mode = SA_GLOBAL;
+    if (ends) p->mode = SA_ENDS_FREE | *ends;
+    else if (request.alignmentType == SequenceAlignment::programArgs::GLOBAL) p->mode = SA_GLOBAL;
     else if (request.alignmentType == SequenceAlignment::programArgs::LOCAL) p->mode = SA_LOCAL;
     else if (fit && request.alignmentType == SequenceAlignment::programArgs::SEMI_GLOBAL) p->mode = SA_FIT;
     else return false;
@@ -40,6 +43,14 @@ bool toParams(const SequenceAlignment::Request &request, sa_params *p, bool fit 
     p->score_matrix = request.scoreMatrix;
     p->alphabet = request.alphabet;
     return true;
+}
+
+// the flags of an ends-free function: SA_FREE_TEXT_BEGIN | ... | SA_FREE_PATTERN_END, nothing else
+bool endsFlagsOk(int freeEnds, const char *name)
+{
+    if (freeEnds >= 0 && freeEnds <= 15) return true;
+    std::cout << "error: " << name << " takes freeEnds 0..15 (SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END | SA_FREE_PATTERN_BEGIN | SA_FREE_PATTERN_END)\n";
+    return false;
 }
 
 uint64_t runGPU(const SequenceAlignment::Request &request, SequenceAlignment::Response *response, bool fillOnly)
@@ -189,16 +200,16 @@ namespace
 {
 // scoreSequencesGPU, scoreSequencesGPUAffine and scoreSequencesGPUBanded: `gap` null is the requests'
 // linear gapPenalty, else {gap open, gap extend} and gapPenalty is ignored; `band` non-null is the
-// band's half-width
+// band's half-width; `ends` non-null is scoreSequencesGPUEndsFree with these flags
 uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
-                       int *scores, const char *name, const int *band = nullptr)
+                       int *scores, const char *name, const int *band = nullptr, const int *ends = nullptr)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
     std::vector<sa_host_pair> pairs(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
-        if (!toParams(requests[i], &params[i], true))
+        if (!toParams(requests[i], &params[i], true, ends))
         {
             std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
             return 1;
@@ -225,9 +236,10 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
     return 0;
 }
 
-// alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded
+// alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded; with `ends`, alignSequencesGPUEndsFree
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
-                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name);
+                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name,
+                       const int *ends = nullptr);
 }  // namespace
 
 uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
@@ -261,10 +273,25 @@ uint64_t SequenceAlignment::alignSequencesGPUBanded(const Request *requests, Res
     return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, &band, "alignSequencesGPUBanded");
 }
 
+uint64_t SequenceAlignment::scoreSequencesGPUEndsFree(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                      int gapExtend, int freeEnds, int *scores)
+{
+    if (!endsFlagsOk(freeEnds, "scoreSequencesGPUEndsFree")) return 1;
+    const int gap[2] = {gapOpen, gapExtend};
+    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUEndsFree", nullptr, &freeEnds);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUEndsFree(const Request *requests, Response *responses, uint64_t numRequests,
+                                                      int device, int gapOpen, int gapExtend, int freeEnds)
+{
+    if (!endsFlagsOk(freeEnds, "alignSequencesGPUEndsFree")) return 1;
+    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUEndsFree", &freeEnds);
+}
+
 namespace
 {
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
-                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name)
+                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name, const int *ends)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -272,7 +299,7 @@ uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlign
     std::vector<char *> at(numRequests), ap(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
-        if (!toParams(requests[i], &params[i], true))
+        if (!toParams(requests[i], &params[i], true, ends))
         {
             std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
             return 1;

@@ -45,6 +45,20 @@ __global__ __launch_bounds__(64) void align_band_kernel(AlignBandArgs ba)
     score_wave<true, kTraceRows, MODE, SMALL, true, true>(ba.a.sa.s, ba.a.sa.gap_extend, tab, ba.a.tr, ba.band);
 }
 
+// align_affine_kernel with free ends (sa_hip.h SA_ENDS_FREE; sa_score_wave.h: ENDS): the nibbles are
+// unchanged, only the borders and the result cell differ
+struct AlignEndsArgs {
+    AlignAffineArgs a;
+    int32_t ends;
+};
+
+template <int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void align_ends_kernel(AlignEndsArgs ea)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, kTraceRows, MODE, SMALL, true, false, true>(ea.a.sa.s, ea.a.sa.gap_extend, tab, ea.a.tr, 0, ea.ends);
+}
+
 struct WalkArgs {
     const int8_t *text, *pattern;
     const ScorePair *pairs;
@@ -56,7 +70,7 @@ struct WalkArgs {
     char *out_text, *out_pattern;     // both null: results only, no letters are loaded or written
     const char *alphabet;             // A letters and the gap letter
     sa_result *results;
-    int32_t A, mode;                  // mode: one of sa_mode
+    int32_t A, mode;                  // mode: one of sa_mode, or SA_ENDS_FREE with its flags
     int32_t band;                     // the half-width of a banded fill, or -1
 };
 
@@ -74,6 +88,10 @@ struct WalkArgs {
 // SA_FIT starts at (m, end_text) as a local walk starts at its best cell, moves as a global one
 // (column 0 forces TOP) and ends at row 0, where nothing forces LEFT: start_text is the column it
 // arrives in, the 0-based index of the window's first text letter, and start_pattern is 0.
+// SA_ENDS_FREE starts at the fill's result cell and ends at (i, j) when i == 0 && (TB || j == 0) or
+// j == 0 && (PB || i == 0); until then column 0 forces TOP and row 0 forces LEFT. start_text and
+// start_pattern are j and i of that cell. Global (no free begin) and fit (TB) end by the same rule. A
+// walk from (i, j) makes at most i + j moves, so the bound of n + m holds from any start cell.
 // After a banded fill (band >= 0) the words of strip s are those of its window's steps, 64 b0(s) ..
 // 64 b1(s) - 1, and the strips follow one another (trace_band_strip_words): the walk keeps the strip it
 // is in, that strip's first word and first step, counts up to the start cell's strip once and steps
@@ -97,7 +115,8 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     char *const op_end = a.out_pattern + slot + (uint64_t)n + (uint64_t)m;
     const uint32_t *const dirs = a.dirs + uniform64(a.dir_off[pi]);
     const uint32_t strip_words = (uint32_t)((n + 126) / 64) * (64u * 64u);
-    const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT;
+    const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT, ends = !BANDED && (a.mode & SA_ENDS_FREE) != 0;
+    const bool tbegin = fit || (ends && (a.mode & SA_FREE_TEXT_BEGIN)), pbegin = ends && (a.mode & SA_FREE_PATTERN_BEGIN);
     const int A = a.A;
     constexpr bool banded = BANDED;
     const Band bd = band_of(n, m, banded ? a.band : 0);
@@ -105,8 +124,8 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     int bsteps = INT32_MAX;       // and the number of its steps: no word is read outside the window
     uint64_t bbase = 0;           // its first word
 
-    int i = local ? min(uniform((int)sr.end_pattern), m) : m;
-    int j = local || fit ? min(uniform((int)sr.end_text), n) : n;
+    int i = local || ends ? min(uniform((int)sr.end_pattern), m) : m;
+    int j = local || fit || ends ? min(uniform((int)sr.end_text), n) : n;
     int ti = j - 1, pj = i - 1;  // the reference's text and pattern indices
     int state = kDirDiag;        // H; kDirLeft: inside a run of E, kDirTop: of F
     int len = 0;
@@ -131,7 +150,10 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     const int max_moves = n + m;
     for (int it = 0;; ++it)
     {
-        if (local ? (i == 0 || j == 0) : fit ? i == 0 : (i == 0 && j == 0))
+        bool stop;
+        if constexpr (BANDED) stop = local ? (i == 0 || j == 0) : fit ? i == 0 : (i == 0 && j == 0);  // the planner admits no free ends
+        else stop = local ? (i == 0 || j == 0) : (i == 0 && (tbegin || j == 0)) || (j == 0 && (pbegin || i == 0));
+        if (stop)
         {
             ended = true;
             break;
@@ -195,10 +217,10 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
         pj = pj - tp > 0 ? pj - tp : 0;
     }
     flush(len & ~63, len & 63);
-    if (fit)  // no quirks: the column the walk reached row 0 in
+    if (fit || ends)  // no quirks: the cell the walk ended in (fit: in row 0)
     {
         ti = j;
-        pj = 0;
+        pj = ends ? i : 0;
     }
     if (lane == 0)
     {
@@ -266,6 +288,20 @@ void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipS
     {
         if (small) hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, a);
         else hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, a);
+    }
+    else if (mode & SA_ENDS_FREE)  // the fit program when the text's end is free, else the global one
+    {
+        const AlignEndsArgs ea = {a, mode & 15};
+        if (mode & SA_FREE_TEXT_END)
+        {
+            if (small) hipLaunchKernelGGL((align_ends_kernel<SA_FIT, true>), dim3(grid), dim3(64), 0, st, ea);
+            else hipLaunchKernelGGL((align_ends_kernel<SA_FIT, false>), dim3(grid), dim3(64), 0, st, ea);
+        }
+        else
+        {
+            if (small) hipLaunchKernelGGL((align_ends_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, ea);
+            else hipLaunchKernelGGL((align_ends_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, ea);
+        }
     }
     else if (mode == SA_FIT)
     {

@@ -316,6 +316,7 @@ int sa_align_batch(const sa_params *P, const sa_host_pair *pairs, int64_t num_pa
     if (!P || num_pairs < 0 || num_gpus < 1 || (num_pairs > 0 && (!pairs || !results)))
         return fail(SA_ERR_INVALID, "sa_align_batch: bad argument");
     if (P->mode == SA_FIT) return fail(SA_ERR_UNSUPPORTED, sa::kFitUnsupported);
+    if (P->mode >= SA_ENDS_FREE && P->mode <= SA_OVERLAP) return fail(SA_ERR_UNSUPPORTED, sa::kEndsUnsupported);
     for (int64_t i = 0; i < num_pairs; ++i)
     {
         const sa_host_pair &h = pairs[i];

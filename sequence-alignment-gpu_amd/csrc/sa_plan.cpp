@@ -509,6 +509,7 @@ int make_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, 
     const int A = P->alphabet_size;
     if (A < 1 || A > 32) return fail(SA_ERR_INVALID, "alphabet_size must be 1..32");
     if (P->mode == SA_FIT) return fail(SA_ERR_UNSUPPORTED, kFitUnsupported);
+    if (P->mode >= SA_ENDS_FREE && P->mode <= SA_OVERLAP) return fail(SA_ERR_UNSUPPORTED, kEndsUnsupported);
     if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL) return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL or SA_LOCAL");
     Limits lim;
     if (int rc = check_limits(P, pairs, np, &lim, err)) return rc;

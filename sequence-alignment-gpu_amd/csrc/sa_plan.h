@@ -20,6 +20,11 @@ constexpr const char *kFitUnsupported =
     "SA_FIT is not implemented in the plans: use sa_score_batch, sa_scorer_create, sa_score_batch_affine, "
     "sa_scorer_create_affine, sa_align_pairs_affine, sa_search or sa_search_affine";
 
+// And to SA_ENDS_FREE with any flags: the same functions take it.
+constexpr const char *kEndsUnsupported =
+    "SA_ENDS_FREE is not implemented in the plans: use sa_score_batch, sa_scorer_create, sa_score_batch_affine, "
+    "sa_scorer_create_affine, sa_align_pairs_affine, sa_search or sa_search_affine";
+
 // Environment knobs, read once per process (the first time the engine needs one) and never again:
 // every field is a tuning or debugging switch; the defaults are the measured best settings.
 struct Knobs {

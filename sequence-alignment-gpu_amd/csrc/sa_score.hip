@@ -49,6 +49,27 @@ __global__ __launch_bounds__(64) void score_band_kernel(ScoreBandArgs ba)
     score_wave<true, R, MODE, SMALL, false, true>(ba.sa.s, ba.sa.gap_extend, tab, TraceArgs(), ba.band);
 }
 
+// score_kernel and score_affine_kernel with free ends (sa_hip.h SA_ENDS_FREE; sa_score_wave.h: ENDS):
+// MODE is the program, SA_FIT when the text's end is free and SA_GLOBAL otherwise, `ends` the flags
+struct ScoreEndsArgs {
+    ScoreAffineArgs sa;
+    int32_t ends;
+};
+
+template <int R, int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void score_ends_kernel(ScoreEndsArgs ea)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<false, R, MODE, SMALL, false, false, true>(ea.sa.s, 0, tab, TraceArgs(), 0, ea.ends);
+}
+
+template <int R, int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void score_affine_ends_kernel(ScoreEndsArgs ea)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, R, MODE, SMALL, false, false, true>(ea.sa.s, ea.sa.gap_extend, tab, TraceArgs(), 0, ea.ends);
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -61,18 +82,28 @@ namespace {
 // score_kernel or, with AFFINE, score_affine_kernel on `grid` one-wave workgroups: the one place that
 // picks <R, MODE, SMALL>. R is 1, 2, 4 or 8; mode is one of sa_mode (the planner has checked it);
 // a.gap is the linear penalty or the gap-open penalty. BAND (affine, global or local; band >= 0) is
-// score_band_kernel.
+// score_band_kernel. A mode with SA_ENDS_FREE is score_ends_kernel or score_affine_ends_kernel, the fit
+// program when the text's end is free and the global one otherwise.
 template <bool AFFINE, bool BAND = false>
 void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st, int band = 0)
 {
     const ScoreAffineArgs aa = {a, gap_extend};
     const ScoreBandArgs ba = {aa, band};
+    const bool ends = (mode & SA_ENDS_FREE) != 0;
+    const ScoreEndsArgs ea = {aa, mode & 15};
+    const int shape = !ends ? mode : mode & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL;
     auto launch = [&](auto rc, auto modec, auto smallc) {
         constexpr int RR = decltype(rc)::value, MODE = decltype(modec)::value;
         constexpr bool SMALL = decltype(smallc)::value;
         if constexpr (BAND)
         {
             if constexpr (MODE != SA_FIT) hipLaunchKernelGGL((score_band_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ba);
+        }
+        else if (ends)
+        {
+            if constexpr (MODE == SA_LOCAL) return;
+            else if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_ends_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ea);
+            else hipLaunchKernelGGL((score_ends_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ea);
         }
         else if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, aa);
         else hipLaunchKernelGGL((score_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, a);
@@ -83,8 +114,8 @@ void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool smal
         const std::integral_constant<int, SA_GLOBAL> global;
         const std::integral_constant<int, SA_LOCAL> local;
         const std::integral_constant<int, SA_FIT> fit;
-        if (mode == SA_LOCAL) small ? launch(rc, local, yes) : launch(rc, local, no);
-        else if (mode == SA_FIT) small ? launch(rc, fit, yes) : launch(rc, fit, no);
+        if (shape == SA_LOCAL) small ? launch(rc, local, yes) : launch(rc, local, no);
+        else if (shape == SA_FIT) small ? launch(rc, fit, yes) : launch(rc, fit, no);
         else small ? launch(rc, global, yes) : launch(rc, global, no);
     };
     switch (R)
@@ -375,10 +406,10 @@ static int search(const sa_params *P, const ScoreGap *gapm, const char *query, u
     // the hits: the texts and the query are already on the device
     std::vector<sa_pair> hp((size_t)nh);
     for (int64_t h = 0; h < nh; ++h) hp[h] = dp[rank[h]];
-    // the plans have no fit mode: a linear fit search aligns through the traced path with
-    // gap_open = gap_extend = gap_penalty, which is the linear recurrence
+    // the plans have no fit and no ends-free modes: a linear search in one of them aligns through the
+    // traced path with gap_open = gap_extend = gap_penalty, which is the linear recurrence
     const ScoreGap lin = {P->gap_penalty, P->gap_penalty};
-    const ScoreGap *const hg = gapm ? gapm : P->mode == SA_FIT ? &lin : nullptr;
+    const ScoreGap *const hg = gapm ? gapm : P->mode == SA_FIT || (P->mode & SA_ENDS_FREE) ? &lin : nullptr;
     rc = hg ? align_affine_device(P, hg->open, hg->extend, hp.data(), nh, device, dt.p, dq.p, hit_results, aligned_text,
                                   aligned_pattern)
             : align_hits_linear(P, hp, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern);

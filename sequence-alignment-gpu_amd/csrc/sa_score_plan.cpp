@@ -45,14 +45,16 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
     const int A = P->alphabet_size;
     if (A < 1 || A > 32) return fail(SA_ERR_INVALID, "alphabet_size must be 1..32");
-    if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL && P->mode != SA_FIT)
-        return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL, SA_LOCAL or SA_FIT");
+    const bool ends = P->mode >= SA_ENDS_FREE && P->mode <= SA_OVERLAP;
+    if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL && P->mode != SA_FIT && !ends)
+        return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL, SA_LOCAL, SA_FIT or SA_ENDS_FREE with its flags");
     if (np > INT32_MAX) return fail(SA_ERR_UNSUPPORTED, "more than 2^31-1 pairs");
     if (band)
     {
         if (!affine) return fail(SA_ERR_INVALID, "a band takes gap_open and gap_extend");
         if (*band < 0) return fail(SA_ERR_INVALID, "band must be >= 0");
         if (P->mode == SA_FIT) return fail(SA_ERR_UNSUPPORTED, "SA_FIT takes no band");
+        if (ends) return fail(SA_ERR_UNSUPPORTED, "SA_ENDS_FREE takes no band");
     }
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
@@ -123,9 +125,10 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     // strip takes the steps of its window, jmax - jmin + 64 (n + 63 when the band admits every cell): a
     // tall strip under a narrow band mostly steps through out-of-band cells, so R falls with the band. A fit
     // step is a global step plus the best of row m: kScoreFitStepBest + (R - 1) * kScoreFitStepSelect,
-    // the same in both kernels ----
+    // the same in both kernels. An ends-free mode runs the fit program when the text's end is free and
+    // the global one otherwise: the other free ends cost nothing per step ----
     static const int kR[4] = {1, 2, 4, 8};
-    const bool fit = P->mode == SA_FIT;
+    const bool fit = P->mode == SA_FIT || (ends && (P->mode & SA_FREE_TEXT_END));
     const int step_base = (affine ? kScoreAffineStepBase : kScoreStepBase) + (fit ? kScoreFitStepBest - kScoreFitStepSelect : 0);
     const int step_row = (P->mode == SA_LOCAL ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
                                               : (affine ? kScoreAffineStepRowGlobal : kScoreStepRowGlobal)) +

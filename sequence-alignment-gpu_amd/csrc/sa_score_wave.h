@@ -75,6 +75,23 @@
 //    it never wins a maximum, never ties, and no direction nibble that is read points out of band.
 //  - TRACE stores a word only for the steps the strip runs: the pair's directions are the strips'
 //    windows one after another, 64 (b1 - b0) steps of 64 words each (trace_band_dir_bytes).
+//
+// ENDS (MODE SA_GLOBAL or SA_FIT; score_ends_kernel, score_affine_ends_kernel, align_ends_kernel) is
+// ends-free alignment, sa_hip.h SA_ENDS_FREE: `ends` holds the flags, TB, TE, PB and PE for short.
+// TE decides the program: unset it is the global program, set it is the fit program (the running best
+// of row m), and the host launches MODE accordingly. The other three flags are wave-uniform values and
+// cost nothing per step; everything of ENDS is under `if constexpr (ENDS)`, so the other instances
+// compile to what they were.
+//  - TB, PB: the border values. H[0][j] (the top row fed to strip 0) is 0 under TB and H[i][0] (hl, el
+//    and upprev at the start of a strip) is 0 under PB; the stand-ins for E and F follow from them.
+//  - PE: after a strip hl[r] is H[row][n], so every lane folds its rows <= m into one running best of
+//    the last column (strictly greater keeps the earlier row, within the lane and across strips), and
+//    after the last strip one wave maximum of the key (value + 2^30, ~row) gives the lowest row of the
+//    maximum: the planner keeps |H| below 2^30.
+//  - The result: lane 0 compares the best of row m (TE unset: H[m][n]), the best of the last column
+//    and the closed-form border candidates H[0][n] and H[m][0] in the tie order of sa_hip.h.
+//  - An empty side: every candidate is a border cell; the early-out compares the border values at
+//    0, 1 and the side's length, as a gap's cost need not grow with its length.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -127,13 +144,14 @@ struct MaskedStep : std::true_type {
 
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
 // registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
-template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false>
+template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false>
 __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs(),
-                                           int band = 0)
+                                           int band = 0, int ends = 0)
 {
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
     static_assert(!BAND || (AFFINE && MODE != SA_FIT), "banded instances: affine, global or local");
+    static_assert(!ENDS || (MODE != SA_LOCAL && !BAND), "ends-free instances: the global or the fit program, no band");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
     constexpr int SENT = kBandSentinel;
     using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
@@ -148,6 +166,10 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
     const int kb = a.key_rowbits;
     const uint32_t kmask = (1u << kb) - 1u;
     bool bad = false;
+    // ENDS: the free ends but TE, which is FIT; gapc(k), the cost of a border gap of k >= 1 cells
+    const bool etb = ENDS && (ends & SA_FREE_TEXT_BEGIN), epb = ENDS && (ends & SA_FREE_PATTERN_BEGIN),
+               epe = ENDS && (ends & SA_FREE_PATTERN_END);
+    auto gapc = [&](int k) { return AFFINE ? g + (k - 1) * ge : g * k; };
     for (;;)
     {
         int w = 0;
@@ -157,7 +179,36 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         const int pi = uniform(a.order[w]);
         const ScorePair pd = a.pairs[pi];
         const int n = uniform((int)pd.n), m = uniform((int)pd.m);
-        if (n == 0 || m == 0)
+        if constexpr (ENDS)
+        {
+            if (n == 0 || m == 0)
+            {
+                // the candidates are cells of the other side's border, 0 .. k: cell k, or under the
+                // side's free end the first maximum, which lies at 0, 1 or k
+                if (lane == 0)
+                {
+                    const bool rows = n == 0;  // the border is column 0 (both sides empty: its cell 0)
+                    const int k = rows ? m : n;
+                    const bool zero = rows ? epb : etb, anywhere = rows ? epe : FIT;
+                    auto bval = [&](int c) { return c == 0 || zero ? 0 : -gapc(c); };
+                    int bc = k, bv = bval(k);
+                    if (anywhere)
+                    {
+                        bc = 0, bv = 0;
+                        if (k >= 1 && bval(1) > bv) bc = 1, bv = bval(1);
+                        if (k >= 2 && bval(k) > bv) bc = k, bv = bval(k);
+                    }
+                    sa_score_result r;
+                    r.score = bv;
+                    r.status = SA_OK;
+                    r.end_text = rows ? 0 : (uint64_t)bc;
+                    r.end_pattern = rows ? (uint64_t)bc : 0;
+                    a.out[pi] = r;
+                }
+                continue;
+            }
+        }
+        else if (n == 0 || m == 0)
         {
             // H[m][n] of an empty side is one run of max(n, m) gaps (alignSequenceCPU.cpp:232-236, :247-248)
             if (lane == 0)
@@ -184,6 +235,9 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         const int flast = m - 1 - (nstrips - 1) * 64 * R;
         const int frm = flast % R, flm = flast / R;
         int fbest = INT32_MIN, fbestt = 0;
+        // ENDS: the lane's first maximum of H[row][n] over its rows <= m of the strips so far, started
+        // below any score, and its row
+        int pebest = -(1 << 30), perow = 0;
         uint32_t *dlane = nullptr;  // TRACE: the lane's word of step 0 of the pair's first strip
         if constexpr (TRACE) dlane = tr.dirs + uniform64(tr.dir_off[pi]) + lane;
         // BAND: cell (i, j) is in band iff (unsigned)(j - i - blo) <= bspan
@@ -231,6 +285,11 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     el[r] = hl[r] - g + ge;  // stands for E[row][0] = -infinity
                 }
                 else hl[r] = LOCAL ? 0 : -(row1 + r + 1) * g;
+                if constexpr (ENDS)
+                {
+                    hl[r] = epb ? 0 : hl[r];
+                    if constexpr (AFFINE) el[r] = hl[r] - g + ge;
+                }
                 if constexpr (BAND)
                 {
                     // a window past body 0 starts left of the band in every row; in body 0 the border
@@ -250,6 +309,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             int upprev;  // H[row1][column - 1]
             if constexpr (AFFINE) upprev = LOCAL || row1 == 0 ? 0 : -(g + (row1 - 1) * ge);
             else upprev = LOCAL ? 0 : -row1 * g;
+            if constexpr (ENDS) upprev = epb ? 0 : upprev;
             if constexpr (BAND)
             {
                 if (bfirst == 0) upprev = row1 <= -blo ? upprev : SENT;
@@ -389,7 +449,8 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 {
                     if (s == 0)
                     {
-                        feed = LOCAL || FIT ? 0 : -(g + c0 * ge);  // H[0][c0 + 1]
+                        if constexpr (ENDS) feed = etb ? 0 : -(g + c0 * ge);
+                        else feed = LOCAL || FIT ? 0 : -(g + c0 * ge);  // H[0][c0 + 1]
                         feedf = feed - g + ge;              // stands for F[0][c0 + 1] = -infinity
                     }
                     else
@@ -409,7 +470,11 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 }
                 else
                 {
-                    if (s == 0) feed = LOCAL || FIT ? 0 : -(c0 + 1) * g;
+                    if (s == 0)
+                    {
+                        if constexpr (ENDS) feed = etb ? 0 : -(c0 + 1) * g;
+                        else feed = LOCAL || FIT ? 0 : -(c0 + 1) * g;
+                    }
                     else feed = c0 < n ? rowbuf[c0] : 0;
                 }
                 // BAND: the body's diagonals j - i run from lane 63's last row at its first step to lane
@@ -455,6 +520,17 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 }
             }
             if constexpr (TRACE && BAND) dlane += (uint64_t)(bend - bfirst) * (64 * 64);
+            if constexpr (ENDS)
+            {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                {
+                    const int row = row1 + r + 1;
+                    const bool better = row <= m && hl[r] > pebest;
+                    pebest = better ? hl[r] : pebest;
+                    perow = better ? row : perow;
+                }
+            }
             if (LOCAL)
             {
 #pragma unroll
@@ -494,6 +570,42 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             res.score = __builtin_amdgcn_readlane(v, last / R);
             res.end_text = (uint64_t)n;
             res.end_pattern = (uint64_t)m;
+        }
+        if constexpr (ENDS)
+        {
+            // res is the candidate of row m; the lowest row of the last column's maximum beats it when
+            // it is no smaller and lies above row m (it is then at least H[m][n]); a border candidate,
+            // (0, n) before (m, 0), wins only when it is strictly greater
+            int bv = res.score;
+            if (epe)
+            {
+                const uint64_t key = wave_max_u64(((uint64_t)(uint32_t)(pebest + (1 << 30)) << 32) | (uint64_t)~(uint32_t)perow);
+                const int vc = (int)(uint32_t)(key >> 32) - (1 << 30), rc = (int)~(uint32_t)key;
+                if (vc >= bv && rc < m)
+                {
+                    bv = vc;
+                    res.end_pattern = (uint64_t)rc;
+                    res.end_text = (uint64_t)n;
+                }
+                const int h0n = etb ? 0 : -gapc(n);
+                if (h0n > bv)
+                {
+                    bv = h0n;
+                    res.end_pattern = 0;
+                    res.end_text = (uint64_t)n;
+                }
+            }
+            if constexpr (FIT)
+            {
+                const int hm0 = epb ? 0 : -gapc(m);
+                if (hm0 > bv)
+                {
+                    bv = hm0;
+                    res.end_pattern = (uint64_t)m;
+                    res.end_text = 0;
+                }
+            }
+            res.score = bv;
         }
         if (lane == 0) a.out[pi] = res;
     }

@@ -18,6 +18,11 @@ SA_GLOBAL, SA_LOCAL = 0, 1
 # score_batch, Scorer, align_pairs_affine and search; Plan, align_pair and align_batch answer
 # SA_ERR_UNSUPPORTED.
 FIT = SA_FIT = 2
+# sa_mode SA_ENDS_FREE: global alignment with free sequence ends, mode = ENDS_FREE | flags (16..31).
+# Taken and refused by the same functions as FIT; the banded functions (band=) refuse it too.
+ENDS_FREE = 16
+FREE_TEXT_BEGIN, FREE_TEXT_END, FREE_PATTERN_BEGIN, FREE_PATTERN_END = 1, 2, 4, 8
+OVERLAP = ENDS_FREE | 15
 STATUS = {0: "SA_OK", 1: "SA_ERR_INVALID", 2: "SA_ERR_NOMEM", 3: "SA_ERR_HIP", 4: "SA_ERR_UNSUPPORTED",
           5: "SA_ERR_TIMEOUT"}
 
@@ -165,6 +170,14 @@ def _params(mode: int, S: np.ndarray, gap: int, alphabet: bytes | None, rows_per
     return p, S, alphabet
 
 
+def ends_free(text_begin: bool = False, text_end: bool = False, pattern_begin: bool = False,
+              pattern_end: bool = False) -> int:
+    """The ends-free mode (sa_hip.h SA_ENDS_FREE) in which the named sequence ends cost nothing: all
+    four is OVERLAP, the text's two is FIT, none is global alignment."""
+    return (ENDS_FREE | (FREE_TEXT_BEGIN if text_begin else 0) | (FREE_TEXT_END if text_end else 0) |
+            (FREE_PATTERN_BEGIN if pattern_begin else 0) | (FREE_PATTERN_END if pattern_end else 0))
+
+
 def selftest(device: int = 0) -> None:
     _check(lib.sa_selftest(device))
 
@@ -228,7 +241,9 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
                        gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
-    ones. With gap_open == gap_extend == g every value is align_pair's for gap g. With `band`,
+    ones. With gap_open == gap_extend == g every value is align_pair's for gap g. `mode` may also be FIT
+    or an ends-free mode (ends_free(), OVERLAP): start_text and start_pattern are then the 0-based
+    indices of the first aligned letters. With `band` (SA_GLOBAL and SA_LOCAL only),
     sa_align_pairs_banded: the alignment inside the diagonal band of that half-width (sa_hip.h)."""
     return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band)
 
@@ -365,7 +380,9 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
     the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
     sa_score_batch_banded: the scores inside the diagonal band of that half-width (sa_hip.h); without
-    `gap_extend` the gap is linear, gap_open = gap_extend = gap."""
+    `gap_extend` the gap is linear, gap_open = gap_extend = gap. `mode` is SA_GLOBAL, SA_LOCAL, FIT or
+    an ends-free mode (ends_free(), OVERLAP; not with `band`): end_pattern and end_text are the cell the
+    score is read from."""
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
@@ -385,7 +402,8 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 class Scorer:
     """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback).
     With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty. With
-    `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear)."""
+    `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear). `mode` as
+    score_batch takes it."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
                  device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None):
@@ -434,7 +452,9 @@ def search(mode: int, query: np.ndarray, texts: list[np.ndarray], S: np.ndarray,
     to the lower index), each {"index", "score", "num_bytes", "start_text", "start_pattern"} and, with
     strings, "aligned_text" / "aligned_pattern", as align_pair gives them for that pair. With
     `gap_extend`, sa_search_affine: `gap` is the gap-open penalty, and the hits are aligned under the
-    gap model they were ranked by, as align_pairs_affine gives them."""
+    gap model they were ranked by, as align_pairs_affine gives them. In mode FIT or an ends-free mode
+    (ends_free(), OVERLAP) the hits of a linear search are aligned as align_pairs_affine aligns them with
+    gap_open = gap_extend = gap."""
     p, S_keep, alpha_keep = _params(mode, S, gap, None, 0)
     q = np.ascontiguousarray(query, dtype=np.int8)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]

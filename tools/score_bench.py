@@ -32,7 +32,22 @@ step-cost model, and whether the fit median is within the local median plus the 
 min-max spread. Then search(k = --hits, default 100) in fit and in local mode on the search workload
 under 11 / 2, with the device times of the traced fill and of the walk.
 
+With --mode ends the ends-free scorers (sa_hip.h: SA_ENDS_FREE): the read-mapping workload of --mode
+fit, and an overlap workload, 40000 pairs of DNA reads of 140 to 160 letters in which the last 30 to 120
+letters of each text are a mutated copy of the first letters of its pattern. On each workload, once under
+the linear gap 5 and once under gap open 11 / gap extend 2, the scorers of SA_OVERLAP, SA_ENDS_FREE | TB |
+PE, SA_ENDS_FREE | TB | TE, SA_ENDS_FREE alone, SA_FIT and SA_GLOBAL run alternated round by round in one
+process after a warm-up (device events; median, min and max). The results of SA_ENDS_FREE | TB | TE and
+SA_FIT, and of SA_ENDS_FREE alone and SA_GLOBAL, are asserted equal on every workload and gap. Each
+ends-free mode is compared with the existing mode whose program it runs, SA_FIT when the text's end is
+free and SA_GLOBAL otherwise: the report holds the ratio of the medians and whether the median lies
+within the baseline's median plus the baseline's own min-max spread of the same run. With --tree DIR (a
+built checkout without the modes, e.g. the parent commit) only SA_FIT and SA_GLOBAL run, on the same data:
+the figures the existing modes are compared with across the two libraries.
+
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+    python3 tools/score_bench.py --mode ends [--small] --out profiles/r15/score_ends_bench.json
+    python3 tools/score_bench.py --mode ends --tree ../parent --out profiles/r15/score_ends_bench_parent.json
 With --band W [W ...] the banded scorer and aligner (sa_hip.h: sa_scorer_create_banded,
 sa_align_pairs_banded): related pairs of about 20000 DNA letters, each pattern its text with 5 %
 substitutions and 0.1 % deletions, under gap open / gap extend. Scorer.run of the unbanded affine scorer
@@ -124,6 +139,67 @@ def mapping_workload(small: bool) -> dict:
 
 
 MODES = {"global": 0, "local": 1, "fit": 2}
+
+
+def overlap_workload(small: bool) -> dict:
+    """Pairs of DNA reads of 140..160 letters: the last 30..120 letters of each text are a mutated copy of
+    the first letters of its pattern (two reads that overlap end to start)."""
+    from sa_amd import synthetic
+    npairs = 4000 if small else 40000
+    rng = np.random.default_rng(17)
+    nl, ml, ov = rng.integers(140, 161, npairs), rng.integers(140, 161, npairs), rng.integers(30, 121, npairs)
+    to, po, oo = (np.concatenate([[0], np.cumsum(x)]) for x in (nl, ml, ov))
+    pattern = synthetic.random_sequence(7, int(po[-1]), 4)
+    text = synthetic.random_sequence(8, int(to[-1]), 4).copy()
+    heads = synthetic.mutate(np.concatenate([pattern[po[k]:po[k] + ov[k]] for k in range(npairs)]), 9, 4, int(oo[-1]))
+    for k in range(npairs):
+        text[to[k + 1] - ov[k]:to[k + 1]] = heads[oo[k]:oo[k + 1]]
+    return {"name": "overlap", "S": synthetic.blast_matrix(), "text": text, "pattern": pattern,
+            "pairs": [(int(to[k]), int(nl[k]), int(po[k]), int(ml[k])) for k in range(npairs)]}
+
+
+# --mode ends: the scorers of a run, and for each ends-free one the existing mode whose program it runs
+ENDS_MODES = {"overlap": 31, "ends_tb_pe": 16 | 1 | 8, "ends_tb_te": 16 | 1 | 2, "ends_none": 16, "fit": 2, "global": 0}
+ENDS_BASE = {"overlap": "fit", "ends_tb_te": "fit", "ends_tb_pe": "global", "ends_none": "global"}
+
+
+def ends_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
+    """The ends-free scorers of one gap model on one workload beside SA_FIT and SA_GLOBAL, alternated."""
+    cells = sum(p[1] * p[3] for p in w["pairs"])
+    affine = gap_extend is not None
+    have = hasattr(engine, "ENDS_FREE")  # a --tree checkout from before the modes runs the existing two
+    sc = {k: engine.Scorer(m, w["S"], gap, w["pairs"], gap_extend=gap_extend) for k, m in ENDS_MODES.items() if have or m < 16}
+    row = {"name": w["name"] + ("_affine" if affine else "_linear"), "pairs": len(w["pairs"]), "cells": cells, "gap": gap,
+           "gap_extend": gap_extend, "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for _ in range(2):  # warm-up
+        for k, s in sc.items():
+            s.run(dt.data_ptr(), dp.data_ptr())
+            res[k] = s.results()
+    if have:
+        assert res["ends_tb_te"].tolist() == res["fit"].tolist(), "SA_ENDS_FREE | TB | TE and SA_FIT differ"
+        assert res["ends_none"].tolist() == res["global"].tolist(), "SA_ENDS_FREE and SA_GLOBAL differ"
+        assert (res["global"]["score"] <= res["ends_tb_pe"]["score"]).all() and (res["ends_tb_pe"]["score"] <= res["overlap"]["score"]).all()
+        assert (res["fit"]["score"] <= res["overlap"]["score"]).all()
+        row["identities_hold"] = True
+        row["mean_score"] = {k: round(float(r["score"].mean()), 2) for k, r in res.items()}
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            ms[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    for k, s in sc.items():
+        row[k + "_run"] = stats(ms[k])
+        row[k + "_gcups"] = round(cells / statistics.median(ms[k]) / 1e6, 1)
+        s.close()
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    row["compared"] = {}
+    for k, base in ENDS_BASE.items():
+        if k in sc:
+            spread = max(ms[base]) - min(ms[base])
+            row["compared"][k] = {"baseline": base, "over_baseline": round(med[k] / med[base], 4),
+                                  "baseline_spread_ms": round(spread, 3),
+                                  "within_baseline_plus_spread": bool(med[k] <= med[base] + spread)}
+    return row
 
 
 def related_workload(small: bool) -> dict:
@@ -391,8 +467,9 @@ def main() -> int:
     ap.add_argument("--gap-open", type=int, default=11, help="gap-open penalty of the affine scorer")
     ap.add_argument("--hits", type=int, default=None,
                     help="time search(k=HITS) on the search workload; with --gap-extend also its traced fill and its walk")
-    ap.add_argument("--mode", choices=["fit"], default=None,
-                    help="fit: the fit scorers against the global and local ones on a read-mapping workload")
+    ap.add_argument("--mode", choices=["fit", "ends"], default=None,
+                    help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
+                         "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--tree", default=None,
@@ -400,7 +477,8 @@ def main() -> int:
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
-                                                    ("r13", "score_fit_bench.json") if args.mode == "fit" else ("r09", "score_bench.json")))
+                                                    ("r13", "score_fit_bench.json") if args.mode == "fit" else
+                                                    ("r15", "score_ends_bench.json") if args.mode == "ends" else ("r09", "score_bench.json")))
     if args.tree:
         sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
@@ -428,6 +506,15 @@ def main() -> int:
         row = fit_hits_row(args, engine, next(workloads(args.small, search_only=True)))
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
+    elif args.mode == "ends":
+        report["library_build_id"] = engine.lib.sa_build_id().decode()
+        for w in (mapping_workload(args.small), overlap_workload(args.small)):
+            dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+            for gap, ge in ((5, None), (args.gap_open, args.gap_extend if args.gap_extend is not None else 2)):
+                row = ends_rows(args, engine, w, dt, dp, gap, ge)
+                report["workloads"].append(row)
+                print(json.dumps(row), flush=True)
+            del dt, dp
     for w in ([] if args.mode or args.band else workloads(args.small, search_only=args.hits is not None)):
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
         if args.hits is not None:
