@@ -180,6 +180,22 @@ uint64_t scoreSequencesGPUEndsFree(const Request *requests, uint64_t numRequests
 uint64_t alignSequencesGPUEndsFree(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                    int gapOpen, int gapExtend, int freeEnds);
 
+/// Extension: scores and alignments inside a band of the caller's per request (sa_score_batch_band_at,
+/// sa_align_pairs_band_at; sa_hip.h has the definition): request k counts cell (i, j) iff
+/// bandLo[k] <= j - i <= bandHi[k], whatever its lengths. A read that a seed places at text letter c fits
+/// inside {c - w, c + w}. freeEnds chooses the mode as the ...EndsFree functions do, with one value more:
+/// 0..15 is SA_ENDS_FREE | freeEnds and Request::alignmentType is ignored (3 the fit, 15 the overlap);
+/// -1 leaves the mode to Request::alignmentType, GLOBAL, LOCAL or SEMI_GLOBAL (the fit), so local
+/// alignment is reached this way only. Request::gapPenalty is ignored: a caller with a linear gap passes
+/// its penalty as gapOpen and gapExtend. One alphabet and score matrix for all requests. A request whose
+/// band admits no alignment of the mode fails the whole call (sa_band_reachable tells beforehand), and
+/// so does bandLo[k] > bandHi[k]. Responses as alignSequencesGPUEndsFree fills them (-1: as
+/// alignSequencesGPUAffine does for the type). Returns 0, or 1 with the message on stdout.
+uint64_t scoreSequencesGPUBandAt(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                 int freeEnds, const int *bandLo, const int *bandHi, int *scores);
+uint64_t alignSequencesGPUBandAt(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                 int gapOpen, int gapExtend, int freeEnds, const int *bandLo, const int *bandHi);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

@@ -49,7 +49,8 @@ extern "C" {
  * SA_FIT is taken by sa_score_batch, sa_scorer_create, sa_score_batch_affine,
  * sa_scorer_create_affine, sa_align_pairs_affine, sa_search and sa_search_affine; sa_search aligns
  * its fit hits as sa_align_pairs_affine does with gap_open = gap_extend = gap_penalty (the linear
- * recurrence). sa_plan_create, sa_align_pair and sa_align_batch answer SA_ERR_UNSUPPORTED.
+ * recurrence); the band-at functions take it with a band per pair. sa_plan_create, sa_align_pair and
+ * sa_align_batch answer SA_ERR_UNSUPPORTED.
  *
  * SA_ENDS_FREE (ends-free alignment): global alignment in which each of the four sequence ends may
  * cost nothing. mode = SA_ENDS_FREE | any of the four flags below, 16..31; 3..15 and values from 32
@@ -80,9 +81,9 @@ extern "C" {
  * transposed) while swapping TB with PB and TE with PE gives the same score.
  * The modes are taken by sa_score_batch, sa_scorer_create, sa_score_batch_affine,
  * sa_scorer_create_affine, sa_align_pairs_affine, sa_search and sa_search_affine; sa_search aligns
- * its hits as sa_align_pairs_affine does with gap_open = gap_extend = gap_penalty. The banded
- * functions (a band with free ends needs a diagonal of its own), sa_plan_create, sa_align_pair and
- * sa_align_batch answer SA_ERR_UNSUPPORTED. */
+ * its hits as sa_align_pairs_affine does with gap_open = gap_extend = gap_penalty; the band-at functions
+ * take them with a band per pair. The banded functions on a half-width (a band with free ends needs a
+ * diagonal of its own), sa_plan_create, sa_align_pair and sa_align_batch answer SA_ERR_UNSUPPORTED. */
 enum sa_mode { SA_GLOBAL = 0, SA_LOCAL = 1, SA_FIT = 2, SA_ENDS_FREE = 16 };
 enum sa_free_end {
     SA_FREE_TEXT_BEGIN = 1,    /* TB: H[0][j] = 0                             */
@@ -347,7 +348,8 @@ int sa_search_affine(const sa_params *params, int32_t gap_open, int32_t gap_exte
  * every output equals that of the unbanded function (sa_score_batch_affine, sa_scorer_create_affine,
  * sa_align_pairs_affine).
  * One half-width serves all pairs of a call. Modes: SA_GLOBAL and SA_LOCAL; SA_FIT with a band is
- * SA_ERR_UNSUPPORTED (a fit band needs a diagonal of its own), and so is SA_ENDS_FREE with any flags.
+ * SA_ERR_UNSUPPORTED (a fit band needs a diagonal of its own), and so is SA_ENDS_FREE with any flags:
+ * the band-at functions below take both, with a band of the caller's per pair.
  * band < 0 is SA_ERR_INVALID. The score
  * limit is half that of the unbanded functions: (max|S| + G)(n + m) + G (n + m) must stay below 2^29,
  * G = max(|gap_open|, |gap_extend|) (SA_ERR_UNSUPPORTED). The search functions take no
@@ -365,8 +367,54 @@ int sa_align_pairs_banded(const sa_params *params, int32_t gap_open, int32_t gap
                           const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
                           char *const *aligned_text, char *const *aligned_pattern);
 
+/* ---- banded alignment on a diagonal of the caller's: one band per pair, every mode ----------- */
+
+/* bands[k] is the band of pair k: cell (i, j), 0 <= i <= m, 0 <= j <= n, border cells included, is in
+ * band iff lo <= j - i <= hi. The caller who knows where the pattern lies in the text (read mapping
+ * after a seed hit, read merging, seed extension) says so: a fit of a read that starts near text
+ * letter c takes {c - w, c + w}. Nothing is derived from the lengths.
+ * Modes: SA_GLOBAL, SA_LOCAL, SA_FIT and SA_ENDS_FREE | flags, all 16 sets. The recurrence is Gotoh's
+ * as sa_score_batch_affine states it (a linear caller passes its penalty twice), and H, E and F of
+ * every out-of-band cell are minus infinity, border cells included.
+ *   borders:      "free" is TB for row 0, PB for column 0, and either under SA_LOCAL. H[0][0] = 0 iff
+ *                 the origin is in band; a free border cell is 0 iff it is in band; a non-free border
+ *                 cell (0, j) or (i, 0) is -gap(j) or -gap(i) iff it and the origin are in band (a
+ *                 border gap run starts at a real origin); every other border cell is minus infinity
+ *   result:       the rules of the mode over real (not minus infinity), in-band cells. Global: (m, n).
+ *                 Local: the first maximum in row-major order over in-band cells, or 0 at (0, 0)
+ *                 without a positive one. Fit and ends-free: the candidates and the tie order of
+ *                 SA_ENDS_FREE above, over the in-band candidates only
+ *   walk:         as the mode has it, the stop rule of ends-free included; it never leaves the band
+ *   empty:        with n == 0 or m == 0 every candidate is a border cell and the rules above apply
+ *   reachability: a pair is reachable iff some candidate is real, which holds iff an in-band permitted
+ *                 start is componentwise <= an in-band permitted end. Starts: the origin; under TB the
+ *                 cells (0, j); under PB the cells (i, 0). Ends: (m, n); under TE row m; under PE column
+ *                 n. A local pair is always reachable. sa_band_reachable is the closed form (host only,
+ *                 no device call): 1 reachable, 0 not, -1 for a bad mode
+ * Refusals: the three device functions refuse the whole call with SA_ERR_INVALID when a pair is
+ * unreachable and name the first such pair's index in sa_last_error(): callers filter with
+ * sa_band_reachable first. lo > hi is SA_ERR_INVALID, and so is bands == NULL with num_pairs > 0. Any
+ * other int32 lo and hi are accepted; values beyond [-m, n] act as if clipped to it. The score limit is
+ * that of the banded functions above (SA_ERR_UNSUPPORTED).
+ * Identities: bands[k] = {min(0, d) - w, max(0, d) + w}, d = n - m, in global or local mode gives every
+ * output of the banded function above at half-width w; bands[k] = {-m, n} gives every output of the
+ * unbanded affine function in every mode; SA_ENDS_FREE | TB | TE equals SA_FIT.
+ * The scorer is an ordinary sa_scorer. sa_align_pairs_band_at keeps direction bits for the band's
+ * strips only, as sa_align_pairs_banded does, so a pair whose full directions exceed
+ * SA_TRACE_ARENA_BYTES aligns when its band fits. sa_affine_last_stats reports the call. The search
+ * functions take no band. */
+typedef struct sa_band { int32_t lo, hi; } sa_band;
+int sa_score_batch_band_at(const sa_params *params, int32_t gap_open, int32_t gap_extend, const sa_band *bands,
+                           const sa_host_pair *pairs, int64_t num_pairs, int device, sa_score_result *out);
+int sa_scorer_create_band_at(const sa_params *params, int32_t gap_open, int32_t gap_extend, const sa_band *bands,
+                             const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_align_pairs_band_at(const sa_params *params, int32_t gap_open, int32_t gap_extend, const sa_band *bands,
+                           const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                           char *const *aligned_text, char *const *aligned_pattern);
+int sa_band_reachable(int32_t mode, uint64_t text_len, uint64_t pattern_len, sa_band band);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
- * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded or sa_search_affine (k > 0): device
+ * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

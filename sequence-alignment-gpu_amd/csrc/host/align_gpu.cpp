@@ -200,9 +200,11 @@ namespace
 {
 // scoreSequencesGPU, scoreSequencesGPUAffine and scoreSequencesGPUBanded: `gap` null is the requests'
 // linear gapPenalty, else {gap open, gap extend} and gapPenalty is ignored; `band` non-null is the
-// band's half-width; `ends` non-null is scoreSequencesGPUEndsFree with these flags
+// band's half-width; `ends` non-null is scoreSequencesGPUEndsFree with these flags; `lo` and `hi` non-null
+// are scoreSequencesGPUBandAt's per-request bands
 uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
-                       int *scores, const char *name, const int *band = nullptr, const int *ends = nullptr)
+                       int *scores, const char *name, const int *band = nullptr, const int *ends = nullptr,
+                       const int *lo = nullptr, const int *hi = nullptr)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -224,7 +226,10 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
                                 requests[i].patternNumBytes};
     }
     std::vector<sa_score_result> res(numRequests);
-    const int rc = band ? sa_score_batch_banded(&params[0], gap[0], gap[1], *band, pairs.data(), (int64_t)numRequests, device, res.data())
+    std::vector<sa_band> bands;
+    for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
+    const int rc = lo   ? sa_score_batch_band_at(&params[0], gap[0], gap[1], bands.data(), pairs.data(), (int64_t)numRequests, device, res.data())
+                   : band ? sa_score_batch_banded(&params[0], gap[0], gap[1], *band, pairs.data(), (int64_t)numRequests, device, res.data())
                    : gap ? sa_score_batch_affine(&params[0], gap[0], gap[1], pairs.data(), (int64_t)numRequests, device, res.data())
                          : sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
     if (rc != SA_OK)
@@ -236,11 +241,40 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
     return 0;
 }
 
-// alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded; with `ends`, alignSequencesGPUEndsFree
+// alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded; with `ends`, alignSequencesGPUEndsFree;
+// with `lo` and `hi`, alignSequencesGPUBandAt
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
                        int device, int gapOpen, int gapExtend, const int *band, const std::string &name,
-                       const int *ends = nullptr);
+                       const int *ends = nullptr, const int *lo = nullptr, const int *hi = nullptr);
+
+// the mode argument of the band-at functions: -1 leaves the mode to Request::alignmentType
+bool bandAtArgsOk(int freeEnds, const int *lo, const int *hi, uint64_t numRequests, const char *name)
+{
+    if (numRequests && (!lo || !hi))
+    {
+        std::cout << "error: " << name << " needs bandLo and bandHi, one entry per request\n";
+        return false;
+    }
+    return freeEnds == -1 || endsFlagsOk(freeEnds, name);
+}
 }  // namespace
+
+uint64_t SequenceAlignment::scoreSequencesGPUBandAt(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                    int gapExtend, int freeEnds, const int *bandLo, const int *bandHi, int *scores)
+{
+    if (!bandAtArgsOk(freeEnds, bandLo, bandHi, numRequests, "scoreSequencesGPUBandAt")) return 1;
+    const int gap[2] = {gapOpen, gapExtend};
+    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUBandAt", nullptr,
+                         freeEnds < 0 ? nullptr : &freeEnds, bandLo, bandHi);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUBandAt(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                                    int gapOpen, int gapExtend, int freeEnds, const int *bandLo, const int *bandHi)
+{
+    if (!bandAtArgsOk(freeEnds, bandLo, bandHi, numRequests, "alignSequencesGPUBandAt")) return 1;
+    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUBandAt",
+                         freeEnds < 0 ? nullptr : &freeEnds, bandLo, bandHi);
+}
 
 uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
 {
@@ -291,7 +325,8 @@ uint64_t SequenceAlignment::alignSequencesGPUEndsFree(const Request *requests, R
 namespace
 {
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
-                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name, const int *ends)
+                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name, const int *ends,
+                       const int *lo, const int *hi)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -317,7 +352,11 @@ uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlign
         ap[i] = responses[i].alignedPatternBytes;
     }
     std::vector<sa_result> res(numRequests);
-    const int rc = band ? sa_align_pairs_banded(&params[0], gapOpen, gapExtend, *band, pairs.data(), (int64_t)numRequests, device,
+    std::vector<sa_band> bands;
+    for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
+    const int rc = lo   ? sa_align_pairs_band_at(&params[0], gapOpen, gapExtend, bands.data(), pairs.data(), (int64_t)numRequests, device,
+                                                 res.data(), at.data(), ap.data())
+                   : band ? sa_align_pairs_banded(&params[0], gapOpen, gapExtend, *band, pairs.data(), (int64_t)numRequests, device,
                                                 res.data(), at.data(), ap.data())
                         : sa_align_pairs_affine(&params[0], gapOpen, gapExtend, pairs.data(), (int64_t)numRequests, device,
                                                 res.data(), at.data(), ap.data());

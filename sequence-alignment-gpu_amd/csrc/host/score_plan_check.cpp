@@ -2,11 +2,13 @@
 // GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
 // the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
 //   sa_score_plan_check --mode global|local|fit|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
-//                       [--gap-extend E] [--band W] [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--gap-extend E] [--band W | --band-at LO:HI] [--match M --mismatch X] NxM[xCOUNT] ...
 // With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty. With --band W
 // it is the banded scorer's (sa_hip.h), and the plan also prints band_cells and, for the first 8
 // pairs, "bands": lo, hi, the pair's band cells and the [jmin, jmax, b0, b1] window of every strip at
-// the plan's R.
+// the plan's R. With --band-at LO:HI it is the band-at scorer's, the one band applied to every pair, with
+// the same output ("band" is -1, lo and hi are the clipped limits, an empty strip's window is
+// [1, 0, 0, 0]).
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -27,8 +29,9 @@ int main(int argc, char **argv)
     P.alphabet_size = 4;
     P.gap_penalty = 5;
     int cus = 256, match = 5, mismatch = -4;
-    bool affine = false, banded = false;
+    bool affine = false, banded = false, band_at = false;
     int32_t band = 0;
+    sa_band at = {0, 0};
     ScoreGap gapm = {0, 0};
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
@@ -51,6 +54,18 @@ int main(int argc, char **argv)
         {
             banded = true;
             band = std::atoi(value());
+        }
+        else if (a == "--band-at")
+        {
+            band_at = true;
+            int lo = 0, hi = 0;
+            if (std::sscanf(value(), "%d:%d", &lo, &hi) != 2)
+            {
+                std::fprintf(stderr, "sa_score_plan_check: --band-at takes LO:HI\n");
+                return 2;
+            }
+            at.lo = lo;
+            at.hi = hi;
         }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
@@ -83,8 +98,9 @@ int main(int argc, char **argv)
     gapm.open = P.gap_penalty;
     ScorePlan pl;
     std::string err;
+    const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
     const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr,
-                                   banded ? &band : nullptr);
+                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -101,18 +117,18 @@ int main(int argc, char **argv)
     // the order of a large batch is long: the first 64 entries
     for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
     std::printf("]");
-    if (banded)
+    if (banded || band_at)
     {
         std::printf(", \"band\": %d, \"band_cells\": %llu, \"bands\": [", pl.band, (unsigned long long)pl.band_cells);
         for (size_t i = 0; i < pairs.size() && i < 8; ++i)
         {
             const int64_t n = (int64_t)pairs[i].text_len, m = (int64_t)pairs[i].pattern_len, rows = 64 * pl.R;
-            const Band bd = band_of(n, m, band);
+            const Band bd = band_at ? pl.bands[i] : band_of(n, m, band);
             std::printf("%s{\"lo\": %d, \"hi\": %d, \"cells\": %llu, \"windows\": [", i ? ", " : "", bd.lo, bd.hi,
                         (unsigned long long)band_cells((uint64_t)n, (uint64_t)m, bd));
             for (int64_t s = 0; n && m && s < (m + rows - 1) / rows; ++s)
             {
-                const BandWindow bw = band_window(n, m, rows, s, bd);
+                const BandWindow bw = band_window_at(n, m, rows, s, bd);
                 std::printf("%s[%d, %d, %d, %d]", s ? ", " : "", bw.jmin, bw.jmax, bw.b0, bw.b1);
             }
             std::printf("]}");

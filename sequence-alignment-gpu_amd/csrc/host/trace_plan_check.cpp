@@ -2,10 +2,11 @@
 // stand-alone program. No GPU, no ROCm: it plans the pair shapes on its command line and prints the
 // plan as one JSON object (tests/test_trace_plan.py).
 //   sa_trace_plan_check --mode global|local|fit|<int> --alphabet A --gap G --gap-extend E --cus N
-//                       [--budget BYTES] [--band W] [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--budget BYTES] [--band W | --band-at LO:HI] [--match M --mismatch X] NxM[xCOUNT] ...
 // --gap is the gap-open penalty. With --band W the plan is the banded aligner's (sa_hip.h): dir_bytes
 // are the band's, "steps" is the sum of the strips' window steps, and each pair also lists the
-// [b0, b1] bodies of its strips' windows (the first 64 strips). Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
+// [b0, b1] bodies of its strips' windows (the first 64 strips). With --band-at LO:HI it is the band-at
+// aligner's, the one band applied to every pair, with the same output (an empty strip's window is [0, 0]). Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -26,8 +27,9 @@ int main(int argc, char **argv)
     P.alphabet_size = 4;
     int cus = 256, match = 5, mismatch = -4, go = 11, ge = 2;
     uint64_t budget = trace_arena_budget();
-    bool banded = false;
+    bool banded = false, band_at = false;
     int32_t band = 0;
+    sa_band at = {0, 0};
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
     {
@@ -47,6 +49,18 @@ int main(int argc, char **argv)
         {
             banded = true;
             band = std::atoi(value());
+        }
+        else if (a == "--band-at")
+        {
+            band_at = true;
+            int lo = 0, hi = 0;
+            if (std::sscanf(value(), "%d:%d", &lo, &hi) != 2)
+            {
+                std::fprintf(stderr, "sa_trace_plan_check: --band-at takes LO:HI\n");
+                return 2;
+            }
+            at.lo = lo;
+            at.hi = hi;
         }
         else if (a == "--match") match = std::atoi(value());
         else if (a == "--mismatch") mismatch = std::atoi(value());
@@ -76,8 +90,9 @@ int main(int argc, char **argv)
 
     TracePlan pl;
     std::string err;
+    const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
     const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err,
-                                   banded ? &band : nullptr);
+                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -99,16 +114,16 @@ int main(int argc, char **argv)
         const uint64_t strips = pl.dir_bytes[i] ? trace_strips(pairs[i].pattern_len) : 0;
         std::printf("%s{\"strips\": %llu, \"steps\": %llu, \"dir_bytes\": %llu, \"dir_off\": %llu, \"slot_off\": %llu", i ? ", " : "",
                     (unsigned long long)strips,
-                    (unsigned long long)(banded ? pl.dir_bytes[i] / kTraceStepBytes : pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
+                    (unsigned long long)(banded || band_at ? pl.dir_bytes[i] / kTraceStepBytes : pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
                     (unsigned long long)pl.dir_bytes[i], (unsigned long long)pl.dir_off[i], (unsigned long long)pl.slot_off[i]);
-        if (banded)
+        if (banded || band_at)
         {
             const int64_t n = (int64_t)pairs[i].text_len, m = (int64_t)pairs[i].pattern_len;
-            const Band bd = band_of(n, m, band);
+            const Band bd = band_at ? pl.score.bands[i] : band_of(n, m, band);
             std::printf(", \"windows\": [");
             for (uint64_t s = 0; s < strips && s < 64; ++s)
             {
-                const BandWindow bw = band_window(n, m, (int64_t)kTraceStripRows, (int64_t)s, bd);
+                const BandWindow bw = band_window_at(n, m, (int64_t)kTraceStripRows, (int64_t)s, bd);
                 std::printf("%s[%d, %d]", s ? ", " : "", bw.b0, bw.b1);
             }
             std::printf("]");

@@ -59,6 +59,23 @@ __global__ __launch_bounds__(64) void align_ends_kernel(AlignEndsArgs ea)
     score_wave<true, kTraceRows, MODE, SMALL, true, false, true>(ea.a.sa.s, ea.a.sa.gap_extend, tab, ea.a.tr, 0, ea.ends);
 }
 
+// align_affine_kernel inside a band of the caller's, one per pair (sa_hip.h sa_align_pairs_band_at;
+// sa_score_wave.h: BAT): the local program, or with free ends the fit or the global one; a strip stores
+// the words of its window, an empty strip none
+struct AlignBandAtArgs {
+    AlignAffineArgs a;
+    int32_t ends;
+    const Band *bands;  // per pair, clipped (ScorePlan::bands)
+};
+
+template <int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void align_band_at_kernel(AlignBandAtArgs ba)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, kTraceRows, MODE, SMALL, true, true, MODE != SA_LOCAL, true>(ba.a.sa.s, ba.a.sa.gap_extend, tab, ba.a.tr, 0, ba.ends,
+                                                                                  ba.bands);
+}
+
 struct WalkArgs {
     const int8_t *text, *pattern;
     const ScorePair *pairs;
@@ -72,6 +89,7 @@ struct WalkArgs {
     sa_result *results;
     int32_t A, mode;                  // mode: one of sa_mode, or SA_ENDS_FREE with its flags
     int32_t band;                     // the half-width of a banded fill, or -1
+    const Band *bands;                // after a band-at fill: every pair's band, clipped; else null
 };
 
 // One wave per pair; the walk of DESIGN.md §3.5: oracle_align's loop (oracle/sa_oracle.c) with a
@@ -99,8 +117,15 @@ struct WalkArgs {
 // walk with SA_ERR_HIP. It cannot happen: H of an in-band cell takes E (F) only when that is a real
 // score, which needs a real H or E to the left (H or F above), that is, an in-band cell there; the
 // sentinel-derived values lose every maximum under the planner's limit (sa_score_wave.h, BAND).
-// BANDED is a template flag so that the unbanded walk pays for none of this.
-template <bool BANDED>
+// BANDED is a template flag so that the unbanded walk pays for none of this: 0 no band, 1 the band of
+// the half-width, 2 a band-at fill. There the pair's band is read from `bands`, every mode walks (the
+// start cell and the stop rule of fit and ends-free as in the unbanded walk), and a strip without an
+// in-band cell holds no words (trace_band_at_strip_words is 0), so counting up to the start cell's strip
+// and stepping back pass over it; the walk reads words of in-band interior cells only, whose strips
+// have a window. The argument above holds for any band: on a border the walk only moves where the stop
+// rule has not ended it, that is, along a border that costs, and the planner admits a pair whose
+// in-band cells of such a border reach back to an in-band origin.
+template <int BANDED>
 __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
 {
     const int lane = threadIdx.x;
@@ -115,11 +140,17 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     char *const op_end = a.out_pattern + slot + (uint64_t)n + (uint64_t)m;
     const uint32_t *const dirs = a.dirs + uniform64(a.dir_off[pi]);
     const uint32_t strip_words = (uint32_t)((n + 126) / 64) * (64u * 64u);
-    const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT, ends = !BANDED && (a.mode & SA_ENDS_FREE) != 0;
+    const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT, ends = BANDED != 1 && (a.mode & SA_ENDS_FREE) != 0;
     const bool tbegin = fit || (ends && (a.mode & SA_FREE_TEXT_BEGIN)), pbegin = ends && (a.mode & SA_FREE_PATTERN_BEGIN);
     const int A = a.A;
-    constexpr bool banded = BANDED;
-    const Band bd = band_of(n, m, banded ? a.band : 0);
+    constexpr bool banded = BANDED != 0, bat = BANDED == 2;
+    Band bd;
+    if constexpr (bat)
+    {
+        bd = a.bands[pi];
+        bd = Band{uniform(bd.lo), uniform(bd.hi)};
+    }
+    else bd = band_of(n, m, banded ? a.band : 0);
     int bstrip = -1, bstep0 = 0;  // banded: the strip whose base is held, and its window's first step
     int bsteps = INT32_MAX;       // and the number of its steps: no word is read outside the window
     uint64_t bbase = 0;           // its first word
@@ -151,7 +182,7 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     for (int it = 0;; ++it)
     {
         bool stop;
-        if constexpr (BANDED) stop = local ? (i == 0 || j == 0) : fit ? i == 0 : (i == 0 && j == 0);  // the planner admits no free ends
+        if constexpr (BANDED == 1) stop = local ? (i == 0 || j == 0) : fit ? i == 0 : (i == 0 && j == 0);  // the planner admits no free ends
         else stop = local ? (i == 0 || j == 0) : (i == 0 && (tbegin || j == 0)) || (j == 0 && (pbegin || i == 0));
         if (stop)
         {
@@ -171,10 +202,12 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
                 const int strip = col >> 6;
                 if (banded && strip != bstrip)
                 {
+                    auto words = [&](int st) { return bat ? trace_band_at_strip_words(n, m, st, bd) : trace_band_strip_words(n, m, st, bd); };
                     if (bstrip < 0)
-                        for (bstrip = 0; bstrip < strip; ++bstrip) bbase += trace_band_strip_words(n, m, bstrip, bd);
-                    for (; bstrip > strip; --bstrip) bbase -= trace_band_strip_words(n, m, bstrip - 1, bd);
-                    const BandWindow bw = band_window(n, m, (int64_t)kTraceStripRows, strip, bd);
+                        for (bstrip = 0; bstrip < strip; ++bstrip) bbase += words(bstrip);
+                    for (; bstrip > strip; --bstrip) bbase -= words(bstrip - 1);
+                    const BandWindow bw = bat ? band_window_at(n, m, (int64_t)kTraceStripRows, strip, bd)
+                                              : band_window(n, m, (int64_t)kTraceStripRows, strip, bd);
                     bstep0 = 64 * bw.b0;
                     bsteps = 64 * (bw.b1 - bw.b0);
                 }
@@ -268,9 +301,29 @@ struct Workspace {
     }
 };
 
-void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st, int band)
+void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st, int band, const Band *bands)
 {
-    if (band >= 0)  // the planner admits global and local
+    if (bands)  // SA_GLOBAL and SA_FIT as the ends-free modes they equal
+    {
+        const int fl = mode == SA_FIT ? SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END : mode & SA_ENDS_FREE ? mode & 15 : 0;
+        const AlignBandAtArgs ba = {a, fl, bands};
+        if (mode == SA_LOCAL)
+        {
+            if (small) hipLaunchKernelGGL((align_band_at_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, ba);
+            else hipLaunchKernelGGL((align_band_at_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, ba);
+        }
+        else if (fl & SA_FREE_TEXT_END)
+        {
+            if (small) hipLaunchKernelGGL((align_band_at_kernel<SA_FIT, true>), dim3(grid), dim3(64), 0, st, ba);
+            else hipLaunchKernelGGL((align_band_at_kernel<SA_FIT, false>), dim3(grid), dim3(64), 0, st, ba);
+        }
+        else
+        {
+            if (small) hipLaunchKernelGGL((align_band_at_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, ba);
+            else hipLaunchKernelGGL((align_band_at_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, ba);
+        }
+    }
+    else if (band >= 0)  // the planner admits global and local
     {
         const AlignBandArgs ba = {a, band};
         if (mode == SA_LOCAL)
@@ -319,15 +372,18 @@ void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipS
 
 int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa_pair *pairs, int64_t np, int device,
                             const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
-                            char *const *aligned_pattern, const int32_t *band)
+                            char *const *aligned_pattern, const int32_t *band, bool with_bands, const sa_band *bands)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "affine aligner: null argument");
+    if (with_bands && !bands && np > 0) return fail(SA_ERR_INVALID, "sa_align_pairs_band_at: bands is null");
+    static const sa_band none = {0, 0};
+    if (with_bands && !bands) bands = &none;  // no pair reads it
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     TracePlan pl;
     std::string err;
-    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err, band))
+    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err, band, bands))
         return fail(rc, err);
     if (!P->alphabet) return fail(SA_ERR_INVALID, "affine aligner: params->alphabet is null");
     g_stats = AffineStats();
@@ -352,7 +408,13 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     uint64_t *d_dir_off, *d_slot_off;
     char *d_ot = nullptr, *d_op = nullptr, *d_alpha;
     sa_result *d_results;
+    Band *d_bands = nullptr;
     int rc;
+    if (with_bands)
+    {
+        if ((rc = ws.alloc(&d_bands, (size_t)np * sizeof(Band)))) return rc;
+        HIP_TRY(hipMemcpy(d_bands, pl.score.bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
+    }
     if ((rc = ws.alloc(&d_pairs, (size_t)np * sizeof(ScorePair))) || (rc = ws.alloc(&d_order, (size_t)np * 4)) ||
         (rc = ws.alloc(&d_table, 32 * 32 * 4)) || (rc = ws.alloc(&d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) ||
         (rc = ws.alloc(&d_scores, (size_t)np * sizeof(sa_score_result))) || (rc = ws.alloc(&d_ctrl, 256)) ||
@@ -410,6 +472,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     wa.A = A;
     wa.mode = pl.score.mode;
     wa.band = pl.score.band;
+    wa.bands = d_bands;
     uint32_t ctrl[2] = {0, 0};
     // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
     // copies into `results` and `ctrl` pending when this function returns
@@ -423,11 +486,12 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
             s.np = (int32_t)count;
             wa.order = s.order;
             HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, wa.band);
+            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, wa.band, d_bands);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
-            if (wa.band >= 0) hipLaunchKernelGGL(walk_affine_kernel<true>, dim3((unsigned)count), dim3(64), 0, st, wa);
-            else hipLaunchKernelGGL(walk_affine_kernel<false>, dim3((unsigned)count), dim3(64), 0, st, wa);
+            if (d_bands) hipLaunchKernelGGL(walk_affine_kernel<2>, dim3((unsigned)count), dim3(64), 0, st, wa);
+            else if (wa.band >= 0) hipLaunchKernelGGL(walk_affine_kernel<1>, dim3((unsigned)count), dim3(64), 0, st, wa);
+            else hipLaunchKernelGGL(walk_affine_kernel<0>, dim3((unsigned)count), dim3(64), 0, st, wa);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 2], st));
         }
@@ -473,7 +537,8 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
 
 static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
                             const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
-                            char *const *aligned_text, char *const *aligned_pattern);
+                            char *const *aligned_text, char *const *aligned_pattern, bool with_bands = false,
+                            const sa_band *bands = nullptr);
 
 extern "C" {
 
@@ -489,12 +554,19 @@ int sa_align_pairs_banded(const sa_params *P, int32_t gap_open, int32_t gap_exte
     return align_host_pairs(P, gap_open, gap_extend, &band, pairs, np, device, results, aligned_text, aligned_pattern);
 }
 
+int sa_align_pairs_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands, const sa_host_pair *pairs,
+                           int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern, true, bands);
+}
+
 }  // extern "C"
 
-// sa_align_pairs_affine and, with `band`, sa_align_pairs_banded: the host pairs packed into two arenas
+// sa_align_pairs_affine and, with `band`, sa_align_pairs_banded, with `with_bands`, sa_align_pairs_band_at:
+// the host pairs packed into two arenas
 static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
                             const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
-                            char *const *aligned_text, char *const *aligned_pattern)
+                            char *const *aligned_text, char *const *aligned_pattern, bool with_bands, const sa_band *bands)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
@@ -522,7 +594,7 @@ static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_ex
     if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
     if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
     return align_affine_device(P, gap_open, gap_extend, dp.data(), np, device, dt.p, dpat.p, results, aligned_text,
-                               aligned_pattern, band);
+                               aligned_pattern, band, with_bands, bands);
 }
 
 extern "C" {

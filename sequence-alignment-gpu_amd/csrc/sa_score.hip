@@ -70,6 +70,22 @@ __global__ __launch_bounds__(64) void score_affine_ends_kernel(ScoreEndsArgs ea)
     score_wave<true, R, MODE, SMALL, false, false, true>(ea.sa.s, ea.sa.gap_extend, tab, TraceArgs(), 0, ea.ends);
 }
 
+// score_affine_kernel inside a band of the caller's, one per pair (sa_hip.h sa_score_batch_band_at;
+// sa_score_wave.h: BAT). MODE is the program: SA_LOCAL, or with free ends SA_FIT when the text's end is
+// free and SA_GLOBAL otherwise; global and fit alignment run as the ends-free modes they equal.
+struct ScoreBandAtArgs {
+    ScoreAffineArgs sa;
+    int32_t ends;
+    const Band *bands;  // per pair, clipped (ScorePlan::bands)
+};
+
+template <int R, int MODE, bool SMALL>
+__global__ __launch_bounds__(64) void score_band_at_kernel(ScoreBandAtArgs ba)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, R, MODE, SMALL, false, true, MODE != SA_LOCAL, true>(ba.sa.s, ba.sa.gap_extend, tab, TraceArgs(), 0, ba.ends, ba.bands);
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -84,19 +100,30 @@ namespace {
 // a.gap is the linear penalty or the gap-open penalty. BAND (affine, global or local; band >= 0) is
 // score_band_kernel. A mode with SA_ENDS_FREE is score_ends_kernel or score_affine_ends_kernel, the fit
 // program when the text's end is free and the global one otherwise.
+// `bands` non-null (BAND): score_band_at_kernel on the per-pair bands; SA_GLOBAL and SA_FIT launch as
+// SA_ENDS_FREE with no flags and with the text's two.
 template <bool AFFINE, bool BAND = false>
-void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st, int band = 0)
+void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st, int band = 0,
+                  const Band *bands = nullptr)
 {
+    if (bands && mode == SA_GLOBAL) mode = SA_ENDS_FREE;
+    if (bands && mode == SA_FIT) mode = SA_ENDS_FREE | SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END;
     const ScoreAffineArgs aa = {a, gap_extend};
     const ScoreBandArgs ba = {aa, band};
     const bool ends = (mode & SA_ENDS_FREE) != 0;
     const ScoreEndsArgs ea = {aa, mode & 15};
+    const ScoreBandAtArgs bat = {aa, mode & 15, bands};
     const int shape = !ends ? mode : mode & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL;
     auto launch = [&](auto rc, auto modec, auto smallc) {
         constexpr int RR = decltype(rc)::value, MODE = decltype(modec)::value;
         constexpr bool SMALL = decltype(smallc)::value;
         if constexpr (BAND)
         {
+            if (bands)
+            {
+                hipLaunchKernelGGL((score_band_at_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, bat);
+                return;
+            }
             if constexpr (MODE != SA_FIT) hipLaunchKernelGGL((score_band_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ba);
         }
         else if (ends)
@@ -133,6 +160,7 @@ struct sa_scorer : ScorePlan {
     int device = 0;
     ScorePair *d_pairs = nullptr;
     int32_t *d_order = nullptr, *d_table = nullptr, *d_rows = nullptr;
+    Band *d_bands = nullptr;  // band-at scorer: ScorePlan::bands
     sa_score_result *d_out = nullptr;
     uint32_t *d_ctrl = nullptr;
     bool ran = false;
@@ -144,7 +172,7 @@ void free_scorer(sa_scorer *s)
 {
     if (!s) return;
     DeviceGuard dg(s->device);
-    void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl};
+    void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl, s->d_bands};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -152,19 +180,22 @@ void free_scorer(sa_scorer *s)
 
 }  // namespace
 
-// sa_scorer_create, sa_scorer_create_affine and sa_scorer_create_banded: `gapm` null is the linear
-// scorer, `band` non-null the banded one
+// sa_scorer_create, sa_scorer_create_affine, sa_scorer_create_banded and sa_scorer_create_band_at:
+// `gapm` null is the linear scorer, `band` non-null the banded one, `with_bands` the band-at one on `bands`
 static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out,
-                         const int32_t *band = nullptr)
+                         const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr)
 {
     if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create: null argument");
     *out = nullptr;
+    if (with_bands && !bands && np > 0) return fail(SA_ERR_INVALID, "sa_scorer_create_band_at: bands is null");
+    static const sa_band none = {0, 0};
+    if (with_bands && !bands) bands = &none;  // no pair reads it
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm, band)) return fail(rc, err);
+    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm, band, bands)) return fail(rc, err);
     std::vector<ScorePair> h((size_t)np);
     for (int64_t p = 0; p < np; ++p)
         h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
@@ -176,6 +207,8 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
     if ((rc = dmalloc(&s->d_rows, (size_t)s->grid * s->row_stride * (s->affine ? 8 : 4)))) return rc;
     if ((rc = dmalloc(&s->d_out, (size_t)np * sizeof(sa_score_result)))) return rc;
     if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
+    if (with_bands && (rc = dmalloc(&s->d_bands, std::max<size_t>((size_t)np, 1) * sizeof(Band)))) return rc;
+    if (with_bands && np) HIP_TRY(hipMemcpy(s->d_bands, s->bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
     if (np)
     {
         HIP_TRY(hipMemcpy(s->d_pairs, h.data(), h.size() * sizeof(ScorePair), hipMemcpyHostToDevice));
@@ -188,7 +221,7 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
 
 // sa_score_batch, sa_score_batch_affine and sa_score_batch_banded
 static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_pair *pairs, int64_t np, int device,
-                       sa_score_result *out, const int32_t *band = nullptr)
+                       sa_score_result *out, const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch: null argument");
     std::vector<sa_pair> dp((size_t)np);
@@ -204,7 +237,7 @@ static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_p
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     sa_scorer *raw = nullptr;
-    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw, band)) return rc;
+    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw, band, with_bands, bands)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
     std::vector<char> ht(tb), hp(pb);
     for (int64_t p = 0; p < np; ++p)
@@ -242,6 +275,13 @@ int sa_scorer_create_banded(const sa_params *P, int32_t gap_open, int32_t gap_ex
     return create_scorer(P, &gapm, pairs, np, device, out, &band);
 }
 
+int sa_scorer_create_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands, const sa_pair *pairs,
+                             int64_t np, int device, sa_scorer **out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return create_scorer(P, &gapm, pairs, np, device, out, nullptr, true, bands);
+}
+
 int sa_scorer_destroy(sa_scorer *s)
 {
     free_scorer(s);
@@ -273,7 +313,8 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     a.key_rowbits = s->key_rowbits;
     a.row_stride = s->row_stride;
     const bool small = s->A <= 4;
-    if (s->band >= 0) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, s->band);
+    if (s->d_bands) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, 0, s->d_bands);
+    else if (s->band >= 0) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, s->band);
     else if (s->affine) launch_score<true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st);
     else launch_score<false>(a, 0, s->R, s->mode, small, s->grid, st);
     HIP_TRY(hipGetLastError());
@@ -322,6 +363,13 @@ int sa_score_batch_banded(const sa_params *P, int32_t gap_open, int32_t gap_exte
 {
     const ScoreGap gapm = {gap_open, gap_extend};
     return score_batch(P, &gapm, pairs, np, device, out, &band);
+}
+
+int sa_score_batch_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands,
+                           const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return score_batch(P, &gapm, pairs, np, device, out, nullptr, true, bands);
 }
 
 }  // extern "C"

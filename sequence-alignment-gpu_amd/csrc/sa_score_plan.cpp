@@ -38,8 +38,46 @@ int bitlen(uint64_t v)
 
 }  // namespace
 
+// sa_hip.h: an in-band permitted start componentwise <= an in-band permitted end. A start on row 0
+// lies above every end, so the one of the smallest column serves for all of them (the origin, or under
+// TB the band's first cell of row 0), likewise the start of the smallest row on column 0; an end on
+// row m lies below every start, so the rightmost serves ((m, n), or under TE the band's last cell of
+// row m), likewise the lowest end on column n.
+extern "C" int sa_band_reachable(int32_t mode, uint64_t text_len, uint64_t pattern_len, sa_band band)
+{
+    if (mode == SA_LOCAL) return 1;
+    int fl;
+    if (mode == SA_GLOBAL) fl = 0;
+    else if (mode == SA_FIT) fl = SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END;
+    else if (mode >= SA_ENDS_FREE && mode <= SA_OVERLAP) fl = mode & 15;
+    else return -1;
+    if (band.lo > band.hi) return 0;
+    const int64_t n = (int64_t)std::min<uint64_t>(text_len, (uint64_t)1 << 40), m = (int64_t)std::min<uint64_t>(pattern_len, (uint64_t)1 << 40);
+    const int64_t lo = band.lo, hi = band.hi;
+    auto in = [&](int64_t i, int64_t j) { return lo <= j - i && j - i <= hi; };
+    int64_t st[2][2], en[2][2];
+    int ns = 0, ne = 0;
+    if (in(0, 0)) st[ns][0] = 0, st[ns][1] = 0, ++ns;
+    else
+    {
+        if ((fl & SA_FREE_TEXT_BEGIN) && lo > 0 && lo <= n) st[ns][0] = 0, st[ns][1] = lo, ++ns;
+        if ((fl & SA_FREE_PATTERN_BEGIN) && hi < 0 && -hi <= m) st[ns][0] = -hi, st[ns][1] = 0, ++ns;
+    }
+    if (in(m, n)) en[ne][0] = m, en[ne][1] = n, ++ne;
+    else
+    {
+        // row m: columns m + lo .. m + hi inside 0 .. n; column n: rows n - hi .. n - lo inside 0 .. m
+        if ((fl & SA_FREE_TEXT_END) && m + lo <= n && m + hi >= 0) en[ne][0] = m, en[ne][1] = std::min(n, m + hi), ++ne;
+        if ((fl & SA_FREE_PATTERN_END) && n - hi <= m && n - lo >= 0) en[ne][0] = std::min(m, n - lo), en[ne][1] = n, ++ne;
+    }
+    for (int a = 0; a < ns; ++a)
+        for (int b = 0; b < ne; ++b)
+            if (st[a][0] <= en[b][0] && st[a][1] <= en[b][1]) return 1;
+    return 0;
+}
+
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine, const int32_t *band)
+                    ScorePlan *out, std::string *err, const ScoreGap *affine, const int32_t *band, const sa_band *bands)
 {
     auto fail = [&](int code, const char *msg) { *err = msg; return code; };
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
@@ -56,6 +94,8 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
         if (P->mode == SA_FIT) return fail(SA_ERR_UNSUPPORTED, "SA_FIT takes no band");
         if (ends) return fail(SA_ERR_UNSUPPORTED, "SA_ENDS_FREE takes no band");
     }
+    if (bands && (!affine || band)) return fail(SA_ERR_INVALID, "per-pair bands take gap_open and gap_extend and no half-width");
+    const bool banded = band || bands;
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
     if (R == 16 || R == 32) R = 8;  // a params struct shared with a plan: the scorer's tallest strip
@@ -86,13 +126,39 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
         const uint64_t span = n + m;
         const uint64_t bound = ((uint64_t)sabs + (uint64_t)std::llabs(g)) * span + (uint64_t)std::llabs(g) * span;
         if (bound >= (1ull << 30)) return fail(SA_ERR_UNSUPPORTED, "scores may exceed the int32 range");
-        if (band && bound >= kBandScoreLimit) return fail(SA_ERR_UNSUPPORTED, "scores may reach the band's sentinel");
+        if (banded && bound >= kBandScoreLimit) return fail(SA_ERR_UNSUPPORTED, "scores may reach the band's sentinel");
         const uint64_t h = g >= 0 ? (uint64_t)std::max<int64_t>(smax, 0) * std::min(n, m)
                                   : ((uint64_t)sabs + (uint64_t)(-g)) * span;
         hmax_local = std::max(hmax_local, h);
         pl.max_text = std::max(pl.max_text, n);
         pl.input_bytes += n + m;
     }
+    // ---- the band-at scorer: every pair's band is a band and admits an alignment; the kernels take the
+    // clipped bands and rely on both ----
+    if (bands)
+    {
+        pl.bands.resize((size_t)np);
+        for (int64_t p = 0; p < np; ++p)
+        {
+            const std::string who = "pair " + std::to_string(p) + ": band [" + std::to_string(bands[p].lo) + ", " + std::to_string(bands[p].hi) + "]";
+            if (bands[p].lo > bands[p].hi)
+            {
+                *err = who + " has lo > hi";
+                return SA_ERR_INVALID;
+            }
+            if (sa_band_reachable(P->mode, pairs[p].text_len, pairs[p].pattern_len, bands[p]) != 1)
+            {
+                *err = who + " admits no alignment of " + std::to_string(pairs[p].text_len) + " text and " +
+                       std::to_string(pairs[p].pattern_len) + " pattern letters in mode " + std::to_string(P->mode) + " (sa_band_reachable)";
+                return SA_ERR_INVALID;
+            }
+            pl.bands[p] = band_clip((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, bands[p].lo, bands[p].hi);
+        }
+    }
+    // a pair's band and the window of one of its strips: band_window_at is band_window on the bands of band_of
+    auto pair_band = [&](int64_t p) {
+        return bands ? pl.bands[p] : band_of((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, *band);
+    };
     pl.key_rowbits = std::max(1, bitlen(lmax + 1));
     if (P->mode == SA_LOCAL && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * pl.key_rowbits))
         return fail(SA_ERR_UNSUPPORTED, "local scores may exceed the best-cell key range");
@@ -114,8 +180,8 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     for (int64_t p = 0; p < np; ++p)
     {
         const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
-        cells[p] = band ? band_cells(n, m, band_of((int64_t)n, (int64_t)m, *band)) : n * m;
-        if (band) pl.band_cells += cells[p];
+        cells[p] = banded ? band_cells(n, m, pair_band(p)) : n * m;
+        if (banded) pl.band_cells += cells[p];
     }
     std::stable_sort(pl.order.begin(), pl.order.end(), [&](int32_t a, int32_t b) { return cells[a] > cells[b]; });
 
@@ -143,16 +209,16 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
             const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
             if (n == 0 || m == 0) continue;
             const uint64_t strips = (m + rows - 1) / rows;
-            if (!band)
+            if (!banded)
             {
                 c += (n + 63) * strips * per_step;
                 continue;
             }
-            const Band bd = band_of((int64_t)n, (int64_t)m, *band);
+            const Band bd = pair_band(p);
             for (uint64_t s = 0; s < strips; ++s)
             {
-                const BandWindow bw = band_window((int64_t)n, (int64_t)m, (int64_t)rows, (int64_t)s, bd);
-                c += (uint64_t)(bw.jmax - bw.jmin + 64) * per_step;
+                const BandWindow bw = band_window_at((int64_t)n, (int64_t)m, (int64_t)rows, (int64_t)s, bd);
+                if (bw.b1 > bw.b0) c += (uint64_t)(bw.jmax - bw.jmin + 64) * per_step;  // an empty strip runs no step
             }
         }
         pl.cost[k] = c;
@@ -162,13 +228,13 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     for (int64_t p = 0; p < np; ++p)
     {
         const uint64_t rows = 64ull * pl.R, n = pairs[p].text_len, m = pairs[p].pattern_len, strips = (m + rows - 1) / rows;
-        if (!band || n == 0) pl.padded_cells += n * strips * rows;
+        if (!banded || n == 0) pl.padded_cells += n * strips * rows;
         else
         {
-            const Band bd = band_of((int64_t)n, (int64_t)m, *band);
+            const Band bd = pair_band(p);
             for (uint64_t s = 0; s < strips; ++s)
             {
-                const BandWindow bw = band_window((int64_t)n, (int64_t)m, (int64_t)rows, (int64_t)s, bd);
+                const BandWindow bw = band_window_at((int64_t)n, (int64_t)m, (int64_t)rows, (int64_t)s, bd);
                 pl.padded_cells += (uint64_t)(bw.jmax - bw.jmin + 1) * rows;
             }
         }
@@ -179,7 +245,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
                         : affine ? score_affine_waves_per_simd(pl.R) : score_waves_per_simd(pl.R);
     pl.grid = (int)std::min<int64_t>(np, (int64_t)pl.num_cu * 4 * pl.waves_per_simd);
     pl.row_stride = (pl.max_text + 63) / 64 * 64 + 64;
-    const uint64_t per_pair = 24 /* descriptor */ + 4 /* order */ + sizeof(sa_score_result);
+    const uint64_t per_pair = 24 /* descriptor */ + (bands ? 8 : 0) /* band */ + 4 /* order */ + sizeof(sa_score_result);
     pl.device_bytes = pl.input_bytes + (uint64_t)np * per_pair + (uint64_t)pl.grid * pl.row_stride * (affine ? 8 : 4) +
                       32 * 32 * 4 /* score table */ + 256 /* counter and flags */;
     return SA_OK;

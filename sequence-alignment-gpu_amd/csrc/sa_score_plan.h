@@ -79,17 +79,44 @@ SA_BAND_FN BandWindow band_window(int64_t n, int64_t m, int64_t rows, int64_t s,
     const int64_t jmin = first + bd.lo > 1 ? first + bd.lo : 1, jmax = last + bd.hi < n ? last + bd.hi : n;
     return BandWindow{(int32_t)jmin, (int32_t)jmax, (int32_t)((jmin - 1) / 64), (int32_t)((jmax + 62) / 64 + 1)};
 }
-// Cells (i, j), 1 <= i <= m, 1 <= j <= n, inside the band: the sum over the rows of
+// Cells (i, j), 1 <= i <= m, 1 <= j <= n, inside the band, for any lo <= hi: the sum over the rows
+// ia .. ib that hold an in-band column (i + hi >= 1 and i + lo <= n) of
 // min(n, i + hi) - max(1, i + lo) + 1, in closed form.
 inline uint64_t band_cells(uint64_t n_, uint64_t m_, Band bd)
 {
     const int64_t n = (int64_t)n_, m = (int64_t)m_, lo = bd.lo, hi = bd.hi;
-    if (n == 0 || m == 0) return 0;
-    const int64_t k = std::min(std::max<int64_t>(n - hi, 0), m);  // rows whose last column is i + hi
-    const int64_t right = k * (k + 1) / 2 + k * hi + (m - k) * n;
-    const int64_t k2 = std::min(std::max<int64_t>(-lo, 0), m);    // rows whose first column is 1
-    const int64_t left = k2 + (m * (m + 1) / 2 - k2 * (k2 + 1) / 2) + (m - k2) * lo;
-    return (uint64_t)(right - left + m);
+    if (n == 0 || m == 0 || lo > hi) return 0;
+    const int64_t ia = std::max<int64_t>(1, 1 - hi), ib = std::min<int64_t>(m, n - lo);
+    if (ia > ib) return 0;
+    auto tri = [](int64_t a, int64_t b) { return b < a ? 0 : (a + b) * (b - a + 1) / 2; };  // a + .. + b
+    const int64_t k = std::min(std::max<int64_t>(n - hi, ia - 1), ib);   // rows ia .. k end at column i + hi
+    const int64_t right = tri(ia, k) + (k - ia + 1) * hi + (ib - k) * n;
+    const int64_t k2 = std::min(std::max<int64_t>(1 - lo, ia - 1), ib);  // rows ia .. k2 start at column 1
+    const int64_t left = (k2 - ia + 1) + tri(k2 + 1, ib) + (ib - k2) * lo;
+    return (uint64_t)(right - left + (ib - ia + 1));
+}
+
+// A caller's band (sa_hip.h sa_band, one per pair: the band-at functions) as the kernels take it: both
+// limits brought into [-m, n], which changes no in-band cell of a reachable pair. A band with no cell
+// at all (lo > n or hi < -m; only a local pair gets this far) becomes {n, n} or {-m, -m}: one border
+// cell, no interior cell.
+SA_BAND_FN Band band_clip(int64_t n, int64_t m, int64_t lo, int64_t hi)
+{
+    const int64_t l = lo < -m ? -m : lo > n ? n : lo, h = hi < -m ? -m : hi > n ? n : hi;
+    return Band{(int32_t)l, (int32_t)h};
+}
+// band_window for any lo <= hi. Rows of the strip with an in-band column in 1..n are those from 1 - hi
+// to n - lo; their windows shift right row by row, so the strip's in-band columns run from the first
+// such row's to the last such row's. A strip without one is empty: b0 == b1, jmax < jmin, no body runs
+// and no direction word is stored. With lo <= min(0, n - m) and hi >= max(0, n - m) (band_of) every row
+// has one and the result is band_window's.
+SA_BAND_FN BandWindow band_window_at(int64_t n, int64_t m, int64_t rows, int64_t s, Band bd)
+{
+    const int64_t first = rows * s + 1, last = m < rows * (s + 1) ? m : rows * (s + 1);
+    const int64_t ia = first > 1 - bd.hi ? first : 1 - bd.hi, ib = last < n - bd.lo ? last : n - bd.lo;
+    if (ia > ib) return BandWindow{1, 0, 0, 0};
+    const int64_t jmin = ia + bd.lo > 1 ? ia + bd.lo : 1, jmax = ib + bd.hi < n ? ib + bd.hi : n;
+    return BandWindow{(int32_t)jmin, (int32_t)jmax, (int32_t)((jmin - 1) / 64), (int32_t)((jmax + 62) / 64 + 1)};
 }
 
 // The value of H, E and F of every out-of-band cell, and the limit of the banded planner: with
@@ -104,6 +131,7 @@ struct ScorePlan {
     bool affine = false;           // score_affine_kernel: gap, gap_extend
     int gap_extend = 0;
     int band = -1;                 // banded scorer (affine only): the half-width; -1: the whole rectangle
+    std::vector<Band> bands;       // band-at scorer (affine only): every pair's band, clipped (band_clip); band is -1
     int num_cu = 0, waves_per_simd = 0, grid = 0;
     int64_t num_pairs = 0;
     uint64_t max_text = 0;         // longest text
@@ -122,8 +150,13 @@ struct ScorePlan {
 // `band` non-null: the banded scorer of that half-width (affine only, global or local): a strip is
 // charged the steps of its window, the work order and padded_cells count band cells, and the score
 // limit is kBandScoreLimit.
+// `bands` non-null (and `band` null): the band-at scorer (sa_hip.h sa_score_batch_band_at), bands[p] the
+// band of pair p, in every mode: lo > hi and a pair that sa_band_reachable denies are SA_ERR_INVALID, the
+// message naming the pair; the rest as with `band`, on the clipped bands (ScorePlan::bands), and the
+// descriptors count 8 more bytes per pair.
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr, const int32_t *band = nullptr);
+                    ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr, const int32_t *band = nullptr,
+                    const sa_band *bands = nullptr);
 
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).

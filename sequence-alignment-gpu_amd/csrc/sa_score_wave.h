@@ -92,6 +92,28 @@
 //    and the closed-form border candidates H[0][n] and H[m][0] in the tie order of sa_hip.h.
 //  - An empty side: every candidate is a border cell; the early-out compares the border values at
 //    0, 1 and the side's length, as a gap's cost need not grow with its length.
+//
+// BAT (BAND; MODE SA_LOCAL, or ENDS with the global or the fit program: score_band_at_kernel,
+// align_band_at_kernel) is the band program on a band of the caller's, sa_hip.h sa_band: `bands` holds
+// one (lo, hi) per pair, clipped to [-m, n] by the planner and read once per pair as a wave-uniform
+// value. Neither lo <= 0 <= hi nor "every row has an in-band cell" holds any more; the planner admits
+// only pairs with an alignment inside their band (sa_band_reachable), and in such a pair every in-band
+// cell, border cells included, is a real score: an in-band border cell that costs implies an in-band
+// origin, and every in-band cell lies on a diagonal that starts in a real border cell. Everything of
+// BAT is under `if constexpr (BAT)`; the other instances compile to what they were.
+//  - Windows. band_window_at may be empty (b0 == b1): the strip runs no body, stores no direction word
+//    and leaves the row buffer alone. The strip after it masks the whole row above it (an empty strip's
+//    last row holds no in-band column in 1..n), so the buffer's stale content is never read; the
+//    between-strips argument of "Bottom row" holds between two strips that both ran as it stands.
+//  - Borders. (row, 0) is real iff in band, -hi <= row <= -lo, and (0, j) iff lo <= j <= hi. Strip 0
+//    under lo > 0 starts past body 0: lane 0's upprev is then the border H[0][64 b0], not a row-buffer word.
+//  - Result. PE folds a row only if (row, n) is in band: only then did the strip's window reach column n
+//    and hl[r] is H[row][n]. The running best of row m sees sentinels (out-of-band columns) before or
+//    after real values; a real value is above -2^29 under the planner's limit and the sentinel never
+//    ties one, so the best is the leftmost real maximum, or at most -2^29 when row m has no in-band
+//    column in 1..n. Lane 0 drops a row-m candidate that is not real ((m, n) out of band without TE) and
+//    counts H[0][n] and H[m][0] only in band; reachability leaves at least one candidate.
+//  - An empty side: the candidates are the border's in-band cells.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -144,14 +166,15 @@ struct MaskedStep : std::true_type {
 
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
 // registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
-template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false>
+template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false, bool BAT = false>
 __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs(),
-                                           int band = 0, int ends = 0)
+                                           int band = 0, int ends = 0, const Band *bands = nullptr)
 {
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
-    static_assert(!BAND || (AFFINE && MODE != SA_FIT), "banded instances: affine, global or local");
-    static_assert(!ENDS || (MODE != SA_LOCAL && !BAND), "ends-free instances: the global or the fit program, no band");
+    static_assert(!BAND || (AFFINE && (BAT || MODE != SA_FIT)), "banded instances: affine; on the half-width, global or local");
+    static_assert(!ENDS || (MODE != SA_LOCAL && (BAT || !BAND)), "ends-free instances: the global or the fit program, no band but the caller's");
+    static_assert(!BAT || (BAND && (ENDS || MODE == SA_LOCAL)), "band-at instances: banded; local, or ends-free (global and fit are two of its flag sets)");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
     constexpr int SENT = kBandSentinel;
     using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
@@ -192,7 +215,22 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     const bool zero = rows ? epb : etb, anywhere = rows ? epe : FIT;
                     auto bval = [&](int c) { return c == 0 || zero ? 0 : -gapc(c); };
                     int bc = k, bv = bval(k);
-                    if (anywhere)
+                    if constexpr (BAT)
+                    {
+                        // only the border's in-band cells count: (c, 0) for -hi <= c <= -lo, (0, c) for
+                        // lo <= c <= hi. The planner admitted the pair, so there is one, cell k is one
+                        // unless any will do, and a border that costs has the origin in band. bval is
+                        // linear from 1 on: the first maximum lies at ca, at 1 after 0, or at cb
+                        const Band bd = bands[pi];
+                        const int ca = max(0, rows ? -bd.hi : bd.lo), cb = min(k, rows ? -bd.lo : bd.hi);
+                        if (anywhere)
+                        {
+                            bc = ca, bv = bval(ca);
+                            if (ca == 0 && cb >= 1 && bval(1) > bv) bc = 1, bv = bval(1);
+                            if (cb > bc && bval(cb) > bv) bc = cb, bv = bval(cb);
+                        }
+                    }
+                    else if (anywhere)
                     {
                         bc = 0, bv = 0;
                         if (k >= 1 && bval(1) > bv) bc = 1, bv = bval(1);
@@ -243,18 +281,27 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         // BAND: cell (i, j) is in band iff (unsigned)(j - i - blo) <= bspan
         int blo = 0;
         uint32_t bspan = 0;
-        if constexpr (BAND)
+        if constexpr (BAT)
+        {
+            // the caller's band of this pair, clipped by the planner (band_clip): wave-uniform
+            const Band bd = bands[pi];
+            blo = uniform(bd.lo);
+            bspan = (uint32_t)(uniform(bd.hi) - blo);
+        }
+        else if constexpr (BAND)
         {
             const Band bd = band_of(n, m, band);
             blo = bd.lo;
             bspan = (uint32_t)(bd.hi - bd.lo);
         }
+        auto inb = [&](int i, int j) { return (uint32_t)(j - i - blo) <= bspan; };  // BAND: cell (i, j) is in band
         for (int s = 0; s < nstrips; ++s)
         {
             const int row1 = s * 64 * R + R * lane;  // rows row1 + 1 .. row1 + R
             // the strip's bodies: all of them, or (BAND) its window's
             BandWindow bw = {};
-            if constexpr (BAND) bw = band_window(n, m, 64 * R, s, Band{blo, blo + (int)bspan});
+            if constexpr (BAT) bw = band_window_at(n, m, 64 * R, s, Band{blo, blo + (int)bspan});  // may be empty: no body
+            else if constexpr (BAND) bw = band_window(n, m, 64 * R, s, Band{blo, blo + (int)bspan});
             const int bfirst = BAND ? bw.b0 : 0, bend = BAND ? bw.b1 : nbodies;
             int s0[R], s1[R], s2[R], s3[R];  // S[pattern letter of the row][0..3] (SMALL)
             int prow[R];               // A * pattern letter of the row (LDS table row)
@@ -294,7 +341,8 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 {
                     // a window past body 0 starts left of the band in every row; in body 0 the border
                     // cell (row, 0) is in band down to row -lo
-                    const bool in = bfirst == 0 && row1 + r + 1 <= -blo;
+                    // (BAT: from row -hi on, too)
+                    const bool in = bfirst == 0 && (BAT ? inb(row1 + r + 1, 0) : row1 + r + 1 <= -blo);
                     hl[r] = in ? hl[r] : SENT;
                     el[r] = in ? el[r] : SENT;
                 }
@@ -312,14 +360,22 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             if constexpr (ENDS) upprev = epb ? 0 : upprev;
             if constexpr (BAND)
             {
-                if (bfirst == 0) upprev = row1 <= -blo ? upprev : SENT;
+                if (bfirst == 0) upprev = (BAT ? inb(row1, 0) : row1 <= -blo) ? upprev : SENT;
                 else
                 {
                     // the cell left of the window in the row above: out of band for every lane but 0,
                     // whose row above is the previous strip's last and may have its band edge there
                     const int col = 64 * bfirst;  // >= 64 and < n; the previous strip's window holds it
                     const bool in = lane == 0 && (uint32_t)(col - row1 - blo) <= bspan;
-                    upprev = in ? rowbuf[col - 1].x : SENT;
+                    if constexpr (BAT)
+                    {
+                        // a band with lo > 0 starts strip 0 past body 0: the row above is the border
+                        // H[0][col]. After an empty strip `in` is false: its last row holds no in-band column
+                        int v = SENT;
+                        if (in) v = s == 0 ? (LOCAL || etb ? 0 : -gapc(col)) : rowbuf[col - 1].x;
+                        upprev = v;
+                    }
+                    else upprev = in ? rowbuf[col - 1].x : SENT;
                 }
             }
             int tl = 0, tfeed = 0, feed = 0, ofeed = 0;
@@ -526,7 +582,9 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 for (int r = 0; r < R; ++r)
                 {
                     const int row = row1 + r + 1;
-                    const bool better = row <= m && hl[r] > pebest;
+                    // BAT: hl[r] is H[row][n] only where (row, n) is in band: the strip's window then reached
+                    // column n; an empty strip and one that ends left of n fold nothing
+                    const bool better = row <= m && (!BAT || inb(row, n)) && hl[r] > pebest;
                     pebest = better ? hl[r] : pebest;
                     perow = better ? row : perow;
                 }
@@ -577,18 +635,30 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             // it is no smaller and lies above row m (it is then at least H[m][n]); a border candidate,
             // (0, n) before (m, 0), wins only when it is strictly greater
             int bv = res.score;
+            if constexpr (BAT)
+            {
+                // only in-band candidates count; the planner admitted the pair, so one of them does, and
+                // in such a pair every in-band cell, border cells included, holds a real score (it lies
+                // on a diagonal that starts in a permitted, in-band border cell). Row m: the running
+                // best took the sentinel of an out-of-band column only until a real value came, which
+                // is above -2^29 under the planner's limit and never ties it; a row m without an in-band
+                // column in 1..n (or a last strip that ran no body) leaves something below. TE unset:
+                // hl is H[m][n] only if (m, n) is in band
+                const bool rowm = FIT ? bv > -(1 << 29) : inb(m, n);
+                bv = rowm ? bv : SENT;
+            }
             if (epe)
             {
                 const uint64_t key = wave_max_u64(((uint64_t)(uint32_t)(pebest + (1 << 30)) << 32) | (uint64_t)~(uint32_t)perow);
                 const int vc = (int)(uint32_t)(key >> 32) - (1 << 30), rc = (int)~(uint32_t)key;
-                if (vc >= bv && rc < m)
+                if ((!BAT || vc > SENT) && vc >= bv && rc < m)  // BAT: no fold at all leaves the start value
                 {
                     bv = vc;
                     res.end_pattern = (uint64_t)rc;
                     res.end_text = (uint64_t)n;
                 }
                 const int h0n = etb ? 0 : -gapc(n);
-                if (h0n > bv)
+                if ((!BAT || inb(0, n)) && h0n > bv)
                 {
                     bv = h0n;
                     res.end_pattern = 0;
@@ -598,7 +668,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             if constexpr (FIT)
             {
                 const int hm0 = epb ? 0 : -gapc(m);
-                if (hm0 > bv)
+                if ((!BAT || inb(m, 0)) && hm0 > bv)
                 {
                     bv = hm0;
                     res.end_pattern = (uint64_t)m;

@@ -18,7 +18,8 @@ uint64_t trace_arena_budget()
 }
 
 int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
-                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err, const int32_t *band)
+                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err, const int32_t *band,
+                    const sa_band *bands)
 {
     if (!out)
     {
@@ -34,7 +35,7 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
     // SA_SCORE_WAVES is tuned for the untraced kernels: here it may lower the grid, not raise it past
     // what the traced instances' registers admit
     k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
-    if (int rc = make_score_plan(P, pairs, np, num_cu, k8, &pl.score, err, &gapm, band)) return rc;
+    if (int rc = make_score_plan(P, pairs, np, num_cu, k8, &pl.score, err, &gapm, band, bands)) return rc;
     pl.budget = budget;
     pl.dir_bytes.resize((size_t)np);
     pl.dir_off.resize((size_t)np);
@@ -42,7 +43,9 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
     for (int64_t p = 0; p < np; ++p)
     {
         const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
-        pl.dir_bytes[p] = band ? trace_band_dir_bytes(n, m, *band) : trace_dir_bytes(n, m);
+        pl.dir_bytes[p] = bands  ? trace_band_at_dir_bytes(n, m, pl.score.bands[p])
+                          : band ? trace_band_dir_bytes(n, m, *band)
+                                 : trace_dir_bytes(n, m);
         pl.total_dir_bytes += pl.dir_bytes[p];
         pl.slot_off[p] = pl.string_bytes;
         pl.string_bytes += n + m;

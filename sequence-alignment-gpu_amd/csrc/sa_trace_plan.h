@@ -56,6 +56,21 @@ inline uint64_t trace_band_dir_bytes(uint64_t n, uint64_t m, int64_t band)
     return words * 4;
 }
 
+// The same for a band of the caller's (any lo <= hi, clipped: band_clip): band_window_at, whose empty
+// strips store nothing. On the bands of band_of both give the figures above.
+SA_BAND_FN uint64_t trace_band_at_strip_words(int64_t n, int64_t m, int64_t s, Band bd)
+{
+    const BandWindow bw = band_window_at(n, m, (int64_t)kTraceStripRows, s, bd);
+    return (uint64_t)(bw.b1 - bw.b0) * (64 * 64);
+}
+inline uint64_t trace_band_at_dir_bytes(uint64_t n, uint64_t m, Band bd)
+{
+    if (n == 0 || m == 0) return 0;
+    uint64_t words = 0;
+    for (uint64_t s = 0; s < trace_strips(m); ++s) words += trace_band_at_strip_words((int64_t)n, (int64_t)m, (int64_t)s, bd);
+    return words * 4;
+}
+
 struct TracePlan {
     ScorePlan score;                  // validation, work order, key bits, grid and boundary rows (R = 8, affine)
     uint64_t budget = 0;              // direction bytes one chunk may hold
@@ -73,8 +88,10 @@ struct TracePlan {
 // for the affine gap model, or SA_ERR_UNSUPPORTED for a pair whose directions exceed `budget`.
 // `band` non-null: the banded aligner; a pair's directions are its band's (trace_band_dir_bytes), the
 // chunks are cut by them, and a pair is refused only when its band exceeds the budget.
+// `bands` non-null (and `band` null): the band-at aligner, bands[p] the band of pair p
+// (make_score_plan's checks; trace_band_at_dir_bytes of the clipped band).
 int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
                     int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err,
-                    const int32_t *band = nullptr);
+                    const int32_t *band = nullptr, const sa_band *bands = nullptr);
 
 }  // namespace sa

@@ -37,7 +37,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_batch_last_stats", "sa_plan_fill_kind", "sa_score_batch", "sa_scorer_create", "sa_scorer_run",
            "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search", "sa_score_batch_affine",
            "sa_scorer_create_affine", "sa_align_pairs_affine", "sa_search_affine", "sa_affine_last_stats",
-           "sa_score_batch_banded", "sa_scorer_create_banded", "sa_align_pairs_banded")
+           "sa_score_batch_banded", "sa_scorer_create_banded", "sa_align_pairs_banded",
+           "sa_score_batch_band_at", "sa_scorer_create_band_at", "sa_align_pairs_band_at", "sa_band_reachable")
 
 
 class SaParams(ctypes.Structure):
@@ -58,6 +59,10 @@ class SaResult(ctypes.Structure):
 class SaScoreResult(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("end_text", ctypes.c_uint64),
                 ("end_pattern", ctypes.c_uint64)]
+
+
+class SaBand(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_int32), ("hi", ctypes.c_int32)]
 
 
 class SaError(RuntimeError):
@@ -130,6 +135,13 @@ def _load():
                                           ctypes.POINTER(P)]
     L.sa_align_pairs_banded.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.c_int64, I,
                                         ctypes.POINTER(SaResult), P, P]
+    L.sa_score_batch_band_at.argtypes = [ctypes.POINTER(SaParams), I32, I32, P, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_band_at.argtypes = [ctypes.POINTER(SaParams), I32, I32, P, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                           ctypes.POINTER(P)]
+    L.sa_align_pairs_band_at.argtypes = [ctypes.POINTER(SaParams), I32, I32, P, P, ctypes.c_int64, I,
+                                         ctypes.POINTER(SaResult), P, P]
+    L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
+    L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_int32)]
     for name in EXPORTS:
@@ -176,6 +188,24 @@ def ends_free(text_begin: bool = False, text_end: bool = False, pattern_begin: b
     four is OVERLAP, the text's two is FIT, none is global alignment."""
     return (ENDS_FREE | (FREE_TEXT_BEGIN if text_begin else 0) | (FREE_TEXT_END if text_end else 0) |
             (FREE_PATTERN_BEGIN if pattern_begin else 0) | (FREE_PATTERN_END if pattern_end else 0))
+
+
+def _bands(bands, num_pairs: int) -> np.ndarray:
+    """`bands` as the (num_pairs, 2) int32 array of sa_band the band-at functions take."""
+    b = np.ascontiguousarray(bands, dtype=np.int32).reshape(-1, 2)
+    if len(b) != num_pairs:
+        raise ValueError(f"bands holds {len(b)} (lo, hi) pairs for {num_pairs} pairs")
+    return b
+
+
+def band_reachable(mode: int, n: int, m: int, lo: int, hi: int) -> bool:
+    """sa_band_reachable (host only, no device call): whether a pair of n text and m pattern letters has
+    an alignment of `mode` inside the band lo <= j - i <= hi. The band-at functions (bands=) refuse a
+    call that holds a pair without one: filter with this first."""
+    r = lib.sa_band_reachable(mode, n, m, SaBand(lo, hi))
+    if r < 0:
+        raise SaError(1, "sa_band_reachable: bad mode")
+    return bool(r)
 
 
 def selftest(device: int = 0) -> None:
@@ -238,14 +268,19 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
-                       gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None) -> list[dict]:
+                       gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None,
+                       bands=None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
     ones. With gap_open == gap_extend == g every value is align_pair's for gap g. `mode` may also be FIT
     or an ends-free mode (ends_free(), OVERLAP): start_text and start_pattern are then the 0-based
     indices of the first aligned letters. With `band` (SA_GLOBAL and SA_LOCAL only),
-    sa_align_pairs_banded: the alignment inside the diagonal band of that half-width (sa_hip.h)."""
-    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band)
+    sa_align_pairs_banded: the alignment inside the diagonal band of that half-width (sa_hip.h). With
+    `bands` (an (np, 2) int32 array or a list of (lo, hi), one per pair; not with `band`),
+    sa_align_pairs_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode."""
+    if band is not None and bands is not None:
+        raise ValueError("band= and bands= exclude each other")
+    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band, bands)
 
 
 def affine_last_stats() -> dict:
@@ -256,7 +291,8 @@ def affine_last_stats() -> dict:
     return {"fill_ms": f.value, "walk_ms": w.value, "arena_bytes": b.value, "num_chunks": c.value}
 
 
-def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings, band=None) -> list[dict]:
+def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings, band=None,
+                      bands=None) -> list[dict]:
     """align_batch (gap_extend None) and align_pairs_affine (with `band`, sa_align_pairs_banded): one
     packing of the host pairs and buffers."""
     p, S_keep, alpha_keep = _params(mode, S, gap, alphabet, 0)
@@ -271,6 +307,9 @@ def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, devic
     res = (SaResult * max(1, n))()
     if gap_extend is None:
         _check(lib.sa_align_batch(ctypes.byref(p), hp, n, num_gpus, res, at, ap))
+    elif bands is not None:
+        b = _bands(bands, n)
+        _check(lib.sa_align_pairs_band_at(ctypes.byref(p), gap, gap_extend, b.ctypes.data, hp, n, device, res, at, ap))
     elif band is None:
         _check(lib.sa_align_pairs_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, res, at, ap))
     else:
@@ -375,21 +414,30 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
-                device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None) -> np.ndarray:
+                device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
+                bands=None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
     the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
     sa_score_batch_banded: the scores inside the diagonal band of that half-width (sa_hip.h); without
     `gap_extend` the gap is linear, gap_open = gap_extend = gap. `mode` is SA_GLOBAL, SA_LOCAL, FIT or
     an ends-free mode (ends_free(), OVERLAP; not with `band`): end_pattern and end_text are the cell the
-    score is read from."""
+    score is read from. With `bands` (an (np, 2) int32 array or a list of (lo, hi), one per pair; not with
+    `band`), sa_score_batch_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode; a pair
+    without an alignment in its band fails the call (band_reachable)."""
+    if band is not None and bands is not None:
+        raise ValueError("band= and bands= exclude each other")
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
     n = len(ts)
     hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
     out = np.zeros(max(1, n), SCORE_DTYPE)
-    if band is not None:
+    if bands is not None:
+        b = _bands(bands, n)
+        _check(lib.sa_score_batch_band_at(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, b.ctypes.data, hp, n,
+                                          device, out.ctypes.data))
+    elif band is not None:
         _check(lib.sa_score_batch_banded(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, band, hp, n,
                                          device, out.ctypes.data))
     elif gap_extend is None:
@@ -402,18 +450,26 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 class Scorer:
     """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback).
     With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty. With
-    `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear). `mode` as
+    `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear). With
+    `bands`, one (lo, hi) per pair, a band-at scorer (sa_scorer_create_band_at; not with `band`). `mode` as
     score_batch takes it."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
-                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None):
+                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
+                 bands=None):
+        if band is not None and bands is not None:
+            raise ValueError("band= and bands= exclude each other")
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)
         self.pairs = pairs
         self.device = device
         h = ctypes.c_void_p()
-        if band is not None:
+        if bands is not None:
+            b = _bands(bands, len(pairs))
+            _check(lib.sa_scorer_create_band_at(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend,
+                                                b.ctypes.data, arr, len(pairs), device, ctypes.byref(h)))
+        elif band is not None:
             _check(lib.sa_scorer_create_banded(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, band,
                                                arr, len(pairs), device, ctypes.byref(h)))
         elif gap_extend is None:

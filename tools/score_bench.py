@@ -138,6 +138,24 @@ def mapping_workload(small: bool) -> dict:
             "pairs": [(int(to[k]), int(nl[k]), int(po[k]), int(ml[k])) for k in range(npairs)]}
 
 
+def mapped_workload(small: bool) -> dict:
+    """The shapes of mapping_workload with every read mutated on its own, so that read k does start at
+    letter at[k] of its window: mapping_workload mutates the concatenated reads, whose deletions shift all
+    later reads off their windows, which no band around at[k] would survive."""
+    from sa_amd import synthetic
+    npairs = 4000 if small else 40000
+    rng = np.random.default_rng(13)
+    nl, ml = rng.integers(450, 751, npairs), rng.integers(140, 161, npairs)
+    to, po = np.concatenate([[0], np.cumsum(nl)]), np.concatenate([[0], np.cumsum(ml)])
+    text = synthetic.random_sequence(5, int(to[-1]), 4)
+    at = rng.integers(0, nl - ml + 1)
+    # a piece 16 letters longer than the read where the window has them: about 5 % of it is deleted
+    pattern = np.concatenate([synthetic.mutate(text[to[k] + at[k]:min(to[k] + at[k] + ml[k] + 16, to[k + 1])], 600 + k, 4, int(ml[k]))
+                              for k in range(npairs)])
+    return {"name": "mapped", "S": synthetic.blast_matrix(), "text": text, "pattern": pattern, "at": at,
+            "pairs": [(int(to[k]), int(nl[k]), int(po[k]), int(ml[k])) for k in range(npairs)]}
+
+
 MODES = {"global": 0, "local": 1, "fit": 2}
 
 
@@ -293,6 +311,72 @@ def band_rows(args, engine, w, dt, dp) -> dict:
         same = sum(g == f for g, f in zip(got[k], got["unbanded"]))
         row["aligned"][k] = {"fill": stats(v["fill_ms"]), "walk": stats(v["walk_ms"]), "end_to_end_wall": stats(v["wall_ms"]),
                              "arena_bytes": v["arena_bytes"], "num_chunks": v["num_chunks"], "alignments_equal_to_unbanded": same}
+    return row
+
+
+def band_at_model_cost(pairs, bands, R: int) -> int:
+    """The planner's instruction count of the band-at fit scorer (sa_score_plan.h: band_window_at): the
+    affine fit step, charged jmax - jmin + 64 times per strip that holds an in-band cell."""
+    step, rows, total = 18 + 4 + R * 11, 64 * R, 0
+    for (_, n, _, m), (lo, hi) in zip(pairs, bands):
+        lo, hi = max(lo, -m), min(hi, n)
+        for first in range(1, m + 1, rows):
+            ia, ib = max(first, 1 - hi), min(m, first + rows - 1, n - lo)
+            if ia <= ib:
+                total += (min(n, ib + hi) - max(1, ia + lo) + 64) * step
+    return total
+
+
+def fit_path_diagonals(res) -> tuple[int, int]:
+    """The lowest and highest j - i over the cells of a fit alignment: it starts at (0, start_text)."""
+    d = lo = hi = int(res["start_text"])
+    for a, b in zip(res["aligned_text"], res["aligned_pattern"]):
+        d += (a != "-") - (b != "-")
+        lo, hi = min(lo, d), max(hi, d)
+    return lo, hi
+
+
+def mapped_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
+    """Fit scoring of the mapped workload inside the band [at - w, at + w] of each read's true offset,
+    w = 16 and 64, beside the unbanded fit scorer of the same gap model, alternated."""
+    pairs, cells, affine = w["pairs"], sum(p[1] * p[3] for p in w["pairs"]), gap_extend is not None
+    bands = {b: [(int(a) - b, int(a) + b) for a in w["at"]] for b in (16, 64)}
+    sc = {"fit": engine.Scorer(2, w["S"], gap, pairs, gap_extend=gap_extend)}
+    for b in bands:
+        sc[f"band_at_{b}"] = engine.Scorer(2, w["S"], gap, pairs, gap_extend=gap_extend, bands=bands[b])
+    row = {"name": w["name"] + ("_affine" if affine else "_linear"), "pairs": len(pairs), "cells": cells, "gap": gap,
+           "gap_extend": gap_extend, "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for _ in range(2):  # warm-up
+        for k, s in sc.items():
+            s.run(dt.data_ptr(), dp.data_ptr())
+            res[k] = s.results()
+    # a subsample aligned without a band: where its path lies inside the band the scores are equal
+    sub = list(range(0, len(pairs), max(1, len(pairs) // 400)))
+    texts = [w["text"][pairs[k][0]:pairs[k][0] + pairs[k][1]] for k in sub]
+    pats = [w["pattern"][pairs[k][2]:pairs[k][2] + pairs[k][3]] for k in sub]
+    full = engine.align_pairs_affine(2, texts, pats, w["S"], gap, gap if gap_extend is None else gap_extend)
+    assert [f["score"] for f in full] == res["fit"]["score"][sub].tolist(), "the fit scorer and aligner differ"
+    diags = [fit_path_diagonals(f) for f in full]
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            ms[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    fit_model = model_cost(pairs, row["scorers"]["fit"]["rows_per_lane"], False, affine, True)
+    row["fit_run"] = stats(ms["fit"])
+    row["bands"] = {}
+    for b in bands:
+        k = f"band_at_{b}"
+        assert (res[k]["score"] <= res["fit"]["score"]).all(), f"band {b}: a banded score exceeds the unbanded one"
+        free = [i for i, (pr, (dlo, dhi)) in enumerate(zip(sub, diags)) if bands[b][pr][0] <= dlo and dhi <= bands[b][pr][1]]
+        assert all(res[k]["score"][sub[i]] == full[i]["score"] for i in free), f"band {b}: scores differ where the band does not bind"
+        model = band_at_model_cost(pairs, bands[b], row["scorers"][k]["rows_per_lane"])
+        row["bands"][str(b)] = dict(stats(ms[k]), subsample=len(sub), subsample_band_does_not_bind=len(free),
+                                    pairs_with_the_unbanded_score=int((res[k]["score"] == res["fit"]["score"]).sum()),
+                                    banded_over_fit=round(med[k] / med["fit"], 4), model_banded_over_fit=round(model / fit_model, 4))
+    for s in sc.values():
+        s.close()
     return row
 
 
@@ -467,9 +551,11 @@ def main() -> int:
     ap.add_argument("--gap-open", type=int, default=11, help="gap-open penalty of the affine scorer")
     ap.add_argument("--hits", type=int, default=None,
                     help="time search(k=HITS) on the search workload; with --gap-extend also its traced fill and its walk")
-    ap.add_argument("--mode", choices=["fit", "ends"], default=None,
+    ap.add_argument("--mode", choices=["fit", "ends", "mapped"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
-                         "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload")
+                         "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload; "
+                         "mapped: the band-at fit scorer around each read's true offset against the unbanded fit scorer "
+                         "(profiles/r16/score_mapped_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--tree", default=None,
@@ -478,7 +564,8 @@ def main() -> int:
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
-                                                    ("r15", "score_ends_bench.json") if args.mode == "ends" else ("r09", "score_bench.json")))
+                                                    ("r15", "score_ends_bench.json") if args.mode == "ends" else
+                                                    ("r16", "score_mapped_bench.json") if args.mode == "mapped" else ("r09", "score_bench.json")))
     if args.tree:
         sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
@@ -506,6 +593,14 @@ def main() -> int:
         row = fit_hits_row(args, engine, next(workloads(args.small, search_only=True)))
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
+    elif args.mode == "mapped":
+        w = mapped_workload(args.small)
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        for gap, ge in ((5, None), (args.gap_open, args.gap_extend if args.gap_extend is not None else 2)):
+            row = mapped_rows(args, engine, w, dt, dp, gap, ge)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+        del dt, dp
     elif args.mode == "ends":
         report["library_build_id"] = engine.lib.sa_build_id().decode()
         for w in (mapping_workload(args.small), overlap_workload(args.small)):
