@@ -196,6 +196,19 @@ uint64_t scoreSequencesGPUBandAt(const Request *requests, uint64_t numRequests, 
 uint64_t alignSequencesGPUBandAt(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                  int gapOpen, int gapExtend, int freeEnds, const int *bandLo, const int *bandHi);
 
+/// Extension: extension alignment (sa_score_batch_extend, sa_align_pairs_extend; sa_hip.h has the
+/// definition): the alignment starts at the first letters of both sequences (the end of a seed), ends at
+/// the best-scoring cell, and rows after the first one whose best lies more than xdrop below the best seen
+/// count for nothing; xdrop -1 (SA_NO_XDROP) never stops. Request::alignmentType and Request::gapPenalty are
+/// ignored: a caller with a linear gap passes its penalty as gapOpen and gapExtend. One alphabet and score
+/// matrix for all requests. Response::startInAlignedText and startInAlignedPattern are 0; the aligned
+/// strings without their gap letters are the prefixes of text and pattern the extension covers. Returns 0,
+/// or 1 with the message on stdout.
+uint64_t scoreSequencesGPUExtend(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                 int xdrop, int *scores);
+uint64_t alignSequencesGPUExtend(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                 int gapOpen, int gapExtend, int xdrop);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

@@ -413,8 +413,53 @@ int sa_align_pairs_band_at(const sa_params *params, int32_t gap_open, int32_t ga
                            char *const *aligned_text, char *const *aligned_pattern);
 int sa_band_reachable(int32_t mode, uint64_t text_len, uint64_t pattern_len, sa_band band);
 
+/* ---- extension alignment: anchored start, best cell anywhere, row X-drop ---------------------- */
+
+/* The alignment starts at the origin (the end of a seed), ends at whichever cell scores best, and the
+ * fill stops once a row's best has dropped more than xdrop below the best seen: the primitive of
+ * seed-and-extend mapping. H, E and F are Gotoh's matrices as sa_score_batch_affine states them, with
+ * global borders and no clamp: H[0][0] = 0, H[0][j] = -gap(j), H[i][0] = -gap(i),
+ * gap(k) = gap_open + (k - 1) gap_extend. For n >= 1 and m >= 1:
+ *   row maxima:   r(i) = max over 1 <= j <= n of H[i][j], i = 1..m
+ *   running best: B(0) = 0 (the origin, the empty extension), B(i) = max(B(i - 1), r(i))
+ *   stop row i*:  with xdrop = X >= 0 the smallest i in 1..m with B(i - 1) - r(i) > X; with
+ *                 xdrop = SA_NO_XDROP, or when no row qualifies, i* = m + 1
+ *   result:       over the interior cells (i, j), 1 <= i < i*, 1 <= j <= n: if their maximum is > 0 it is
+ *                 the score and end_pattern, end_text its first cell in row-major order; otherwise the
+ *                 score is 0 at (0, 0) with an empty alignment (the rule local has). Border cells are
+ *                 never candidates
+ *   walk:         from the result cell in state H, with the tie rules of DESIGN.md 3.5, to the origin;
+ *                 row 0 forces LEFT and column 0 forces TOP
+ *   strings:      start_text = start_pattern = 0 without quirks, for the empty alignment too.
+ *                 aligned_text without its gap letters is text[0 : end_text], aligned_pattern without
+ *                 them pattern[0 : end_pattern]; sa_result carries no end cell, it follows from the
+ *                 strings (the scorers report it)
+ *   empty:        n == 0 or m == 0 scores 0 at (0, 0) with an empty alignment
+ * The drop is defined on rows of the full, unpruned matrix: every cell of the rows < i* has its plain
+ * value, so no output depends on rows_per_lane, on the grid or on how much work the engine skips.
+ * Skipping rows >= i* is an optimisation; they count for nothing even if the score recovers there.
+ * Identities: (I1) the score and both strings equal those of sa_align_pairs_affine in SA_GLOBAL mode on
+ * text[:end_text], pattern[:end_pattern]. (I2) The score is non-decreasing in X, and X = 2^30 - 1 gives
+ * every output of SA_NO_XDROP (under the score limit no difference B - r reaches 2^30). (I3) Under
+ * non-negative penalties the SA_NO_XDROP score is >= max(0, the score of SA_ENDS_FREE | TE | PE).
+ * (I4) gap_open == gap_extend == g is the linear recurrence of gap penalty g, and the scorers then run
+ * the linear kernels. Extending to the left of a seed is the same call on both sequences reversed.
+ * params->mode must be SA_GLOBAL (the borders are global's), else SA_ERR_INVALID; xdrop < -1 or
+ * xdrop >= 2^30 is SA_ERR_INVALID. One xdrop serves all pairs of a call. The limits are those of the
+ * unbanded affine functions and of local mode's best-cell key (SA_ERR_UNSUPPORTED). There is no band.
+ * The scorer is an ordinary sa_scorer. sa_align_pairs_extend plans a pair with the direction bytes of a
+ * global pair and chunks as sa_align_pairs_affine does; sa_affine_last_stats reports the call. */
+#define SA_NO_XDROP (-1)
+int sa_score_batch_extend(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop,
+                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_score_result *out);
+int sa_scorer_create_extend(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop,
+                            const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_align_pairs_extend(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop,
+                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                          char *const *aligned_text, char *const *aligned_pattern);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
- * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at or sa_search_affine (k > 0): device
+ * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

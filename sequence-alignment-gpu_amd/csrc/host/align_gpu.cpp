@@ -201,21 +201,24 @@ namespace
 // scoreSequencesGPU, scoreSequencesGPUAffine and scoreSequencesGPUBanded: `gap` null is the requests'
 // linear gapPenalty, else {gap open, gap extend} and gapPenalty is ignored; `band` non-null is the
 // band's half-width; `ends` non-null is scoreSequencesGPUEndsFree with these flags; `lo` and `hi` non-null
-// are scoreSequencesGPUBandAt's per-request bands
+// are scoreSequencesGPUBandAt's per-request bands; `xdrop` non-null is scoreSequencesGPUExtend (the mode is
+// SA_GLOBAL, whose borders an extension has, and Request::alignmentType is ignored)
 uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
                        int *scores, const char *name, const int *band = nullptr, const int *ends = nullptr,
-                       const int *lo = nullptr, const int *hi = nullptr)
+                       const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
     std::vector<sa_host_pair> pairs(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
-        if (!toParams(requests[i], &params[i], true, ends))
+        const int none = 0;
+        if (!toParams(requests[i], &params[i], true, xdrop ? &none : ends))
         {
             std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
             return 1;
         }
+        if (xdrop) params[i].mode = SA_GLOBAL;
         if (gap) params[i].gap_penalty = 0;
         if (!sameScheme(params[0], params[i]))
         {
@@ -228,7 +231,8 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
     std::vector<sa_score_result> res(numRequests);
     std::vector<sa_band> bands;
     for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
-    const int rc = lo   ? sa_score_batch_band_at(&params[0], gap[0], gap[1], bands.data(), pairs.data(), (int64_t)numRequests, device, res.data())
+    const int rc = xdrop ? sa_score_batch_extend(&params[0], gap[0], gap[1], *xdrop, pairs.data(), (int64_t)numRequests, device, res.data())
+                   : lo ? sa_score_batch_band_at(&params[0], gap[0], gap[1], bands.data(), pairs.data(), (int64_t)numRequests, device, res.data())
                    : band ? sa_score_batch_banded(&params[0], gap[0], gap[1], *band, pairs.data(), (int64_t)numRequests, device, res.data())
                    : gap ? sa_score_batch_affine(&params[0], gap[0], gap[1], pairs.data(), (int64_t)numRequests, device, res.data())
                          : sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
@@ -242,10 +246,10 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
 }
 
 // alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded; with `ends`, alignSequencesGPUEndsFree;
-// with `lo` and `hi`, alignSequencesGPUBandAt
+// with `lo` and `hi`, alignSequencesGPUBandAt; with `xdrop`, alignSequencesGPUExtend
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
                        int device, int gapOpen, int gapExtend, const int *band, const std::string &name,
-                       const int *ends = nullptr, const int *lo = nullptr, const int *hi = nullptr);
+                       const int *ends = nullptr, const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr);
 
 // the mode argument of the band-at functions: -1 leaves the mode to Request::alignmentType
 bool bandAtArgsOk(int freeEnds, const int *lo, const int *hi, uint64_t numRequests, const char *name)
@@ -274,6 +278,20 @@ uint64_t SequenceAlignment::alignSequencesGPUBandAt(const Request *requests, Res
     if (!bandAtArgsOk(freeEnds, bandLo, bandHi, numRequests, "alignSequencesGPUBandAt")) return 1;
     return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUBandAt",
                          freeEnds < 0 ? nullptr : &freeEnds, bandLo, bandHi);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUExtend(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                    int gapExtend, int xdrop, int *scores)
+{
+    const int gap[2] = {gapOpen, gapExtend};
+    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUExtend", nullptr, nullptr, nullptr, nullptr, &xdrop);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUExtend(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                                    int gapOpen, int gapExtend, int xdrop)
+{
+    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUExtend", nullptr, nullptr,
+                         nullptr, &xdrop);
 }
 
 uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
@@ -326,7 +344,7 @@ namespace
 {
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
                        int device, int gapOpen, int gapExtend, const int *band, const std::string &name, const int *ends,
-                       const int *lo, const int *hi)
+                       const int *lo, const int *hi, const int *xdrop)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -334,11 +352,13 @@ uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlign
     std::vector<char *> at(numRequests), ap(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
-        if (!toParams(requests[i], &params[i], true, ends))
+        const int none = 0;
+        if (!toParams(requests[i], &params[i], true, xdrop ? &none : ends))
         {
             std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
             return 1;
         }
+        if (xdrop) params[i].mode = SA_GLOBAL;
         params[i].gap_penalty = 0;
         if (!sameScheme(params[0], params[i]))
         {
@@ -354,7 +374,9 @@ uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlign
     std::vector<sa_result> res(numRequests);
     std::vector<sa_band> bands;
     for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
-    const int rc = lo   ? sa_align_pairs_band_at(&params[0], gapOpen, gapExtend, bands.data(), pairs.data(), (int64_t)numRequests, device,
+    const int rc = xdrop ? sa_align_pairs_extend(&params[0], gapOpen, gapExtend, *xdrop, pairs.data(), (int64_t)numRequests, device,
+                                                 res.data(), at.data(), ap.data())
+                   : lo ? sa_align_pairs_band_at(&params[0], gapOpen, gapExtend, bands.data(), pairs.data(), (int64_t)numRequests, device,
                                                  res.data(), at.data(), ap.data())
                    : band ? sa_align_pairs_banded(&params[0], gapOpen, gapExtend, *band, pairs.data(), (int64_t)numRequests, device,
                                                 res.data(), at.data(), ap.data())

@@ -2,13 +2,15 @@
 // GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
 // the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
 //   sa_score_plan_check --mode global|local|fit|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
-//                       [--gap-extend E] [--band W | --band-at LO:HI] [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--gap-extend E] [--band W | --band-at LO:HI] [--extend X|none] [--match M --mismatch X] NxM[xCOUNT] ...
 // With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty. With --band W
 // it is the banded scorer's (sa_hip.h), and the plan also prints band_cells and, for the first 8
 // pairs, "bands": lo, hi, the pair's band cells and the [jmin, jmax, b0, b1] window of every strip at
 // the plan's R. With --band-at LO:HI it is the band-at scorer's, the one band applied to every pair, with
 // the same output ("band" is -1, lo and hi are the clipped limits, an empty strip's window is
 // [1, 0, 0, 0]).
+// With --extend X it is the extension scorer's (sa_score_batch_extend; "none" is SA_NO_XDROP), which takes
+// --gap-extend and prints "extend": true and "xdrop".
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -32,6 +34,8 @@ int main(int argc, char **argv)
     bool affine = false, banded = false, band_at = false;
     int32_t band = 0;
     sa_band at = {0, 0};
+    bool extend = false;
+    int32_t xdrop = SA_NO_XDROP;
     ScoreGap gapm = {0, 0};
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
@@ -67,6 +71,12 @@ int main(int argc, char **argv)
             at.lo = lo;
             at.hi = hi;
         }
+        else if (a == "--extend")
+        {
+            extend = true;
+            const std::string v = value();
+            xdrop = v == "none" ? SA_NO_XDROP : std::atoi(v.c_str());
+        }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
         else if (a == "--match") match = std::atoi(value());
@@ -96,11 +106,12 @@ int main(int argc, char **argv)
     P.score_matrix = S.data();
 
     gapm.open = P.gap_penalty;
+    const ScoreExtend ext = {xdrop, false};
     ScorePlan pl;
     std::string err;
     const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
     const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr,
-                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr);
+                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr, extend ? &ext : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -117,6 +128,7 @@ int main(int argc, char **argv)
     // the order of a large batch is long: the first 64 entries
     for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
     std::printf("]");
+    if (extend) std::printf(", \"extend\": true, \"xdrop\": %d", pl.xdrop);
     if (banded || band_at)
     {
         std::printf(", \"band\": %d, \"band_cells\": %llu, \"bands\": [", pl.band, (unsigned long long)pl.band_cells);

@@ -2,11 +2,12 @@
 // stand-alone program. No GPU, no ROCm: it plans the pair shapes on its command line and prints the
 // plan as one JSON object (tests/test_trace_plan.py).
 //   sa_trace_plan_check --mode global|local|fit|<int> --alphabet A --gap G --gap-extend E --cus N
-//                       [--budget BYTES] [--band W | --band-at LO:HI] [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--budget BYTES] [--band W | --band-at LO:HI] [--extend X|none] [--match M --mismatch X] NxM[xCOUNT] ...
 // --gap is the gap-open penalty. With --band W the plan is the banded aligner's (sa_hip.h): dir_bytes
 // are the band's, "steps" is the sum of the strips' window steps, and each pair also lists the
 // [b0, b1] bodies of its strips' windows (the first 64 strips). With --band-at LO:HI it is the band-at
 // aligner's, the one band applied to every pair, with the same output (an empty strip's window is [0, 0]). Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
+// With --extend X it is the extension aligner's (sa_align_pairs_extend; "none" is SA_NO_XDROP).
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -30,6 +31,8 @@ int main(int argc, char **argv)
     bool banded = false, band_at = false;
     int32_t band = 0;
     sa_band at = {0, 0};
+    bool extend = false;
+    int32_t xdrop = SA_NO_XDROP;
     std::vector<sa_pair> pairs;
     for (int i = 1; i < argc; ++i)
     {
@@ -43,6 +46,12 @@ int main(int argc, char **argv)
         else if (a == "--alphabet") P.alphabet_size = std::atoi(value());
         else if (a == "--gap") go = std::atoi(value());
         else if (a == "--gap-extend") ge = std::atoi(value());
+        else if (a == "--extend")
+        {
+            extend = true;
+            const std::string v = value();
+            xdrop = v == "none" ? SA_NO_XDROP : std::atoi(v.c_str());
+        }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--budget") budget = std::strtoull(value(), nullptr, 10);
         else if (a == "--band")
@@ -92,7 +101,7 @@ int main(int argc, char **argv)
     std::string err;
     const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
     const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err,
-                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr);
+                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr, extend ? &xdrop : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());

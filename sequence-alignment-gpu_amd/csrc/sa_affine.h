@@ -12,10 +12,11 @@ namespace sa {
 // (sa_trace_plan.h), on the null stream; synchronous. results: np entries. aligned_text /
 // aligned_pattern: both null, or np host buffers of at least text_len + pattern_len bytes each.
 // `band` non-null: inside the diagonal band of that half-width (sa_align_pairs_banded). `with_bands`:
-// inside bands[p] for pair p (sa_align_pairs_band_at; null bands with pairs is SA_ERR_INVALID).
+// inside bands[p] for pair p (sa_align_pairs_band_at; null bands with pairs is SA_ERR_INVALID). `xdrop`
+// non-null: extension alignment under that X-drop (sa_align_pairs_extend).
 int align_affine_device(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
                         int device, const void *d_text, const void *d_pattern, sa_result *results,
                         char *const *aligned_text, char *const *aligned_pattern, const int32_t *band = nullptr,
-                        bool with_bands = false, const sa_band *bands = nullptr);
+                        bool with_bands = false, const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
 
 }  // namespace sa

@@ -76,6 +76,21 @@ __global__ __launch_bounds__(64) void align_band_at_kernel(AlignBandAtArgs ba)
                                                                                   ba.bands);
 }
 
+// align_affine_kernel as extension alignment (sa_hip.h sa_align_pairs_extend; sa_score_wave.h: EXT): the
+// global nibbles; a fill that stops at its X-drop row stores no word below that row's strip
+struct AlignExtendArgs {
+    AlignAffineArgs a;
+    int32_t xdrop;
+};
+
+template <bool SMALL>
+__global__ __launch_bounds__(64) void align_extend_kernel(AlignExtendArgs xa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, kTraceRows, SA_GLOBAL, SMALL, true, false, false, false, true>(xa.a.sa.s, xa.a.sa.gap_extend, tab, xa.a.tr, 0, 0, nullptr,
+                                                                                    xa.xdrop);
+}
+
 struct WalkArgs {
     const int8_t *text, *pattern;
     const ScorePair *pairs;
@@ -301,9 +316,16 @@ struct Workspace {
     }
 };
 
-void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st, int band, const Band *bands)
+void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st, int band, const Band *bands,
+                  const int32_t *xdrop = nullptr)
 {
-    if (bands)  // SA_GLOBAL and SA_FIT as the ends-free modes they equal
+    if (xdrop)
+    {
+        const AlignExtendArgs xa = {a, *xdrop};
+        if (small) hipLaunchKernelGGL((align_extend_kernel<true>), dim3(grid), dim3(64), 0, st, xa);
+        else hipLaunchKernelGGL((align_extend_kernel<false>), dim3(grid), dim3(64), 0, st, xa);
+    }
+    else if (bands)  // SA_GLOBAL and SA_FIT as the ends-free modes they equal
     {
         const int fl = mode == SA_FIT ? SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END : mode & SA_ENDS_FREE ? mode & 15 : 0;
         const AlignBandAtArgs ba = {a, fl, bands};
@@ -372,7 +394,8 @@ void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipS
 
 int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa_pair *pairs, int64_t np, int device,
                             const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
-                            char *const *aligned_pattern, const int32_t *band, bool with_bands, const sa_band *bands)
+                            char *const *aligned_pattern, const int32_t *band, bool with_bands, const sa_band *bands,
+                            const int32_t *xdrop)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "affine aligner: null argument");
@@ -383,7 +406,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     TracePlan pl;
     std::string err;
-    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err, band, bands))
+    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err, band, bands, xdrop))
         return fail(rc, err);
     if (!P->alphabet) return fail(SA_ERR_INVALID, "affine aligner: params->alphabet is null");
     g_stats = AffineStats();
@@ -470,7 +493,8 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     wa.alphabet = d_alpha;
     wa.results = d_results;
     wa.A = A;
-    wa.mode = pl.score.mode;
+    // an extension walks as SA_ENDS_FREE with no flag: from the fill's result cell to the origin
+    wa.mode = xdrop ? SA_ENDS_FREE : pl.score.mode;
     wa.band = pl.score.band;
     wa.bands = d_bands;
     uint32_t ctrl[2] = {0, 0};
@@ -486,7 +510,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
             s.np = (int32_t)count;
             wa.order = s.order;
             HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, wa.band, d_bands);
+            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, wa.band, d_bands, xdrop);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
             if (d_bands) hipLaunchKernelGGL(walk_affine_kernel<2>, dim3((unsigned)count), dim3(64), 0, st, wa);
@@ -538,7 +562,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
 static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
                             const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
                             char *const *aligned_text, char *const *aligned_pattern, bool with_bands = false,
-                            const sa_band *bands = nullptr);
+                            const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
 
 extern "C" {
 
@@ -560,13 +584,21 @@ int sa_align_pairs_band_at(const sa_params *P, int32_t gap_open, int32_t gap_ext
     return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern, true, bands);
 }
 
+int sa_align_pairs_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_host_pair *pairs,
+                          int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern, false, nullptr,
+                            &xdrop);
+}
+
 }  // extern "C"
 
-// sa_align_pairs_affine and, with `band`, sa_align_pairs_banded, with `with_bands`, sa_align_pairs_band_at:
-// the host pairs packed into two arenas
+// sa_align_pairs_affine and, with `band`, sa_align_pairs_banded, with `with_bands`, sa_align_pairs_band_at, with
+// `xdrop`, sa_align_pairs_extend: the host pairs packed into two arenas
 static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
                             const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
-                            char *const *aligned_text, char *const *aligned_pattern, bool with_bands, const sa_band *bands)
+                            char *const *aligned_text, char *const *aligned_pattern, bool with_bands, const sa_band *bands,
+                            const int32_t *xdrop)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
@@ -594,7 +626,7 @@ static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_ex
     if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
     if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
     return align_affine_device(P, gap_open, gap_extend, dp.data(), np, device, dt.p, dpat.p, results, aligned_text,
-                               aligned_pattern, band, with_bands, bands);
+                               aligned_pattern, band, with_bands, bands, xdrop);
 }
 
 extern "C" {

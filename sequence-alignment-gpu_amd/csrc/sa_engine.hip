@@ -163,6 +163,7 @@ __global__ void selftest_kernel(int *out)
     for (int k = 0; k < 2000; ++k) __builtin_amdgcn_s_sleep(10);
     const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
     out[5 * 64 + lane] = (int)(t1 - t0);
+    out[6 * 64 + lane] = wave_prefix_max((lane * 37) % 64 - 20);  // expect the maximum over lanes 0..lane
 }
 
 }  // namespace sa
@@ -1114,17 +1115,20 @@ int sa_selftest(int device)
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     int *d = nullptr;
-    HIP_TRY(hipMalloc(&d, 6 * 64 * sizeof(int)));
+    HIP_TRY(hipMalloc(&d, 7 * 64 * sizeof(int)));
     hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(64), 0, 0, d);
-    std::vector<int> h(6 * 64);
+    std::vector<int> h(7 * 64);
     HIP_TRY(hipMemcpy(h.data(), d, h.size() * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(hipFree(d));
     uint64_t b = 0;
     for (int l = 0; l < 64; ++l)
         if (l % 3 == 0) b |= 1ull << l;
     const int sbfe[4] = {5, 10, -9, 24};
+    int pmax = INT32_MIN;
     for (int l = 0; l < 64; ++l)
     {
+        pmax = std::max(pmax, (l * 37) % 64 - 20);
+        if (h[384 + l] != pmax) return fail(SA_ERR_UNSUPPORTED, "DPP prefix maximum mismatch at lane " + std::to_string(l));
         if (h[l] != (l == 0 ? -1 : 100 + l - 1)) return fail(SA_ERR_UNSUPPORTED, "DPP wave_shr:1 mismatch at lane " + std::to_string(l));
         if (h[64 + l] != (l == 63 ? -2 : 100 + l + 1)) return fail(SA_ERR_UNSUPPORTED, "DPP wave_shl:1 mismatch at lane " + std::to_string(l));
         if (h[128 + l] != 100 + (l + 1) % 64) return fail(SA_ERR_UNSUPPORTED, "DPP wave_rol:1 mismatch at lane " + std::to_string(l));

@@ -86,6 +86,28 @@ __global__ __launch_bounds__(64) void score_band_at_kernel(ScoreBandAtArgs ba)
     score_wave<true, R, MODE, SMALL, false, true, MODE != SA_LOCAL, true>(ba.sa.s, ba.sa.gap_extend, tab, TraceArgs(), 0, ba.ends, ba.bands);
 }
 
+// score_kernel and score_affine_kernel as extension alignment (sa_hip.h sa_score_batch_extend;
+// sa_score_wave.h: EXT): the global borders, the best interior cell before the stop row of `xdrop`
+struct ScoreExtendArgs {
+    ScoreAffineArgs sa;
+    int32_t xdrop;
+};
+
+template <int R, bool SMALL>
+__global__ __launch_bounds__(64) void score_extend_kernel(ScoreExtendArgs xa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<false, R, SA_GLOBAL, SMALL, false, false, false, false, true>(xa.sa.s, 0, tab, TraceArgs(), 0, 0, nullptr, xa.xdrop);
+}
+
+template <int R, bool SMALL>
+__global__ __launch_bounds__(64) void score_affine_extend_kernel(ScoreExtendArgs xa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, R, SA_GLOBAL, SMALL, false, false, false, false, true>(xa.sa.s, xa.sa.gap_extend, tab, TraceArgs(), 0, 0, nullptr,
+                                                                            xa.xdrop);
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -102,6 +124,27 @@ namespace {
 // program when the text's end is free and the global one otherwise.
 // `bands` non-null (BAND): score_band_at_kernel on the per-pair bands; SA_GLOBAL and SA_FIT launch as
 // SA_ENDS_FREE with no flags and with the text's two.
+// score_extend_kernel or, with AFFINE, score_affine_extend_kernel: <R, SMALL> as launch_score picks them
+template <bool AFFINE>
+void launch_score_extend(const ScoreArgs &a, int gap_extend, int xdrop, int R, bool small, int grid, hipStream_t st)
+{
+    const ScoreExtendArgs xa = {{a, gap_extend}, xdrop};
+    auto launch = [&](auto rc, auto smallc) {
+        constexpr int RR = decltype(rc)::value;
+        constexpr bool SMALL = decltype(smallc)::value;
+        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_extend_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, xa);
+        else hipLaunchKernelGGL((score_extend_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, xa);
+    };
+    auto with_r = [&](auto rc) { small ? launch(rc, std::true_type{}) : launch(rc, std::false_type{}); };
+    switch (R)
+    {
+    case 1: with_r(std::integral_constant<int, 1>{}); break;
+    case 2: with_r(std::integral_constant<int, 2>{}); break;
+    case 4: with_r(std::integral_constant<int, 4>{}); break;
+    default: with_r(std::integral_constant<int, 8>{}); break;
+    }
+}
+
 template <bool AFFINE, bool BAND = false>
 void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st, int band = 0,
                   const Band *bands = nullptr)
@@ -181,9 +224,11 @@ void free_scorer(sa_scorer *s)
 }  // namespace
 
 // sa_scorer_create, sa_scorer_create_affine, sa_scorer_create_banded and sa_scorer_create_band_at:
-// `gapm` null is the linear scorer, `band` non-null the banded one, `with_bands` the band-at one on `bands`
+// `gapm` null is the linear scorer, `band` non-null the banded one, `with_bands` the band-at one on `bands`,
+// `xdrop` non-null the extension scorer (sa_scorer_create_extend)
 static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out,
-                         const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr)
+                         const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr,
+                         const int32_t *xdrop = nullptr)
 {
     if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create: null argument");
     *out = nullptr;
@@ -195,7 +240,9 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm, band, bands)) return fail(rc, err);
+    const ScoreExtend ext = {xdrop ? *xdrop : SA_NO_XDROP, false};
+    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm, band, bands, xdrop ? &ext : nullptr))
+        return fail(rc, err);
     std::vector<ScorePair> h((size_t)np);
     for (int64_t p = 0; p < np; ++p)
         h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
@@ -221,7 +268,8 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
 
 // sa_score_batch, sa_score_batch_affine and sa_score_batch_banded
 static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_pair *pairs, int64_t np, int device,
-                       sa_score_result *out, const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr)
+                       sa_score_result *out, const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr,
+                       const int32_t *xdrop = nullptr)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch: null argument");
     std::vector<sa_pair> dp((size_t)np);
@@ -237,7 +285,7 @@ static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_p
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     sa_scorer *raw = nullptr;
-    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw, band, with_bands, bands)) return rc;
+    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw, band, with_bands, bands, xdrop)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
     std::vector<char> ht(tb), hp(pb);
     for (int64_t p = 0; p < np; ++p)
@@ -282,6 +330,13 @@ int sa_scorer_create_band_at(const sa_params *P, int32_t gap_open, int32_t gap_e
     return create_scorer(P, &gapm, pairs, np, device, out, nullptr, true, bands);
 }
 
+int sa_scorer_create_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_pair *pairs,
+                            int64_t np, int device, sa_scorer **out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return create_scorer(P, &gapm, pairs, np, device, out, nullptr, false, nullptr, &xdrop);
+}
+
 int sa_scorer_destroy(sa_scorer *s)
 {
     free_scorer(s);
@@ -313,7 +368,9 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     a.key_rowbits = s->key_rowbits;
     a.row_stride = s->row_stride;
     const bool small = s->A <= 4;
-    if (s->d_bands) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, 0, s->d_bands);
+    if (s->extend && s->affine) launch_score_extend<true>(a, s->gap_extend, s->xdrop, s->R, small, s->grid, st);
+    else if (s->extend) launch_score_extend<false>(a, 0, s->xdrop, s->R, small, s->grid, st);
+    else if (s->d_bands) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, 0, s->d_bands);
     else if (s->band >= 0) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, s->band);
     else if (s->affine) launch_score<true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st);
     else launch_score<false>(a, 0, s->R, s->mode, small, s->grid, st);
@@ -370,6 +427,13 @@ int sa_score_batch_band_at(const sa_params *P, int32_t gap_open, int32_t gap_ext
 {
     const ScoreGap gapm = {gap_open, gap_extend};
     return score_batch(P, &gapm, pairs, np, device, out, nullptr, true, bands);
+}
+
+int sa_score_batch_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_host_pair *pairs,
+                          int64_t np, int device, sa_score_result *out)
+{
+    const ScoreGap gapm = {gap_open, gap_extend};
+    return score_batch(P, &gapm, pairs, np, device, out, nullptr, false, nullptr, &xdrop);
 }
 
 }  // extern "C"

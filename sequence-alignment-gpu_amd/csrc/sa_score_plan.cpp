@@ -21,10 +21,10 @@ const ScoreKnobs &score_knobs()
 }
 
 // the instance of each R with the most registers (local, alphabets up to 4): 53, 71, 101 and 165
-// VGPRs of the SIMD's 512
+// VGPRs of the SIMD's 512; the extension instances, planned as local ones, take 49, 67, 95 and 129
 int score_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 7 : 8; }
 
-// score_affine_kernel: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4)
+// score_affine_kernel: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4); extension: 59, 79, 114, 154
 int score_affine_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 5 : 8; }
 
 namespace {
@@ -77,7 +77,8 @@ extern "C" int sa_band_reachable(int32_t mode, uint64_t text_len, uint64_t patte
 }
 
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine, const int32_t *band, const sa_band *bands)
+                    ScorePlan *out, std::string *err, const ScoreGap *affine, const int32_t *band, const sa_band *bands,
+                    const ScoreExtend *extend)
 {
     auto fail = [&](int code, const char *msg) { *err = msg; return code; };
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
@@ -95,6 +96,21 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
         if (ends) return fail(SA_ERR_UNSUPPORTED, "SA_ENDS_FREE takes no band");
     }
     if (bands && (!affine || band)) return fail(SA_ERR_INVALID, "per-pair bands take gap_open and gap_extend and no half-width");
+    if (extend)
+    {
+        if (!affine) return fail(SA_ERR_INVALID, "extension alignment takes gap_open and gap_extend");
+        if (P->mode != SA_GLOBAL) return fail(SA_ERR_INVALID, "extension alignment takes mode SA_GLOBAL: its borders are global's");
+        if (extend->xdrop < SA_NO_XDROP || extend->xdrop >= (1 << 30)) return fail(SA_ERR_INVALID, "xdrop must be SA_NO_XDROP or 0 .. 2^30 - 1");
+        if (band || bands) return fail(SA_ERR_UNSUPPORTED, "extension alignment inside a band (band or bands with xdrop) is not built");
+    }
+    // gap open == gap extend is the linear recurrence of that penalty: the linear instances, step costs and
+    // boundary row, with the penalty in the place of P->gap_penalty
+    int64_t g = P->gap_penalty;
+    if (extend && !extend->traced && affine->open == affine->extend)
+    {
+        g = affine->open;
+        affine = nullptr;
+    }
     const bool banded = band || bands;
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
@@ -103,7 +119,6 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
 
     // ---- the limits of the plans, unchanged; an affine gap counts as the larger of
     // |open| and |extend|, and as negative if either is ----
-    int64_t g = P->gap_penalty;
     if (affine)
     {
         g = std::max(std::llabs((long long)affine->open), std::llabs((long long)affine->extend));
@@ -160,7 +175,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
         return bands ? pl.bands[p] : band_of((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, *band);
     };
     pl.key_rowbits = std::max(1, bitlen(lmax + 1));
-    if (P->mode == SA_LOCAL && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * pl.key_rowbits))
+    if ((P->mode == SA_LOCAL || extend) && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * pl.key_rowbits))
         return fail(SA_ERR_UNSUPPORTED, "local scores may exceed the best-cell key range");
 
     pl.mode = P->mode;
@@ -169,6 +184,8 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     pl.affine = affine != nullptr;
     pl.gap_extend = affine ? affine->extend : 0;
     pl.band = band ? *band : -1;
+    pl.extend = extend != nullptr;
+    pl.xdrop = extend ? extend->xdrop : SA_NO_XDROP;
     pl.num_pairs = np;
     pl.num_cu = kn.max_cus > 0 ? std::min(num_cu, kn.max_cus) : num_cu;
 
@@ -196,7 +213,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     static const int kR[4] = {1, 2, 4, 8};
     const bool fit = P->mode == SA_FIT || (ends && (P->mode & SA_FREE_TEXT_END));
     const int step_base = (affine ? kScoreAffineStepBase : kScoreStepBase) + (fit ? kScoreFitStepBest - kScoreFitStepSelect : 0);
-    const int step_row = (P->mode == SA_LOCAL ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
+    const int step_row = (P->mode == SA_LOCAL || extend ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
                                               : (affine ? kScoreAffineStepRowGlobal : kScoreStepRowGlobal)) +
                          (fit ? kScoreFitStepSelect : 0);
     int best = 0;

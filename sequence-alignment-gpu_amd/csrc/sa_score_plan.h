@@ -49,6 +49,13 @@ struct ScoreGap {
     int32_t open, extend;
 };
 
+// Extension alignment (sa_hip.h sa_score_batch_extend): the X-drop of the call, SA_NO_XDROP for none.
+// `traced` is set by the trace planner: the traced instance is the affine one whatever the penalties.
+struct ScoreExtend {
+    int32_t xdrop;
+    bool traced;
+};
+
 #if defined(__HIPCC__)
 #define SA_BAND_FN __host__ __device__ inline
 #else
@@ -132,6 +139,8 @@ struct ScorePlan {
     int gap_extend = 0;
     int band = -1;                 // banded scorer (affine only): the half-width; -1: the whole rectangle
     std::vector<Band> bands;       // band-at scorer (affine only): every pair's band, clipped (band_clip); band is -1
+    bool extend = false;           // extension scorer: mode is SA_GLOBAL, the program local's; affine iff open != extend
+    int xdrop = SA_NO_XDROP;       // its X-drop
     int num_cu = 0, waves_per_simd = 0, grid = 0;
     int64_t num_pairs = 0;
     uint64_t max_text = 0;         // longest text
@@ -154,9 +163,14 @@ struct ScorePlan {
 // band of pair p, in every mode: lo > hi and a pair that sa_band_reachable denies are SA_ERR_INVALID, the
 // message naming the pair; the rest as with `band`, on the clipped bands (ScorePlan::bands), and the
 // descriptors count 8 more bytes per pair.
+// `extend` non-null: the extension scorer (sa_hip.h sa_score_batch_extend), which takes `affine`, the mode
+// SA_GLOBAL and an xdrop of SA_NO_XDROP .. 2^30 - 1 (else SA_ERR_INVALID) and no band of either kind
+// (SA_ERR_UNSUPPORTED). Cost, R, grid and bytes are the local program's, the linear one when gap open
+// equals gap extend (unless `traced`); xdrop changes nothing, the stop rows are not known beforehand. The
+// limits are the int32 one and the local best-cell key's.
 int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
                     ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr, const int32_t *band = nullptr,
-                    const sa_band *bands = nullptr);
+                    const sa_band *bands = nullptr, const ScoreExtend *extend = nullptr);
 
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).

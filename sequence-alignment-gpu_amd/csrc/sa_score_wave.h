@@ -114,6 +114,31 @@
 //    column in 1..n. Lane 0 drops a row-m candidate that is not real ((m, n) out of band without TE) and
 //    counts H[0][n] and H[m][0] only in band; reachability leaves at least one candidate.
 //  - An empty side: the candidates are the border's in-band cells.
+//
+// EXT (MODE SA_GLOBAL, no band, no free ends: score_extend_kernel, score_affine_extend_kernel,
+// align_extend_kernel) is extension alignment, sa_hip.h sa_score_batch_extend: the start anchored at the
+// origin, the end at the best interior cell of the rows before the stop row i*, `xdrop` a wave-uniform
+// kernel argument. It is the local program's result on the global program's cells; everything of EXT is
+// under `if constexpr (EXT)` or a constant condition, so the other instances compile to what they were.
+//  - Cells. The borders, the recurrence and the traced nibble are global's: no clamp, no STOP nibble.
+//  - Per-row best. best[r] starts below any score at every strip and a lane outside columns 1..n
+//    registers nothing (the fit step's `valid` test): H[row][0] may exceed the row's real cells, which the
+//    local step never sees as its values are >= 0. After a strip best[r] is r(row) for every row <= m, as
+//    every strip runs all columns. The key and its `best > 0` condition are local's: without a positive
+//    row the wave maximum is 0, the empty extension at (0, 0).
+//  - Drop test, after every strip, outside the step. Row i drops iff B(i - 1) - r(i) > xdrop. B(i - 1) is
+//    the maximum of B carried from the strips before (a scalar, 0 at the start: the origin), of the lanes
+//    before this one (an inclusive prefix maximum of the lanes' strip maxima, wave_prefix_max, shifted by
+//    one lane) and of the lane's rows before. A ballot finds the first lane that holds a dropping row and
+//    a readlane its first such row: i*, wave-uniform. Rows past m neither raise B nor drop.
+//  - Exit. Without a drop B is carried on. With one, only rows < i* fold into the key and the strip loop
+//    ends (a uniform break): the strips below run no body, store no direction word and leave the
+//    boundary row as strip s wrote it. That row is stale for this pair's shape, and harmless: strip 0 of
+//    the wave's next pair reads its top row from the border formula, never from the buffer, and every
+//    later strip reads only columns the strip before it wrote (the BAT argument above, without windows).
+//    The walk starts at a cell of a row < i*, rows only fall along it, and those rows' strips stored
+//    every word: it never reads a word of a strip that did not run.
+//  - xdrop SA_NO_XDROP skips the test: every row counts, as with a drop that no score can reach.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -166,16 +191,19 @@ struct MaskedStep : std::true_type {
 
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
 // registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
-template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false, bool BAT = false>
+template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false, bool BAT = false,
+          bool EXT = false>
 __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs(),
-                                           int band = 0, int ends = 0, const Band *bands = nullptr)
+                                           int band = 0, int ends = 0, const Band *bands = nullptr, int xdrop = SA_NO_XDROP)
 {
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
     static_assert(!BAND || (AFFINE && (BAT || MODE != SA_FIT)), "banded instances: affine; on the half-width, global or local");
     static_assert(!ENDS || (MODE != SA_LOCAL && (BAT || !BAND)), "ends-free instances: the global or the fit program, no band but the caller's");
     static_assert(!BAT || (BAND && (ENDS || MODE == SA_LOCAL)), "band-at instances: banded; local, or ends-free (global and fit are two of its flag sets)");
+    static_assert(!EXT || (MODE == SA_GLOBAL && !BAND && !ENDS), "extension instances: the global borders, no band, no free ends");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
+    constexpr bool BEST = LOCAL || EXT;  // the result is the best cell: per-row running best and the key
     constexpr int SENT = kBandSentinel;
     using Col = std::conditional_t<AFFINE, int2, int32_t>;  // a column of the boundary row
     const int lane = threadIdx.x;
@@ -253,11 +281,11 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             {
                 const int k = FIT ? m : max(n, m);  // FIT: the text is free, only the pattern costs
                 sa_score_result r;
-                if constexpr (AFFINE) r.score = LOCAL || k == 0 ? 0 : -(g + (k - 1) * ge);
-                else r.score = LOCAL ? 0 : -g * k;
+                if constexpr (AFFINE) r.score = BEST || k == 0 ? 0 : -(g + (k - 1) * ge);
+                else r.score = BEST ? 0 : -g * k;
                 r.status = SA_OK;
-                r.end_text = LOCAL || (FIT && m == 0) ? 0 : (uint64_t)n;
-                r.end_pattern = LOCAL ? 0 : (uint64_t)m;
+                r.end_text = BEST || (FIT && m == 0) ? 0 : (uint64_t)n;
+                r.end_pattern = BEST ? 0 : (uint64_t)m;
                 a.out[pi] = r;
             }
             continue;
@@ -276,6 +304,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         // ENDS: the lane's first maximum of H[row][n] over its rows <= m of the strips so far, started
         // below any score, and its row
         int pebest = -(1 << 30), perow = 0;
+        int bcarry = 0;  // EXT: B of the last row of the strips so far; B(0) = 0, the origin
         uint32_t *dlane = nullptr;  // TRACE: the lane's word of step 0 of the pair's first strip
         if constexpr (TRACE) dlane = tr.dirs + uniform64(tr.dir_off[pi]) + lane;
         // BAND: cell (i, j) is in band iff (unsigned)(j - i - blo) <= bspan
@@ -346,7 +375,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     hl[r] = in ? hl[r] : SENT;
                     el[r] = in ? el[r] : SENT;
                 }
-                best[r] = 0;
+                best[r] = EXT ? INT32_MIN : 0;  // EXT: below any score, so that after the strip it is r(row)
                 bestt[r] = 0;
             }
             if constexpr (FIT)
@@ -454,10 +483,11 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                         h = valid ? h : hl[r];
                         if constexpr (AFFINE) e = valid ? e : el[r];
                     }
-                    if (LOCAL)
+                    if (BEST)
                     {
-                        // a row meets its columns in ascending order: strictly greater keeps the first
-                        const bool better = h > best[r];
+                        // a row meets its columns in ascending order: strictly greater keeps the first.
+                        // EXT: H[row][0] (or H[row][n] again) may exceed the row's cells and is no candidate
+                        const bool better = EXT ? valid && h > best[r] : h > best[r];
                         best[r] = better ? h : best[r];
                         bestt[r] = better ? t : bestt[r];
                     }
@@ -589,7 +619,41 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     perow = better ? row : perow;
                 }
             }
-            if (LOCAL)
+            // EXT: rows from `stop` on count for nothing; a strip that holds row i* is the last one run
+            int stop = INT32_MAX;
+            if constexpr (EXT)
+            {
+                if (xdrop >= 0)  // wave-uniform
+                {
+                    // row i drops iff B(i - 1) - r(i) > xdrop, B(i - 1) the maximum of the carried B, of the
+                    // lanes before (their rows come first) and of the lane's rows before
+                    int lm = INT32_MIN, pm[R];
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                    {
+                        pm[r] = lm;
+                        lm = row1 + r < m ? max(lm, best[r]) : lm;
+                    }
+                    const int inc = wave_prefix_max(lm);
+                    const int before = max(bcarry, dpp_shr1(INT32_MIN, inc));
+                    int fr = R;  // the lane's first dropping row
+#pragma unroll
+                    for (int r = R - 1; r >= 0; --r)
+                    {
+                        // |H| < 2^30 and 0 <= B < 2^30 (planner): the difference stays inside int32
+                        const bool drop = row1 + r < m && max(before, pm[r]) - best[r] > xdrop;
+                        fr = drop ? r : fr;
+                    }
+                    const uint64_t dl = ballot(fr < R);
+                    if (dl)
+                    {
+                        const int l0 = __builtin_ctzll(dl);
+                        stop = s * 64 * R + R * l0 + __builtin_amdgcn_readlane(fr, l0) + 1;
+                    }
+                    else bcarry = max(bcarry, __builtin_amdgcn_readlane(inc, kWave - 1));
+                }
+            }
+            if (BEST)
             {
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -597,13 +661,17 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     const int row = row1 + r + 1, col = bestt[r] - lane + 1;
                     const uint64_t key = ((uint64_t)(uint32_t)best[r] << (2 * kb)) |
                                          ((uint64_t)(~(uint32_t)row & kmask) << kb) | (uint64_t)(~(uint32_t)col & kmask);
-                    if (row <= m && best[r] > 0 && key > lanekey) lanekey = key;
+                    if (row <= m && (!EXT || row < stop) && best[r] > 0 && key > lanekey) lanekey = key;
                 }
+            }
+            if constexpr (EXT)
+            {
+                if (stop != INT32_MAX) break;  // uniform: the strips below run no body and store nothing
             }
         }
         sa_score_result res;
         res.status = SA_OK;
-        if (LOCAL)
+        if (BEST)
         {
             const uint64_t key = wave_max_u64(lanekey);
             const uint32_t H = (uint32_t)(key >> (2 * kb));

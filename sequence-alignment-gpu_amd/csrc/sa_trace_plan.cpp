@@ -19,7 +19,7 @@ uint64_t trace_arena_budget()
 
 int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
                     int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err, const int32_t *band,
-                    const sa_band *bands)
+                    const sa_band *bands, const int32_t *xdrop)
 {
     if (!out)
     {
@@ -35,7 +35,8 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
     // SA_SCORE_WAVES is tuned for the untraced kernels: here it may lower the grid, not raise it past
     // what the traced instances' registers admit
     k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
-    if (int rc = make_score_plan(P, pairs, np, num_cu, k8, &pl.score, err, &gapm, band, bands)) return rc;
+    const ScoreExtend ext = {xdrop ? *xdrop : SA_NO_XDROP, true};
+    if (int rc = make_score_plan(P, pairs, np, num_cu, k8, &pl.score, err, &gapm, band, bands, xdrop ? &ext : nullptr)) return rc;
     pl.budget = budget;
     pl.dir_bytes.resize((size_t)np);
     pl.dir_off.resize((size_t)np);

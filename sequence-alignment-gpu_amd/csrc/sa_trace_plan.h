@@ -90,8 +90,10 @@ struct TracePlan {
 // chunks are cut by them, and a pair is refused only when its band exceeds the budget.
 // `bands` non-null (and `band` null): the band-at aligner, bands[p] the band of pair p
 // (make_score_plan's checks; trace_band_at_dir_bytes of the clipped band).
+// `xdrop` non-null: the extension aligner (sa_hip.h sa_align_pairs_extend; make_score_plan's checks). A pair
+// is planned with the directions of a global pair: where its fill stops is not known beforehand.
 int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
                     int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err,
-                    const int32_t *band = nullptr, const sa_band *bands = nullptr);
+                    const int32_t *band = nullptr, const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
 
 }  // namespace sa

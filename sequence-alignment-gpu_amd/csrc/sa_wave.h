@@ -66,6 +66,18 @@ __device__ __forceinline__ int wave_prefix_sum(int x)
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
     return x;
 }
+// Inclusive prefix maximum over the wave's lanes (lane l: maximum of lanes 0..l), the same shifts: a
+// lane without a source keeps INT32_MIN (bound_ctrl off, `old` below any value), which no maximum takes
+__device__ __forceinline__ int wave_prefix_max(int x)
+{
+    x = max(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x111, 0xf, 0xf, false));
+    x = max(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x112, 0xf, 0xf, false));
+    x = max(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x114, 0xf, 0xf, false));
+    x = max(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x118, 0xf, 0xf, false));
+    x = max(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x142, 0xa, 0xf, false));
+    x = max(x, __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x143, 0xc, 0xf, false));
+    return x;
+}
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint64_t uniform64(uint64_t v)
 {

@@ -23,6 +23,9 @@ FIT = SA_FIT = 2
 ENDS_FREE = 16
 FREE_TEXT_BEGIN, FREE_TEXT_END, FREE_PATTERN_BEGIN, FREE_PATTERN_END = 1, 2, 4, 8
 OVERLAP = ENDS_FREE | 15
+# xdrop= of score_batch, Scorer and align_pairs_affine (sa_hip.h SA_NO_XDROP): extension alignment that
+# never stops early
+NO_XDROP = -1
 STATUS = {0: "SA_OK", 1: "SA_ERR_INVALID", 2: "SA_ERR_NOMEM", 3: "SA_ERR_HIP", 4: "SA_ERR_UNSUPPORTED",
           5: "SA_ERR_TIMEOUT"}
 
@@ -38,7 +41,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_scorer_fetch", "sa_scorer_info", "sa_scorer_destroy", "sa_search", "sa_score_batch_affine",
            "sa_scorer_create_affine", "sa_align_pairs_affine", "sa_search_affine", "sa_affine_last_stats",
            "sa_score_batch_banded", "sa_scorer_create_banded", "sa_align_pairs_banded",
-           "sa_score_batch_band_at", "sa_scorer_create_band_at", "sa_align_pairs_band_at", "sa_band_reachable")
+           "sa_score_batch_band_at", "sa_scorer_create_band_at", "sa_align_pairs_band_at", "sa_band_reachable",
+           "sa_score_batch_extend", "sa_scorer_create_extend", "sa_align_pairs_extend")
 
 
 class SaParams(ctypes.Structure):
@@ -140,6 +144,11 @@ def _load():
                                            ctypes.POINTER(P)]
     L.sa_align_pairs_band_at.argtypes = [ctypes.POINTER(SaParams), I32, I32, P, P, ctypes.c_int64, I,
                                          ctypes.POINTER(SaResult), P, P]
+    L.sa_score_batch_extend.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_extend.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                          ctypes.POINTER(P)]
+    L.sa_align_pairs_extend.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.c_int64, I,
+                                        ctypes.POINTER(SaResult), P, P]
     L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
     L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -269,7 +278,7 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
                        gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None,
-                       bands=None) -> list[dict]:
+                       bands=None, xdrop: int | None = None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
     ones. With gap_open == gap_extend == g every value is align_pair's for gap g. `mode` may also be FIT
@@ -277,10 +286,14 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
     indices of the first aligned letters. With `band` (SA_GLOBAL and SA_LOCAL only),
     sa_align_pairs_banded: the alignment inside the diagonal band of that half-width (sa_hip.h). With
     `bands` (an (np, 2) int32 array or a list of (lo, hi), one per pair; not with `band`),
-    sa_align_pairs_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode."""
+    sa_align_pairs_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode. With `xdrop`
+    (NO_XDROP or 0 .. 2**30 - 1; mode SA_GLOBAL, no band), sa_align_pairs_extend: extension alignment, from
+    the origin to the best cell of the rows before the X-drop's stop row; both starts are 0."""
     if band is not None and bands is not None:
         raise ValueError("band= and bands= exclude each other")
-    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band, bands)
+    if xdrop is not None and (band is not None or bands is not None):
+        raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
+    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band, bands, xdrop)
 
 
 def affine_last_stats() -> dict:
@@ -292,7 +305,7 @@ def affine_last_stats() -> dict:
 
 
 def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings, band=None,
-                      bands=None) -> list[dict]:
+                      bands=None, xdrop=None) -> list[dict]:
     """align_batch (gap_extend None) and align_pairs_affine (with `band`, sa_align_pairs_banded): one
     packing of the host pairs and buffers."""
     p, S_keep, alpha_keep = _params(mode, S, gap, alphabet, 0)
@@ -305,7 +318,10 @@ def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, devic
     at = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_t]) if strings else None
     ap = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_p]) if strings else None
     res = (SaResult * max(1, n))()
-    if gap_extend is None:
+    if xdrop is not None:
+        _check(lib.sa_align_pairs_extend(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, hp, n, device,
+                                         res, at, ap))
+    elif gap_extend is None:
         _check(lib.sa_align_batch(ctypes.byref(p), hp, n, num_gpus, res, at, ap))
     elif bands is not None:
         b = _bands(bands, n)
@@ -415,7 +431,7 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                bands=None) -> np.ndarray:
+                bands=None, xdrop: int | None = None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
     the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
@@ -424,16 +440,23 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     an ends-free mode (ends_free(), OVERLAP; not with `band`): end_pattern and end_text are the cell the
     score is read from. With `bands` (an (np, 2) int32 array or a list of (lo, hi), one per pair; not with
     `band`), sa_score_batch_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode; a pair
-    without an alignment in its band fails the call (band_reachable)."""
+    without an alignment in its band fails the call (band_reachable). With `xdrop` (NO_XDROP or
+    0 .. 2**30 - 1; mode SA_GLOBAL, no band), sa_score_batch_extend: extension alignment, the best cell of
+    the rows before the X-drop's stop row, anchored at the origin; without `gap_extend` the gap is linear."""
     if band is not None and bands is not None:
         raise ValueError("band= and bands= exclude each other")
+    if xdrop is not None and (band is not None or bands is not None):
+        raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
     n = len(ts)
     hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
     out = np.zeros(max(1, n), SCORE_DTYPE)
-    if bands is not None:
+    if xdrop is not None:
+        _check(lib.sa_score_batch_extend(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, hp, n, device,
+                                         out.ctypes.data))
+    elif bands is not None:
         b = _bands(bands, n)
         _check(lib.sa_score_batch_band_at(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, b.ctypes.data, hp, n,
                                           device, out.ctypes.data))
@@ -451,21 +474,27 @@ class Scorer:
     """Scores of many pairs, device-resident arenas, explicit stream (beside Plan: no planes, no traceback).
     With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty. With
     `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear). With
-    `bands`, one (lo, hi) per pair, a band-at scorer (sa_scorer_create_band_at; not with `band`). `mode` as
-    score_batch takes it."""
+    `bands`, one (lo, hi) per pair, a band-at scorer (sa_scorer_create_band_at; not with `band`). With
+    `xdrop`, an extension scorer (sa_scorer_create_extend; mode SA_GLOBAL, no band). `mode` as score_batch
+    takes it."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
                  device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                 bands=None):
+                 bands=None, xdrop: int | None = None):
         if band is not None and bands is not None:
             raise ValueError("band= and bands= exclude each other")
+        if xdrop is not None and (band is not None or bands is not None):
+            raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)
         self.pairs = pairs
         self.device = device
         h = ctypes.c_void_p()
-        if bands is not None:
+        if xdrop is not None:
+            _check(lib.sa_scorer_create_extend(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, xdrop,
+                                               arr, len(pairs), device, ctypes.byref(h)))
+        elif bands is not None:
             b = _bands(bands, len(pairs))
             _check(lib.sa_scorer_create_band_at(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend,
                                                 b.ctypes.data, arr, len(pairs), device, ctypes.byref(h)))

@@ -45,7 +45,21 @@ within the baseline's median plus the baseline's own min-max spread of the same 
 built checkout without the modes, e.g. the parent commit) only SA_FIT and SA_GLOBAL run, on the same data:
 the figures the existing modes are compared with across the two libraries.
 
+With --mode extend the extension scorers and aligner (sa_hip.h: sa_scorer_create_extend,
+sa_align_pairs_extend). Same work: on the read-mapping workload of --mode fit the extension scorer without
+a drop beside the local scorer, whose program it runs, under the linear gap 5 and under 11 / 2, alternated
+round by round (7 rounds unless --rounds says otherwise); the report says whether the extension's median
+lies inside the local scorer's own min-max spread. The early exit: 2048 DNA pairs of 20000 letters, each
+pattern a 5 %-mutated copy of its text for its first quarter and unrelated letters after, under gap open
+16 / gap extend 4 (--exit-gap; under 11 / 2 and under the linear gap 5 unrelated DNA letters score upwards
+against +5 / -4, about 0.2 a row, and no X-drop ever stops them): the extension scorer at X-drop 100, the extension scorer without a drop and the local scorer, alternated;
+beside the measured ratio the model's, strips run over strips in all at the planned rows per lane, from
+the stop rows of a row-by-row numpy reference on a 16-pair subsample, whose results the scorers' must
+equal. Then sa_align_pairs_extend on 64 of these pairs at X-drop 100 and without a drop: the device time
+of the traced fill and of the walk (sa_affine_last_stats).
+
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+    python3 tools/score_bench.py --mode extend [--small] --out profiles/r17/score_extend_bench.json
     python3 tools/score_bench.py --mode ends [--small] --out profiles/r15/score_ends_bench.json
     python3 tools/score_bench.py --mode ends --tree ../parent --out profiles/r15/score_ends_bench_parent.json
 With --band W [W ...] the banded scorer and aligner (sa_hip.h: sa_scorer_create_banded,
@@ -380,6 +394,142 @@ def mapped_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
     return row
 
 
+def chimeric_workload(small: bool) -> dict:
+    """DNA pairs of 20000 letters: the pattern is its text with 5 % substitutions for its first quarter
+    and unrelated letters after it."""
+    from sa_amd import synthetic
+    npairs, side = (128, 20000) if small else (2048, 20000)
+    text = synthetic.random_sequence(31, npairs * side, 4)
+    pattern = synthetic.random_sequence(32, npairs * side, 4).copy()
+    q = side // 4
+    for k in range(npairs):
+        pattern[k * side:k * side + q] = synthetic.mutate(text[k * side:k * side + q], 2000 + k, 4, q, p_del=0.0, p_ins=0.0, p_sub=0.05)
+    return {"name": "chimeric", "S": synthetic.blast_matrix(), "text": text, "pattern": pattern,
+            "pairs": [(k * side, side, k * side, side) for k in range(npairs)]}
+
+
+def extend_rowwise_ref(t, p, S, go: int, ge: int, xdrop):
+    """(score, end_pattern, end_text, stop row) of extension alignment (sa_hip.h), row by row in numpy and
+    no further than the stop row; xdrop None is no drop. For go >= ge >= 0, where a gap along the row never
+    opens from a cell that a gap along the row reached: E[j] = max over k < j of
+    max(diag, F)[k] - go - (j - 1 - k) ge, a running maximum."""
+    assert go >= ge >= 0
+    t, p, S = np.asarray(t, dtype=np.int64), np.asarray(p, dtype=np.int64), np.asarray(S, dtype=np.int64)
+    n, m = len(t), len(p)
+    if n == 0 or m == 0:
+        return 0, 0, 0, m + 1
+    NEG = -(1 << 40)
+    cols = np.arange(n + 1, dtype=np.int64)
+    Hup = np.concatenate([[0], -(go + (cols[1:] - 1) * ge)])
+    F = np.full(n + 1, NEG, dtype=np.int64)
+    B, best, bi, bj = 0, 0, 0, 0
+    for i in range(1, m + 1):
+        F = np.maximum(F - ge, Hup - go)
+        hp = np.empty(n + 1, dtype=np.int64)
+        hp[0] = -(go + (i - 1) * ge)
+        hp[1:] = np.maximum(Hup[:-1] + S[p[i - 1], t], F[1:])
+        acc = np.maximum.accumulate(hp + cols * ge)
+        H = hp.copy()
+        H[1:] = np.maximum(hp[1:], acc[:-1] - go - cols[:-1] * ge)
+        r = int(H[1:].max())
+        if xdrop is not None and B - r > xdrop:
+            return best, bi, bj, i
+        B = max(B, r)
+        if r > best:
+            best, bi, bj = r, i, 1 + int(H[1:].argmax())
+        Hup = H
+    return best, bi, bj, m + 1
+
+
+def extend_same_work_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
+    """The extension scorer without a drop beside the local scorer of the same penalties, alternated."""
+    cells, affine = sum(p[1] * p[3] for p in w["pairs"]), gap_extend is not None
+    sc = {"local": engine.Scorer(1, w["S"], gap, w["pairs"], gap_extend=gap_extend),
+          "extend_no_xdrop": engine.Scorer(0, w["S"], gap, w["pairs"], gap_extend=gap_extend, xdrop=engine.NO_XDROP)}
+    row = {"name": w["name"] + ("_affine" if affine else "_linear"), "pairs": len(w["pairs"]), "cells": cells, "gap": gap,
+           "gap_extend": gap_extend, "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for _ in range(2):  # warm-up
+        for k, s in sc.items():
+            s.run(dt.data_ptr(), dp.data_ptr())
+            res[k] = s.results()
+    assert (res["extend_no_xdrop"]["score"] <= res["local"]["score"]).all(), "an anchored score exceeds the local one"
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            ms[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    for k, s in sc.items():
+        row[k + "_run"] = stats(ms[k])
+        row[k + "_gcups"] = round(cells / statistics.median(ms[k]) / 1e6, 1)
+        s.close()
+    med = statistics.median(ms["extend_no_xdrop"])
+    row["extend_over_local"] = round(med / statistics.median(ms["local"]), 4)
+    row["extend_inside_local_min_max"] = bool(min(ms["local"]) <= med <= max(ms["local"]))
+    return row
+
+
+def extend_early_exit_row(args, engine, w, dt, dp, go: int, ge: int, xdrop: int) -> dict:
+    """The extension scorer at `xdrop`, without a drop, and the local scorer on the chimeric pairs."""
+    pairs, cells = w["pairs"], sum(p[1] * p[3] for p in w["pairs"])
+    sc = {"extend_xdrop": engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, xdrop=xdrop),
+          "extend_no_xdrop": engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, xdrop=engine.NO_XDROP),
+          "local": engine.Scorer(1, w["S"], go, pairs, gap_extend=ge)}
+    row = {"name": w["name"], "pairs": len(pairs), "cells": cells, "gap_open": go, "gap_extend": ge, "xdrop": xdrop,
+           "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for k, s in sc.items():  # warm-up, and the results
+        s.run(dt.data_ptr(), dp.data_ptr())
+        res[k] = s.results().copy()
+    # the subsample against the reference: every pair at the X-drop (rows up to its stop row), four without one
+    sub = list(range(0, len(pairs), max(1, len(pairs) // 16)))[:16]
+    rows, run, total = 64 * row["scorers"]["extend_xdrop"]["rows_per_lane"], 0, 0
+    stops = []
+    for q, k in enumerate(sub):
+        t, p = w["text"][pairs[k][0]:pairs[k][0] + pairs[k][1]], w["pattern"][pairs[k][2]:pairs[k][2] + pairs[k][3]]
+        want = extend_rowwise_ref(t, p, w["S"], go, ge, xdrop)
+        g = res["extend_xdrop"][k]
+        assert (int(g["score"]), int(g["end_pattern"]), int(g["end_text"])) == want[:3], f"pair {k} differs from the reference at the X-drop"
+        if q % 4 == 0:
+            want0 = extend_rowwise_ref(t, p, w["S"], go, ge, None)
+            g = res["extend_no_xdrop"][k]
+            assert (int(g["score"]), int(g["end_pattern"]), int(g["end_text"])) == want0[:3], f"pair {k} differs from the reference without a drop"
+        stops.append(want[3])
+        run += -(-min(want[3], pairs[k][3]) // rows)
+        total += -(-pairs[k][3] // rows)
+    row["subsample"] = {"pairs": len(sub), "stop_rows": stops, "results_equal_the_reference": True,
+                        "model_strips_run_over_total": round(run / total, 4)}
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            ms[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    for k, s in sc.items():
+        row[k + "_run"] = stats(ms[k])
+        s.close()
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    row["xdrop_over_no_xdrop"] = round(med["extend_xdrop"] / med["extend_no_xdrop"], 4)
+    row["xdrop_over_local"] = round(med["extend_xdrop"] / med["local"], 4)
+    row["no_xdrop_over_local"] = round(med["extend_no_xdrop"] / med["local"], 4)
+    # aligned: the traced fill and the walk of the first pairs, with and without the drop, alternated
+    nal = min(len(pairs), 16 if args.small else 64)
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in pairs[:nal]]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in pairs[:nal]]
+    al = {k: {"fill_ms": [], "walk_ms": []} for k in ("xdrop", "no_xdrop")}
+    for rnd in range(1 + max(3, args.rounds // 2)):
+        for k in al:
+            got = engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, strings=False, xdrop=xdrop if k == "xdrop" else engine.NO_XDROP)
+            st = engine.affine_last_stats()
+            want = res["extend_xdrop" if k == "xdrop" else "extend_no_xdrop"]["score"][:nal].tolist()
+            assert [g["score"] for g in got] == want, "the aligner and the scorer differ"
+            if rnd:  # round 0 warms up
+                al[k]["fill_ms"].append(st["fill_ms"]), al[k]["walk_ms"].append(st["walk_ms"])
+            al[k]["arena_bytes"], al[k]["num_chunks"] = st["arena_bytes"], st["num_chunks"]
+    row["aligned"] = {"pairs": nal}
+    for k, v in al.items():
+        row["aligned"][k] = {"fill": stats(v["fill_ms"]), "walk": stats(v["walk_ms"]), "arena_bytes": v["arena_bytes"],
+                             "num_chunks": v["num_chunks"]}
+    return row
+
+
 def fit_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
     """The fit, global and local scorers of one gap model on the mapping workload, alternated."""
     cells = sum(p[1] * p[3] for p in w["pairs"])
@@ -545,27 +695,35 @@ def hits_row(args, engine, w, dt, dp) -> dict:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="profiles/r09/score_bench.json; --mode fit: profiles/r13/score_fit_bench.json")
-    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=None, help="timed rounds: 5, --mode extend 7")
     ap.add_argument("--small", action="store_true", help="a sixteenth of the batch, a tenth of the texts")
     ap.add_argument("--gap-extend", type=int, default=None, help="compare the affine scorer with the linear one")
     ap.add_argument("--gap-open", type=int, default=11, help="gap-open penalty of the affine scorer")
     ap.add_argument("--hits", type=int, default=None,
                     help="time search(k=HITS) on the search workload; with --gap-extend also its traced fill and its walk")
-    ap.add_argument("--mode", choices=["fit", "ends", "mapped"], default=None,
+    ap.add_argument("--exit-gap", type=int, nargs=2, default=[16, 4], metavar=("OPEN", "EXTEND"),
+                    help="--mode extend: the penalties of the early-exit comparison")
+    ap.add_argument("--xdrop", type=int, default=100, help="--mode extend: the X-drop of the early-exit comparison")
+    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
                          "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload; "
                          "mapped: the band-at fit scorer around each read's true offset against the unbanded fit scorer "
-                         "(profiles/r16/score_mapped_bench.json)")
+                         "(profiles/r16/score_mapped_bench.json); "
+                         "extend: the extension scorers against the local ones, with and without an X-drop "
+                         "(profiles/r17/score_extend_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--tree", default=None,
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
+    if args.rounds is None:
+        args.rounds = 7 if args.mode == "extend" else 5
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
                                                     ("r15", "score_ends_bench.json") if args.mode == "ends" else
-                                                    ("r16", "score_mapped_bench.json") if args.mode == "mapped" else ("r09", "score_bench.json")))
+                                                    ("r16", "score_mapped_bench.json") if args.mode == "mapped" else
+                                                    ("r17", "score_extend_bench.json") if args.mode == "extend" else ("r09", "score_bench.json")))
     if args.tree:
         sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
@@ -600,6 +758,20 @@ def main() -> int:
             row = mapped_rows(args, engine, w, dt, dp, gap, ge)
             report["workloads"].append(row)
             print(json.dumps(row), flush=True)
+        del dt, dp
+    elif args.mode == "extend":
+        w = mapping_workload(args.small)
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        for gap, ge in ((5, None), (args.gap_open, args.gap_extend if args.gap_extend is not None else 2)):
+            row = extend_same_work_rows(args, engine, w, dt, dp, gap, ge)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+        del dt, dp
+        w = chimeric_workload(args.small)
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        row = extend_early_exit_row(args, engine, w, dt, dp, args.exit_gap[0], args.exit_gap[1], args.xdrop)
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
         del dt, dp
     elif args.mode == "ends":
         report["library_build_id"] = engine.lib.sa_build_id().decode()
