@@ -209,6 +209,22 @@ uint64_t scoreSequencesGPUExtend(const Request *requests, uint64_t numRequests, 
 uint64_t alignSequencesGPUExtend(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                  int gapOpen, int gapExtend, int xdrop);
 
+/// Extension: seed extension (sa_score_batch_seeds, sa_align_pairs_seeds; sa_hip.h has the definition). Request
+/// k carries the seed text[seedTextPos[k] : + seedLength[k]] against pattern[seedPatternPos[k] : + seedLength[k]],
+/// which lies without a gap and is scored as it is; the extension alignment of what follows the seed and the
+/// one of what precedes it, both sequences read backwards in place, are joined with it in one call under one
+/// xdrop (-1, SA_NO_XDROP, never stops). The score is the sum of the three; Response::startInAlignedText and
+/// startInAlignedPattern are the 0-based indices of the first aligned letters, and the aligned strings are
+/// the left extension, the seed's letters and the right extension in forward order. Request::alignmentType
+/// and Request::gapPenalty are ignored; one alphabet and score matrix for all requests. A seed that does
+/// not lie inside its request fails the whole call. Returns 0, or 1 with the message on stdout.
+uint64_t scoreSequencesGPUSeeds(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                int xdrop, const uint64_t *seedTextPos, const uint64_t *seedPatternPos,
+                                const uint64_t *seedLength, int *scores);
+uint64_t alignSequencesGPUSeeds(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                int gapOpen, int gapExtend, int xdrop, const uint64_t *seedTextPos,
+                                const uint64_t *seedPatternPos, const uint64_t *seedLength);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

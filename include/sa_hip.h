@@ -443,7 +443,8 @@ int sa_band_reachable(int32_t mode, uint64_t text_len, uint64_t pattern_len, sa_
  * every output of SA_NO_XDROP (under the score limit no difference B - r reaches 2^30). (I3) Under
  * non-negative penalties the SA_NO_XDROP score is >= max(0, the score of SA_ENDS_FREE | TE | PE).
  * (I4) gap_open == gap_extend == g is the linear recurrence of gap penalty g, and the scorers then run
- * the linear kernels. Extending to the left of a seed is the same call on both sequences reversed.
+ * the linear kernels. Extending to the left of a seed is the same call on both sequences reversed: the
+ * seeds functions below do both sides in one call and reverse nothing.
  * params->mode must be SA_GLOBAL (the borders are global's), else SA_ERR_INVALID; xdrop < -1 or
  * xdrop >= 2^30 is SA_ERR_INVALID. One xdrop serves all pairs of a call. The limits are those of the
  * unbanded affine functions and of local mode's best-cell key (SA_ERR_UNSUPPORTED). There is no band.
@@ -458,8 +459,63 @@ int sa_align_pairs_extend(const sa_params *params, int32_t gap_open, int32_t gap
                           const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
                           char *const *aligned_text, char *const *aligned_pattern);
 
+/* ---- seed extension: both ways from a seed, the left side read in place ----------------------- */
+
+/* seeds[k] belongs to pair k, text t of n letters and pattern p of m letters, and says that
+ * t[text_pos : text_pos + length] lies against p[pattern_pos : pattern_pos + length] without a gap; ts,
+ * ps and L below. L = 0 is a bare anchor point. The seed's letters need not match: they are scored as
+ * they are.
+ *   right half: extension alignment of t[ts + L :] against p[ps + L :], exactly what sa_score_batch_extend
+ *               defines under gap_open, gap_extend and xdrop
+ *   left half:  extension alignment of reverse(t[: ts]) against reverse(p[: ps]), the same definition; the
+ *               rows of its X-drop are rows of that reversed matrix. Nothing is reversed or copied: the
+ *               kernels read the two prefixes backwards where they lie
+ *   seed score: the sum over q < L of S[p[ps + q]][t[ts + q]]
+ *   result:     score = left.score + seed + right.score; begin_text = ts - left.end_text,
+ *               begin_pattern = ps - left.end_pattern, end_text = ts + L + right.end_text,
+ *               end_pattern = ps + L + right.end_pattern: the alignment covers t[begin_text : end_text] and
+ *               p[begin_pattern : end_pattern]
+ *   strings:    reverse(left.aligned) + the seed's L letters + right.aligned, on both sides. In sa_result
+ *               start_text = begin_text, start_pattern = begin_pattern and num_alignment_bytes is the sum of
+ *               the three lengths, without quirks; an empty result (L = 0, both halves empty) has
+ *               start = (ts, ps)
+ *   empty half: ts == 0, ps == 0 or a seed that reaches an end: the half scores 0 with an empty alignment,
+ *               extension's own rule
+ * Identities: (S1) every output equals this composition of the extension functions on host-sliced and
+ * host-reversed copies. (S2) The seed {0, 0, 0} gives every output of the _extend function, with
+ * begin = (0, 0). (S3) Mirror: the pair reverse(t), reverse(p) with the seed {n - ts - L, m - ps - L, L} has
+ * the same score, begin' = (n - end_text, m - end_pattern), end' = (n - begin_text, m - begin_pattern) and
+ * both strings reversed; its left half is this pair's right half, so the identity is exact, ties
+ * included. (S4) gap_open == gap_extend runs the linear kernels, as (I4) of extension.
+ * Refusals: params->mode other than SA_GLOBAL or a bad xdrop as the extension functions have them;
+ * seeds == NULL with num_pairs > 0, ts + L > n or ps + L > m: SA_ERR_INVALID, the first such pair's index
+ * in sa_last_error(); a byte outside the alphabet that a kernel reads, the seed's letters included:
+ * SA_ERR_INVALID. The score limit and the best-cell key limit are the extension functions', applied to the
+ * whole pair's (n, m), which covers the sum. There is no band.
+ * A seeds scorer works with sa_scorer_run, _info and _destroy, any number of times on new arena contents;
+ * sa_scorer_fetch on it gives the score with end_text and end_pattern, both absolute, and
+ * sa_scorer_fetch_seeds on any other scorer is SA_ERR_INVALID. Its device memory is the extension scorer's
+ * plus the work items (a pair's non-empty halves) and their results. sa_align_pairs_seeds keeps direction
+ * bytes for the two rectangles ps x ts and (m - ps - L) x (n - ts - L), each as a global pair of that shape,
+ * never for n x m: a seeded pair whose full directions exceed SA_TRACE_ARENA_BYTES aligns, and a pair is
+ * SA_ERR_UNSUPPORTED only when its two halves together exceed it (they share a chunk).
+ * sa_affine_last_stats reports the call. */
+typedef struct sa_seed { uint64_t text_pos, pattern_pos, length; } sa_seed;
+typedef struct sa_seed_result {
+    int32_t score, status;
+    uint64_t begin_text, begin_pattern, end_text, end_pattern;
+} sa_seed_result;
+int sa_score_batch_seeds(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                         const sa_host_pair *pairs, int64_t num_pairs, int device, sa_seed_result *out);
+int sa_scorer_create_seeds(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                           const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_scorer_fetch_seeds(sa_scorer *scorer, sa_seed_result *out, void *stream);
+int sa_align_pairs_seeds(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                         const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                         char *const *aligned_text, char *const *aligned_pattern);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
- * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend or sa_search_affine (k > 0): device
+ * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend, sa_align_pairs_seeds or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

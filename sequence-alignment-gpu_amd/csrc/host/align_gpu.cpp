@@ -202,10 +202,12 @@ namespace
 // linear gapPenalty, else {gap open, gap extend} and gapPenalty is ignored; `band` non-null is the
 // band's half-width; `ends` non-null is scoreSequencesGPUEndsFree with these flags; `lo` and `hi` non-null
 // are scoreSequencesGPUBandAt's per-request bands; `xdrop` non-null is scoreSequencesGPUExtend (the mode is
-// SA_GLOBAL, whose borders an extension has, and Request::alignmentType is ignored)
+// SA_GLOBAL, whose borders an extension has, and Request::alignmentType is ignored); `seeds` non-null (with
+// `xdrop`) is scoreSequencesGPUSeeds
 uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
                        int *scores, const char *name, const int *band = nullptr, const int *ends = nullptr,
-                       const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr)
+                       const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr,
+                       const std::vector<sa_seed> *seeds = nullptr)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -231,6 +233,17 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
     std::vector<sa_score_result> res(numRequests);
     std::vector<sa_band> bands;
     for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
+    if (seeds)
+    {
+        std::vector<sa_seed_result> sres(numRequests);
+        if (sa_score_batch_seeds(&params[0], gap[0], gap[1], *xdrop, seeds->data(), pairs.data(), (int64_t)numRequests, device, sres.data()) != SA_OK)
+        {
+            std::cout << "error: " + std::string(sa_last_error()) + "\n";
+            return 1;
+        }
+        for (uint64_t i = 0; i < numRequests; ++i) scores[i] = sres[i].score;
+        return 0;
+    }
     const int rc = xdrop ? sa_score_batch_extend(&params[0], gap[0], gap[1], *xdrop, pairs.data(), (int64_t)numRequests, device, res.data())
                    : lo ? sa_score_batch_band_at(&params[0], gap[0], gap[1], bands.data(), pairs.data(), (int64_t)numRequests, device, res.data())
                    : band ? sa_score_batch_banded(&params[0], gap[0], gap[1], *band, pairs.data(), (int64_t)numRequests, device, res.data())
@@ -246,10 +259,25 @@ uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numR
 }
 
 // alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded; with `ends`, alignSequencesGPUEndsFree;
-// with `lo` and `hi`, alignSequencesGPUBandAt; with `xdrop`, alignSequencesGPUExtend
+// with `lo` and `hi`, alignSequencesGPUBandAt; with `xdrop`, alignSequencesGPUExtend; with `seeds` too,
+// alignSequencesGPUSeeds
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
                        int device, int gapOpen, int gapExtend, const int *band, const std::string &name,
-                       const int *ends = nullptr, const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr);
+                       const int *ends = nullptr, const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr,
+                       const std::vector<sa_seed> *seeds = nullptr);
+
+// the seeds of the ...Seeds functions: three arrays, one entry per request
+bool seedsOk(const uint64_t *textPos, const uint64_t *patternPos, const uint64_t *length, uint64_t numRequests, const char *name,
+             std::vector<sa_seed> *seeds)
+{
+    if (numRequests && (!textPos || !patternPos || !length))
+    {
+        std::cout << "error: " << name << " needs seedTextPos, seedPatternPos and seedLength, one entry per request\n";
+        return false;
+    }
+    for (uint64_t i = 0; i < numRequests; ++i) seeds->push_back(sa_seed{textPos[i], patternPos[i], length[i]});
+    return true;
+}
 
 // the mode argument of the band-at functions: -1 leaves the mode to Request::alignmentType
 bool bandAtArgsOk(int freeEnds, const int *lo, const int *hi, uint64_t numRequests, const char *name)
@@ -292,6 +320,27 @@ uint64_t SequenceAlignment::alignSequencesGPUExtend(const Request *requests, Res
 {
     return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUExtend", nullptr, nullptr,
                          nullptr, &xdrop);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUSeeds(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                                   int xdrop, const uint64_t *seedTextPos, const uint64_t *seedPatternPos,
+                                                   const uint64_t *seedLength, int *scores)
+{
+    std::vector<sa_seed> seeds;
+    if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "scoreSequencesGPUSeeds", &seeds)) return 1;
+    const int gap[2] = {gapOpen, gapExtend};
+    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUSeeds", nullptr, nullptr, nullptr, nullptr, &xdrop,
+                         &seeds);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUSeeds(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                                   int gapOpen, int gapExtend, int xdrop, const uint64_t *seedTextPos,
+                                                   const uint64_t *seedPatternPos, const uint64_t *seedLength)
+{
+    std::vector<sa_seed> seeds;
+    if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "alignSequencesGPUSeeds", &seeds)) return 1;
+    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUSeeds", nullptr, nullptr,
+                         nullptr, &xdrop, &seeds);
 }
 
 uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
@@ -344,7 +393,7 @@ namespace
 {
 uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
                        int device, int gapOpen, int gapExtend, const int *band, const std::string &name, const int *ends,
-                       const int *lo, const int *hi, const int *xdrop)
+                       const int *lo, const int *hi, const int *xdrop, const std::vector<sa_seed> *seeds)
 {
     if (numRequests == 0) return 0;
     std::vector<sa_params> params(numRequests);
@@ -374,7 +423,9 @@ uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlign
     std::vector<sa_result> res(numRequests);
     std::vector<sa_band> bands;
     for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
-    const int rc = xdrop ? sa_align_pairs_extend(&params[0], gapOpen, gapExtend, *xdrop, pairs.data(), (int64_t)numRequests, device,
+    const int rc = seeds ? sa_align_pairs_seeds(&params[0], gapOpen, gapExtend, *xdrop, seeds->data(), pairs.data(), (int64_t)numRequests,
+                                                device, res.data(), at.data(), ap.data())
+                   : xdrop ? sa_align_pairs_extend(&params[0], gapOpen, gapExtend, *xdrop, pairs.data(), (int64_t)numRequests, device,
                                                  res.data(), at.data(), ap.data())
                    : lo ? sa_align_pairs_band_at(&params[0], gapOpen, gapExtend, bands.data(), pairs.data(), (int64_t)numRequests, device,
                                                  res.data(), at.data(), ap.data())

@@ -11,6 +11,10 @@
 // [1, 0, 0, 0]).
 // With --extend X it is the extension scorer's (sa_score_batch_extend; "none" is SA_NO_XDROP), which takes
 // --gap-extend and prints "extend": true and "xdrop".
+// With --seeds TS:PS:L (once for all pairs, or once per shape argument, in their order) it is the seeds
+// scorer's (sa_score_batch_seeds) under the xdrop of --extend (none without it): "items" lists the work
+// items, "halves" every pair's [left, right] item (-1: empty), and "order", "num_pairs", "grid", "R" and the
+// bytes are those of the items. With a band of either kind the call is refused as --extend with a band is.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -38,6 +42,9 @@ int main(int argc, char **argv)
     int32_t xdrop = SA_NO_XDROP;
     ScoreGap gapm = {0, 0};
     std::vector<sa_pair> pairs;
+    std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
+    std::vector<size_t> shape_of;      // the shape argument of each pair
+    size_t num_shapes = 0;
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -77,6 +84,16 @@ int main(int argc, char **argv)
             const std::string v = value();
             xdrop = v == "none" ? SA_NO_XDROP : std::atoi(v.c_str());
         }
+        else if (a == "--seeds")
+        {
+            unsigned long long ts = 0, ps = 0, len = 0;
+            if (std::sscanf(value(), "%llu:%llu:%llu", &ts, &ps, &len) != 3)
+            {
+                std::fprintf(stderr, "sa_score_plan_check: --seeds takes TS:PS:L\n");
+                return 2;
+            }
+            shape_seeds.push_back(sa_seed{ts, ps, len});
+        }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
         else if (a == "--match") match = std::atoi(value());
@@ -97,7 +114,9 @@ int main(int argc, char **argv)
                 pr.pattern_offset = pairs.empty() ? 0 : pairs.back().pattern_offset + pairs.back().pattern_len;
                 pr.pattern_len = m;
                 pairs.push_back(pr);
+                shape_of.push_back(num_shapes);
             }
+            ++num_shapes;
         }
     }
     const int a = std::min(std::max(P.alphabet_size, 1), 64);
@@ -110,8 +129,21 @@ int main(int argc, char **argv)
     ScorePlan pl;
     std::string err;
     const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
-    const int rc = make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr,
-                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr, extend ? &ext : nullptr);
+    // --seeds: the seeds scorer; with a band of either kind the call is the extension scorer's, refused as it is
+    const bool seeded = !shape_seeds.empty() && !banded && !band_at;
+    if (seeded && shape_seeds.size() != 1 && shape_seeds.size() != num_shapes)
+    {
+        std::fprintf(stderr, "sa_score_plan_check: --seeds once, or once per shape\n");
+        return 2;
+    }
+    std::vector<sa_seed> seeds;
+    for (size_t i = 0; seeded && i < pairs.size(); ++i) seeds.push_back(shape_seeds[shape_seeds.size() == 1 ? 0 : shape_of[i]]);
+    SeedItems si;
+    const int rc = seeded ? make_seeds_score_plan(&P, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &si, &err,
+                                                  affine ? &gapm : nullptr, &ext)
+                          : make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr,
+                                            banded ? &band : nullptr, band_at ? bands.data() : nullptr,
+                                            extend || !shape_seeds.empty() ? &ext : nullptr);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -128,7 +160,21 @@ int main(int argc, char **argv)
     // the order of a large batch is long: the first 64 entries
     for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
     std::printf("]");
-    if (extend) std::printf(", \"extend\": true, \"xdrop\": %d", pl.xdrop);
+    if (extend || seeded) std::printf(", \"extend\": true, \"xdrop\": %d", pl.xdrop);
+    if (seeded)
+    {
+        // the work items (the first 128): "order" above lists item indices, "num_pairs" counts items
+        std::printf(", \"seeds\": true, \"num_seed_pairs\": %zu, \"items\": [", pairs.size());
+        for (size_t k = 0; k < si.items.size() && k < 128; ++k)
+        {
+            const SeedItem &it = si.items[k];
+            std::printf("%s{\"pair\": %d, \"dir\": %d, \"text_off\": %llu, \"pattern_off\": %llu, \"n\": %u, \"m\": %u}", k ? ", " : "",
+                        it.pair, it.dir, (unsigned long long)it.text_off, (unsigned long long)it.pattern_off, it.n, it.m);
+        }
+        std::printf("], \"halves\": [");
+        for (size_t p = 0; p < si.pairs.size() && p < 64; ++p) std::printf("%s[%d, %d]", p ? ", " : "", si.pairs[p].left, si.pairs[p].right);
+        std::printf("]");
+    }
     if (banded || band_at)
     {
         std::printf(", \"band\": %d, \"band_cells\": %llu, \"bands\": [", pl.band, (unsigned long long)pl.band_cells);

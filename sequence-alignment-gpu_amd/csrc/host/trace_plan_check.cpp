@@ -8,6 +8,11 @@
 // [b0, b1] bodies of its strips' windows (the first 64 strips). With --band-at LO:HI it is the band-at
 // aligner's, the one band applied to every pair, with the same output (an empty strip's window is [0, 0]). Without --budget the budget is SA_TRACE_ARENA_BYTES or the default.
 // With --extend X it is the extension aligner's (sa_align_pairs_extend; "none" is SA_NO_XDROP).
+// With --seeds TS:PS:L (once for all pairs, or once per shape argument, in their order) it is the seeds
+// aligner's (sa_align_pairs_seeds) under the xdrop of --extend: "items" lists the work items with their
+// direction bytes and offsets, "order" the items chunk by chunk ("chunk_begin"), "pair_order" and
+// "pair_chunk_begin" the pairs of each chunk's walk. With a band of either kind the call is refused as
+// --extend with a band is.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -34,6 +39,9 @@ int main(int argc, char **argv)
     bool extend = false;
     int32_t xdrop = SA_NO_XDROP;
     std::vector<sa_pair> pairs;
+    std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
+    std::vector<size_t> shape_of;      // the shape argument of each pair
+    size_t num_shapes = 0;
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -51,6 +59,16 @@ int main(int argc, char **argv)
             extend = true;
             const std::string v = value();
             xdrop = v == "none" ? SA_NO_XDROP : std::atoi(v.c_str());
+        }
+        else if (a == "--seeds")
+        {
+            unsigned long long ts = 0, ps = 0, len = 0;
+            if (std::sscanf(value(), "%llu:%llu:%llu", &ts, &ps, &len) != 3)
+            {
+                std::fprintf(stderr, "sa_trace_plan_check: --seeds takes TS:PS:L\n");
+                return 2;
+            }
+            shape_seeds.push_back(sa_seed{ts, ps, len});
         }
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--budget") budget = std::strtoull(value(), nullptr, 10);
@@ -89,7 +107,9 @@ int main(int argc, char **argv)
                 pr.pattern_offset = pairs.empty() ? 0 : pairs.back().pattern_offset + pairs.back().pattern_len;
                 pr.pattern_len = m;
                 pairs.push_back(pr);
+                shape_of.push_back(num_shapes);
             }
+            ++num_shapes;
         }
     }
     const int a = std::min(std::max(P.alphabet_size, 1), 64);
@@ -97,8 +117,56 @@ int main(int argc, char **argv)
     for (int c = 0; c < a; ++c) S[(size_t)c * a + c] = match;
     P.score_matrix = S.data();
 
-    TracePlan pl;
     std::string err;
+    // --seeds: the seeds aligner; with a band of either kind the call is the extension aligner's, refused as it is
+    if (!shape_seeds.empty() && !banded && !band_at)
+    {
+        if (shape_seeds.size() != 1 && shape_seeds.size() != num_shapes)
+        {
+            std::fprintf(stderr, "sa_trace_plan_check: --seeds once, or once per shape\n");
+            return 2;
+        }
+        std::vector<sa_seed> seeds;
+        for (size_t i = 0; i < pairs.size(); ++i) seeds.push_back(shape_seeds[shape_seeds.size() == 1 ? 0 : shape_of[i]]);
+        SeedTracePlan sp;
+        const int rc = make_seeds_trace_plan(&P, go, ge, xdrop, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), budget,
+                                             &sp, &err);
+        if (rc != SA_OK)
+        {
+            std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+            return 0;
+        }
+        std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"gap_extend\": %d, \"R\": %d, \"grid\": %d, \"num_pairs\": %lld, \"num_items\": %zu, "
+                    "\"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, \"num_chunks\": %lld, "
+                    "\"seeds\": true, \"xdrop\": %d, \"chunk_begin\": [",
+                    sp.score.mode, sp.score.A, sp.score.gap, sp.score.gap_extend, sp.score.R, sp.score.grid, (long long)sp.num_pairs,
+                    sp.seeds.items.size(), (unsigned long long)sp.budget, (unsigned long long)sp.arena_bytes,
+                    (unsigned long long)sp.total_dir_bytes, (unsigned long long)sp.string_bytes, (long long)sp.num_chunks(), sp.score.xdrop);
+        for (size_t i = 0; i < sp.chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)sp.chunk_begin[i]);
+        std::printf("], \"pair_chunk_begin\": [");
+        for (size_t i = 0; i < sp.pair_chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)sp.pair_chunk_begin[i]);
+        std::printf("], \"order\": [");
+        for (size_t i = 0; i < sp.score.order.size() && i < 128; ++i) std::printf("%s%d", i ? ", " : "", sp.score.order[i]);
+        std::printf("], \"pair_order\": [");
+        for (size_t i = 0; i < sp.pair_order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", sp.pair_order[i]);
+        std::printf("], \"items\": [");
+        for (size_t k = 0; k < sp.seeds.items.size() && k < 128; ++k)
+        {
+            const SeedItem &it = sp.seeds.items[k];
+            std::printf("%s{\"pair\": %d, \"dir\": %d, \"text_off\": %llu, \"pattern_off\": %llu, \"n\": %u, \"m\": %u, \"dir_bytes\": %llu, "
+                        "\"dir_off\": %llu}",
+                        k ? ", " : "", it.pair, it.dir, (unsigned long long)it.text_off, (unsigned long long)it.pattern_off, it.n, it.m,
+                        (unsigned long long)sp.dir_bytes[k], (unsigned long long)sp.dir_off[k]);
+        }
+        std::printf("], \"pairs\": [");
+        for (size_t p = 0; p < pairs.size() && p < 64; ++p)
+            std::printf("%s{\"left\": %d, \"right\": %d, \"slot_off\": %llu}", p ? ", " : "", sp.seeds.pairs[p].left, sp.seeds.pairs[p].right,
+                        (unsigned long long)sp.slot_off[p]);
+        std::printf("]}\n");
+        return 0;
+    }
+    if (!shape_seeds.empty()) extend = true;
+    TracePlan pl;
     const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
     const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err,
                                    banded ? &band : nullptr, band_at ? bands.data() : nullptr, extend ? &xdrop : nullptr);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "sa_hip.h"
+#include "sa_score_plan.h"
 
 namespace sa {
 
@@ -18,5 +19,27 @@ int align_affine_device(const sa_params *P, int32_t gap_open, int32_t gap_extend
                         int device, const void *d_text, const void *d_pattern, sa_result *results,
                         char *const *aligned_text, char *const *aligned_pattern, const int32_t *band = nullptr,
                         bool with_bands = false, const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
+
+// Seed extension (sa_hip.h sa_score_batch_seeds): seeds_combine_kernel (sa_score.hip), one wave per pair
+// after the items' fill, shared by the seeds scorer and the seeds aligner. It sums the seed's scores, flags
+// a seed letter outside the alphabet in ctrl[1] and writes the pair's sa_seed_result from the results of
+// its items. `stream` is a hipStream_t.
+struct SeedsCombineArgs {
+    const int8_t *text, *pattern;
+    const SeedPair *pairs;
+    const int32_t *order;              // workgroup w combines pair order[w]; null: pair w
+    const int32_t *table;              // A x A scores, [pattern][text]
+    const sa_score_result *item_out;   // the fill's result of every item
+    sa_seed_result *out;
+    uint32_t *ctrl;
+    int32_t A;
+};
+void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream);
+
+// sa_align_pairs_seeds on device arenas: the traced fill of the work items, the combine and the seeded walk,
+// chunk by chunk (sa_trace_plan.h SeedTracePlan); arguments as align_affine_device.
+int align_seeds_device(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                       const sa_pair *pairs, int64_t np, int device, const void *d_text, const void *d_pattern,
+                       sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
 
 }  // namespace sa

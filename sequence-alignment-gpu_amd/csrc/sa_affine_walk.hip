@@ -282,6 +282,173 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     }
 }
 
+// align_extend_kernel on work items (sa_hip.h sa_align_pairs_seeds; sa_score_wave.h: SEED): a.order, a.np,
+// a.out and tr.dir_off speak of items; an item stores the words of a global pair of its shape
+struct AlignSeedsArgs {
+    AlignExtendArgs xa;
+    const SeedItem *items;
+};
+
+template <bool SMALL>
+__global__ __launch_bounds__(64) void align_seeds_kernel(AlignSeedsArgs sa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, kTraceRows, SA_GLOBAL, SMALL, true, false, false, false, true, true>(sa.xa.a.sa.s, sa.xa.a.sa.gap_extend, tab, sa.xa.a.tr, 0, 0,
+                                                                                         nullptr, sa.xa.xdrop, sa.items);
+}
+
+struct SeedWalkArgs {
+    const int8_t *text, *pattern;
+    const SeedItem *items;
+    const SeedPair *pairs;
+    const int32_t *order;             // the chunk's part of the pair order: workgroup w walks pair order[w]
+    const sa_score_result *scores;    // the fill's score and end cell of every item
+    const sa_seed_result *seed_out;   // the combine's result of every pair
+    const uint32_t *dirs;             // the chunk's direction arena
+    const uint64_t *dir_off;          // per item, in words
+    const uint64_t *slot_off;         // num_pairs + 1 entries: pair p's slot is bytes slot_off[p] .. slot_off[p + 1] - 1
+    char *out_text, *out_pattern;     // both null: results only
+    const char *alphabet;
+    sa_result *results;
+    uint64_t *tail_len;               // per pair: the bytes of the right half's piece, at the end of the slot
+    int32_t A;
+};
+
+// The walk of one work item, walk_affine_kernel<0>'s for an extension: from the fill's result cell to the
+// origin, row 0 forcing LEFT and column 0 TOP, the direction words read through the same 64-step window.
+// Letter j of the item's text is tbase[dir * (j - 1)], as the fill read it. LEFT false writes emission k to
+// out[-1 - k], backwards from the end of the pair's slot, as every other walk does. LEFT true writes it to
+// out[k]: the left half's matrix is that of the reversed prefixes, so its walk from the end cell to the
+// origin meets the columns of the final alignment in forward order. Returns the number of emissions;
+// *ended is false for a walk that did not reach the origin within n + m moves.
+template <bool LEFT>
+__device__ __forceinline__ int seed_walk_item(const SeedWalkArgs &a, int item, char *out_t, char *out_p, bool *ended)
+{
+    const int lane = threadIdx.x;
+    const SeedItem sd = a.items[item];
+    const int n = uniform((int)sd.n), m = uniform((int)sd.m), dir = uniform(sd.dir);
+    const sa_score_result sr = a.scores[item];
+    const int8_t *const text = a.text + sd.text_off;
+    const int8_t *const pattern = a.pattern + sd.pattern_off;
+    const uint32_t *const dirs = a.dirs + uniform64(a.dir_off[item]);
+    const uint32_t strip_words = (uint32_t)((n + 126) / 64) * (64u * 64u);
+    const int A = a.A;
+    int i = min(uniform((int)sr.end_pattern), m), j = min(uniform((int)sr.end_text), n);
+    int state = kDirDiag, len = 0;
+    int cur = -1, t0 = 0;
+    uint32_t win = 0;
+    int ri = 0, rj = 0, rd = 0;
+    const bool strings = out_t != nullptr;
+    auto flush = [&](int base, int count) {
+        if (strings && lane < count)
+        {
+            const bool tt = rd == kDirDiag || rd == kDirLeft, tp = rd == kDirDiag || rd == kDirTop;
+            const int ct = tt ? min(max((int)text[(rj - 1) * dir], 0), A - 1) : A;
+            const int cp = tp ? min(max((int)pattern[(ri - 1) * dir], 0), A - 1) : A;
+            const int64_t at = LEFT ? (int64_t)(base + lane) : -1 - (int64_t)(base + lane);
+            out_t[at] = a.alphabet[ct];
+            out_p[at] = a.alphabet[cp];
+        }
+    };
+    *ended = false;
+    const int max_moves = n + m;
+    for (int it = 0;; ++it)
+    {
+        if (i == 0 && j == 0)
+        {
+            *ended = true;
+            break;
+        }
+        if (it >= max_moves) break;
+        int d, next = kDirDiag;
+        if (j == 0) d = kDirTop;
+        else if (i == 0) d = kDirLeft;
+        else
+        {
+            const int col = (i - 1) >> 3, l = col & 63;
+            const int t = j - 1 + l;
+            if (col != cur || t0 - t >= 64)
+            {
+                const int step = t - lane;
+                win = step >= 0 ? dirs[(uint64_t)(col >> 6) * strip_words + ((uint32_t)step * 64u + (uint32_t)l)] : 0u;
+                cur = col;
+                t0 = t;
+            }
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)win, t0 - t);
+            const int nib = (int)(word >> (4 * ((i - 1) & 7))) & 15;
+            d = state == kDirDiag ? (nib & 3) : state;
+            if (d == kDirStop) break;  // no extension cell holds it
+            if (d == kDirLeft) next = nib & kDirEExt ? kDirLeft : kDirDiag;
+            if (d == kDirTop) next = nib & kDirFExt ? kDirTop : kDirDiag;
+        }
+        if (lane == (len & 63))
+        {
+            ri = i;
+            rj = j;
+            rd = d;
+        }
+        ++len;
+        j -= d == kDirDiag || d == kDirLeft;
+        i -= d == kDirDiag || d == kDirTop;
+        state = next;
+        if ((len & 63) == 0) flush(len - 64, 64);
+    }
+    flush(len & ~63, len & 63);
+    return len;
+}
+
+// One wave per pair: the left item's walk written forwards from the start of the pair's slot, the seed's
+// letters after it, and the right item's walk written backwards from the slot's end. The three lengths
+// sum to at most n + m - L, so the slot of n + m bytes holds the head piece and the tail piece apart; the
+// host joins them (tail_len). The result's score and starts are the combine's.
+__global__ __launch_bounds__(64) void walk_seeds_kernel(SeedWalkArgs a)
+{
+    const int lane = threadIdx.x;
+    const int pi = uniform(a.order[blockIdx.x]);
+    const SeedPair sp = a.pairs[pi];
+    const uint64_t slot = uniform64(a.slot_off[pi]), slot_end = uniform64(a.slot_off[pi + 1]);
+    const bool strings = a.out_text != nullptr;
+    const int left = uniform(sp.left), right = uniform(sp.right);
+    const uint64_t L = uniform64(sp.len);
+    bool ok = true;
+    int len_l = 0, len_r = 0;
+    if (left >= 0)
+    {
+        bool ended;
+        len_l = seed_walk_item<true>(a, left, strings ? a.out_text + slot : nullptr, strings ? a.out_pattern + slot : nullptr, &ended);
+        ok = ok && ended;
+    }
+    if (strings)
+    {
+        const int8_t *const ts = a.text + uniform64(sp.text_seed);
+        const int8_t *const ps = a.pattern + uniform64(sp.pattern_seed);
+        char *const ot = a.out_text + slot + (uint64_t)len_l, *const op = a.out_pattern + slot + (uint64_t)len_l;
+        for (uint64_t q = (uint64_t)lane; q < L; q += kWave)
+        {
+            ot[q] = a.alphabet[min(max((int)ts[q], 0), a.A - 1)];
+            op[q] = a.alphabet[min(max((int)ps[q], 0), a.A - 1)];
+        }
+    }
+    if (right >= 0)
+    {
+        bool ended;
+        len_r = seed_walk_item<false>(a, right, strings ? a.out_text + slot_end : nullptr, strings ? a.out_pattern + slot_end : nullptr, &ended);
+        ok = ok && ended;
+    }
+    if (lane == 0)
+    {
+        const sa_seed_result so = a.seed_out[pi];
+        sa_result r;
+        r.score = so.score;
+        r.status = ok ? SA_OK : SA_ERR_HIP;
+        r.num_alignment_bytes = (uint64_t)len_l + L + (uint64_t)len_r;
+        r.start_text = so.begin_text;
+        r.start_pattern = so.begin_pattern;
+        a.results[pi] = r;
+        a.tail_len[pi] = (uint64_t)len_r;
+    }
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -629,7 +796,227 @@ static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_ex
                                aligned_pattern, band, with_bands, bands, xdrop);
 }
 
+int sa::align_seeds_device(const sa_params *P, int32_t go, int32_t ge, int32_t xdrop, const sa_seed *seeds, const sa_pair *pairs,
+                           int64_t np, int device, const void *d_text, const void *d_pattern, sa_result *results,
+                           char *const *aligned_text, char *const *aligned_pattern)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
+        return fail(SA_ERR_INVALID, "seeds aligner: null argument");
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    SeedTracePlan pl;
+    std::string err;
+    if (int rc = make_seeds_trace_plan(P, go, ge, xdrop, pairs, seeds, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err))
+        return fail(rc, err);
+    if (!P->alphabet) return fail(SA_ERR_INVALID, "seeds aligner: params->alphabet is null");
+    g_stats = AffineStats();
+    g_stats.arena_bytes = pl.arena_bytes;
+    g_stats.chunks = (int32_t)pl.num_chunks();
+    if (np == 0) return SA_OK;
+    if ((!d_text || !d_pattern) && pl.score.input_bytes) return fail(SA_ERR_INVALID, "seeds aligner: null arena");
+    const int A = pl.score.A;
+    const size_t ni = pl.seeds.items.size();
+
+    std::vector<uint64_t> dir_words(ni), slots((size_t)np + 1);
+    for (size_t k = 0; k < ni; ++k) dir_words[k] = pl.dir_off[k] / 4;
+    for (int64_t p = 0; p < np; ++p) slots[p] = pl.slot_off[p];
+    slots[(size_t)np] = pl.string_bytes;
+    Workspace ws;
+    SeedItem *d_items;
+    SeedPair *d_seed_pairs;
+    int32_t *d_order, *d_pair_order, *d_table, *d_rows;
+    sa_score_result *d_scores;
+    sa_seed_result *d_seed_out;
+    uint32_t *d_ctrl, *d_dirs;
+    uint64_t *d_dir_off, *d_slot_off, *d_tail;
+    char *d_ot = nullptr, *d_op = nullptr, *d_alpha;
+    sa_result *d_results;
+    int rc;
+    if ((rc = ws.alloc(&d_items, ni * sizeof(SeedItem))) || (rc = ws.alloc(&d_seed_pairs, (size_t)np * sizeof(SeedPair))) ||
+        (rc = ws.alloc(&d_order, ni * 4)) || (rc = ws.alloc(&d_pair_order, (size_t)np * 4)) || (rc = ws.alloc(&d_table, 32 * 32 * 4)) ||
+        (rc = ws.alloc(&d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) || (rc = ws.alloc(&d_scores, ni * sizeof(sa_score_result))) ||
+        (rc = ws.alloc(&d_seed_out, (size_t)np * sizeof(sa_seed_result))) || (rc = ws.alloc(&d_ctrl, 256)) ||
+        (rc = ws.alloc(&d_dirs, pl.arena_bytes)) || (rc = ws.alloc(&d_dir_off, ni * 8)) || (rc = ws.alloc(&d_slot_off, ((size_t)np + 1) * 8)) ||
+        (rc = ws.alloc(&d_tail, (size_t)np * 8)) || (rc = ws.alloc(&d_alpha, 64)) || (rc = ws.alloc(&d_results, (size_t)np * sizeof(sa_result))))
+        return rc;
+    const bool strings = aligned_text != nullptr;
+    if (strings && ((rc = ws.alloc(&d_ot, pl.string_bytes)) || (rc = ws.alloc(&d_op, pl.string_bytes)))) return rc;
+    if (ni)
+    {
+        HIP_TRY(hipMemcpy(d_items, pl.seeds.items.data(), ni * sizeof(SeedItem), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_order, pl.score.order.data(), ni * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_dir_off, dir_words.data(), ni * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(d_seed_pairs, pl.seeds.pairs.data(), (size_t)np * sizeof(SeedPair), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pair_order, pl.pair_order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_slot_off, slots.data(), slots.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_alpha, P->alphabet, (size_t)A + 1, hipMemcpyHostToDevice));
+
+    hipStream_t st = nullptr;
+    const int64_t nchunks = pl.num_chunks();
+    ws.events.reserve((size_t)nchunks * 3);
+    for (int64_t e = 0; e < nchunks * 3; ++e)
+    {
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreate(&ev));
+        ws.events.push_back(ev);
+    }
+    HIP_TRY(hipMemsetAsync(d_ctrl, 0, 256, st));
+    AlignSeedsArgs fa;
+    ScoreArgs &s = fa.xa.a.sa.s;
+    s.text = (const int8_t *)d_text;
+    s.pattern = (const int8_t *)d_pattern;
+    s.pairs = nullptr;
+    s.table = d_table;
+    s.rows = d_rows;
+    s.out = d_scores;
+    s.ctrl = d_ctrl;
+    s.A = A;
+    s.gap = go;
+    s.key_rowbits = pl.score.key_rowbits;
+    s.row_stride = pl.score.row_stride;
+    fa.xa.a.sa.gap_extend = ge;
+    fa.xa.a.tr.dirs = d_dirs;
+    fa.xa.a.tr.dir_off = d_dir_off;
+    fa.xa.xdrop = xdrop;
+    fa.items = d_items;
+    SeedsCombineArgs ca;
+    ca.text = s.text;
+    ca.pattern = s.pattern;
+    ca.pairs = d_seed_pairs;
+    ca.table = d_table;
+    ca.item_out = d_scores;
+    ca.out = d_seed_out;
+    ca.ctrl = d_ctrl;
+    ca.A = A;
+    SeedWalkArgs wa;
+    wa.text = s.text;
+    wa.pattern = s.pattern;
+    wa.items = d_items;
+    wa.pairs = d_seed_pairs;
+    wa.scores = d_scores;
+    wa.seed_out = d_seed_out;
+    wa.dirs = d_dirs;
+    wa.dir_off = d_dir_off;
+    wa.slot_off = d_slot_off;
+    wa.out_text = d_ot;
+    wa.out_pattern = d_op;
+    wa.alphabet = d_alpha;
+    wa.results = d_results;
+    wa.tail_len = d_tail;
+    wa.A = A;
+    uint32_t ctrl[2] = {0, 0};
+    std::vector<uint64_t> tail((size_t)np);
+    auto enqueue = [&]() -> int {
+        for (int64_t c = 0; c < nchunks; ++c)
+        {
+            // the chunk's items in one traced fill, then the combine and the walk of the chunk's pairs
+            const int64_t begin = pl.chunk_begin[c], count = pl.chunk_begin[c + 1] - begin;
+            const int64_t pbegin = pl.pair_chunk_begin[c], pcount = pl.pair_chunk_begin[c + 1] - pbegin;
+            if (c) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 4, st));  // the work counter; the bad-input flag stays
+            s.order = d_order + begin;
+            s.np = (int32_t)count;
+            wa.order = d_pair_order + pbegin;
+            HIP_TRY(hipEventRecord(ws.events[3 * c], st));
+            if (count)
+            {
+                const int grid = (int)std::min<int64_t>(count, pl.score.grid);
+                if (A <= 4) hipLaunchKernelGGL((align_seeds_kernel<true>), dim3(grid), dim3(64), 0, st, fa);
+                else hipLaunchKernelGGL((align_seeds_kernel<false>), dim3(grid), dim3(64), 0, st, fa);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
+            ca.order = wa.order;
+            launch_seeds_combine(ca, pcount, st);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(walk_seeds_kernel, dim3((unsigned)pcount), dim3(64), 0, st, wa);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ws.events[3 * c + 2], st));
+        }
+        HIP_TRY(hipMemcpyAsync(ctrl, d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(results, d_results, (size_t)np * sizeof(sa_result), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(tail.data(), d_tail, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return SA_OK;
+    };
+    if ((rc = enqueue()))
+    {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    for (int64_t c = 0; c < nchunks; ++c)
+    {
+        float f = 0, w = 0;
+        HIP_TRY(hipEventElapsedTime(&f, ws.events[3 * c], ws.events[3 * c + 1]));
+        HIP_TRY(hipEventElapsedTime(&w, ws.events[3 * c + 1], ws.events[3 * c + 2]));
+        g_stats.fill_ms += f;
+        g_stats.walk_ms += w;
+    }
+    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+    for (int64_t p = 0; p < np; ++p)
+        if (results[p].status != SA_OK)
+            return fail(SA_ERR_HIP, "seeded walk of pair " + std::to_string(p) + " did not end within its halves' moves");
+    if (strings && pl.string_bytes)
+    {
+        std::vector<char> ht(pl.string_bytes), hp(pl.string_bytes);
+        HIP_TRY(hipMemcpy(ht.data(), d_ot, pl.string_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hp.data(), d_op, pl.string_bytes, hipMemcpyDeviceToHost));
+        for (int64_t p = 0; p < np; ++p)
+        {
+            // the head piece (the left half and the seed) at the start of the slot, the tail piece (the right
+            // half) at its end
+            const uint64_t cap = pairs[p].text_len + pairs[p].pattern_len;
+            const uint64_t L = std::min<uint64_t>(results[p].num_alignment_bytes, cap), tl = std::min<uint64_t>(tail[p], L), hl = L - tl;
+            if (hl)
+            {
+                std::memcpy(aligned_text[p], ht.data() + pl.slot_off[p], hl);
+                std::memcpy(aligned_pattern[p], hp.data() + pl.slot_off[p], hl);
+            }
+            if (tl)
+            {
+                std::memcpy(aligned_text[p] + hl, ht.data() + pl.slot_off[p] + cap - tl, tl);
+                std::memcpy(aligned_pattern[p] + hl, hp.data() + pl.slot_off[p] + cap - tl, tl);
+            }
+        }
+    }
+    return SA_OK;
+}
+
 extern "C" {
+
+int sa_align_pairs_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                         const sa_host_pair *pairs, int64_t np, int device, sa_result *results, char *const *aligned_text,
+                         char *const *aligned_pattern)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
+        return fail(SA_ERR_INVALID, "sa_align_pairs_seeds: null argument");
+    std::vector<sa_pair> dp((size_t)np);
+    uint64_t tb = 0, pb = 0;
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
+            return fail(SA_ERR_INVALID, "sa_align_pairs_seeds: null sequence");
+        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
+        tb += pairs[p].text_len;
+        pb += pairs[p].pattern_len;
+    }
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    std::vector<char> ht(tb), hp(pb);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
+        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
+    }
+    DevBuf<char> dt, dpat;
+    int rc;
+    if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
+    if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
+    if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
+    return align_seeds_device(P, gap_open, gap_extend, xdrop, seeds, dp.data(), np, device, dt.p, dpat.p, results, aligned_text,
+                              aligned_pattern);
+}
 
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks)
 {

@@ -108,6 +108,71 @@ __global__ __launch_bounds__(64) void score_affine_extend_kernel(ScoreExtendArgs
                                                                             xa.xdrop);
 }
 
+// the extension kernels on work items (sa_hip.h sa_score_batch_seeds; sa_score_wave.h: SEED): a.order, a.np
+// and a.out speak of items, a.pairs is unused
+struct ScoreSeedsArgs {
+    ScoreExtendArgs xa;
+    const SeedItem *items;
+};
+
+template <int R, bool SMALL>
+__global__ __launch_bounds__(64) void score_seeds_kernel(ScoreSeedsArgs sa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<false, R, SA_GLOBAL, SMALL, false, false, false, false, true, true>(sa.xa.sa.s, 0, tab, TraceArgs(), 0, 0, nullptr, sa.xa.xdrop,
+                                                                                   sa.items);
+}
+
+template <int R, bool SMALL>
+__global__ __launch_bounds__(64) void score_affine_seeds_kernel(ScoreSeedsArgs sa)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    score_wave<true, R, SA_GLOBAL, SMALL, false, false, false, false, true, true>(sa.xa.sa.s, sa.xa.sa.gap_extend, tab, TraceArgs(), 0, 0,
+                                                                                  nullptr, sa.xa.xdrop, sa.items);
+}
+
+// One wave per pair, after the items' fill: the seed's substitution scores, summed by the lanes in a strided
+// loop and over the wave by a prefix sum, the bad-letter flag for the seed's letters, and the pair's
+// sa_seed_result from its halves' results (an empty half: 0 at (0, 0)).
+__global__ __launch_bounds__(64) void seeds_combine_kernel(SeedsCombineArgs a)
+{
+    const int lane = threadIdx.x;
+    const int p = a.order ? uniform(a.order[blockIdx.x]) : (int)blockIdx.x;
+    const SeedPair sp = a.pairs[p];
+    const int8_t *const text = a.text + sp.text_seed;
+    const int8_t *const pattern = a.pattern + sp.pattern_seed;
+    const int A = a.A;
+    int sum = 0;
+    bool bad = false;
+    for (uint64_t q = (uint64_t)lane; q < sp.len; q += kWave)
+    {
+        const int ct = text[q], cp = pattern[q];
+        bad = bad || ct < 0 || ct >= A || cp < 0 || cp >= A;
+        sum += a.table[min(max(cp, 0), A - 1) * A + min(max(ct, 0), A - 1)];
+    }
+    sum = __builtin_amdgcn_readlane(wave_prefix_sum(sum), kWave - 1);
+    if (bad) __hip_atomic_store(&a.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0)
+    {
+        sa_score_result l = {0, SA_OK, 0, 0}, r = {0, SA_OK, 0, 0};
+        if (sp.left >= 0) l = a.item_out[sp.left];
+        if (sp.right >= 0) r = a.item_out[sp.right];
+        sa_seed_result o;
+        o.score = l.score + sum + r.score;
+        o.status = SA_OK;
+        o.begin_text = sp.ts - l.end_text;
+        o.begin_pattern = sp.ps - l.end_pattern;
+        o.end_text = sp.ts + sp.len + r.end_text;
+        o.end_pattern = sp.ps + sp.len + r.end_pattern;
+        a.out[p] = o;
+    }
+}
+
+void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream)
+{
+    hipLaunchKernelGGL(seeds_combine_kernel, dim3((unsigned)np), dim3(64), 0, (hipStream_t)stream, a);
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -134,6 +199,27 @@ void launch_score_extend(const ScoreArgs &a, int gap_extend, int xdrop, int R, b
         constexpr bool SMALL = decltype(smallc)::value;
         if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_extend_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, xa);
         else hipLaunchKernelGGL((score_extend_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, xa);
+    };
+    auto with_r = [&](auto rc) { small ? launch(rc, std::true_type{}) : launch(rc, std::false_type{}); };
+    switch (R)
+    {
+    case 1: with_r(std::integral_constant<int, 1>{}); break;
+    case 2: with_r(std::integral_constant<int, 2>{}); break;
+    case 4: with_r(std::integral_constant<int, 4>{}); break;
+    default: with_r(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+// score_seeds_kernel or, with AFFINE, score_affine_seeds_kernel on the work items
+template <bool AFFINE>
+void launch_score_seeds(const ScoreArgs &a, int gap_extend, int xdrop, const SeedItem *items, int R, bool small, int grid, hipStream_t st)
+{
+    const ScoreSeedsArgs sa = {{{a, gap_extend}, xdrop}, items};
+    auto launch = [&](auto rc, auto smallc) {
+        constexpr int RR = decltype(rc)::value;
+        constexpr bool SMALL = decltype(smallc)::value;
+        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_seeds_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, sa);
+        else hipLaunchKernelGGL((score_seeds_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, sa);
     };
     auto with_r = [&](auto rc) { small ? launch(rc, std::true_type{}) : launch(rc, std::false_type{}); };
     switch (R)
@@ -207,6 +293,12 @@ struct sa_scorer : ScorePlan {
     sa_score_result *d_out = nullptr;
     uint32_t *d_ctrl = nullptr;
     bool ran = false;
+    // seeds scorer: the plan (num_pairs, order, d_out) is the work items'; seed_pairs counts the caller's pairs
+    bool seeds = false;
+    int64_t seed_pairs = 0;
+    SeedItem *d_items = nullptr;
+    SeedPair *d_seed_pairs = nullptr;
+    sa_seed_result *d_seed_out = nullptr;
 };
 
 namespace {
@@ -215,7 +307,7 @@ void free_scorer(sa_scorer *s)
 {
     if (!s) return;
     DeviceGuard dg(s->device);
-    void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl, s->d_bands};
+    void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl, s->d_bands, s->d_items, s->d_seed_pairs, s->d_seed_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -263,6 +355,69 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
     }
     HIP_TRY(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
     *out = s.release();
+    return SA_OK;
+}
+
+// sa_scorer_create_seeds: the extension scorer of the work items, with the items, the pairs' seeds and the
+// pairs' results beside it
+static int create_seeds_scorer(const sa_params *P, const ScoreGap &gapm, int32_t xdrop, const sa_seed *seeds, const sa_pair *pairs,
+                               int64_t np, int device, sa_scorer **out)
+{
+    if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create_seeds: null argument");
+    *out = nullptr;
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
+    s->device = device;
+    std::string err;
+    const ScoreExtend ext = {xdrop, false};
+    SeedItems si;
+    if (int rc = make_seeds_score_plan(P, pairs, seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err, &gapm, &ext))
+        return fail(rc, err);
+    s->seeds = true;
+    s->seed_pairs = np;
+    const size_t ni = si.items.size();
+    const int A = s->A;
+    int rc;
+    if ((rc = dmalloc(&s->d_items, std::max<size_t>(ni, 1) * sizeof(SeedItem)))) return rc;
+    if ((rc = dmalloc(&s->d_order, std::max<size_t>(ni, 1) * 4))) return rc;
+    if ((rc = dmalloc(&s->d_table, 32 * 32 * 4))) return rc;
+    if ((rc = dmalloc(&s->d_rows, std::max<size_t>((size_t)s->grid * s->row_stride * (s->affine ? 8 : 4), 8)))) return rc;
+    if ((rc = dmalloc(&s->d_out, std::max<size_t>(ni, 1) * sizeof(sa_score_result)))) return rc;
+    if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
+    if ((rc = dmalloc(&s->d_seed_pairs, std::max<size_t>((size_t)np, 1) * sizeof(SeedPair)))) return rc;
+    if ((rc = dmalloc(&s->d_seed_out, std::max<size_t>((size_t)np, 1) * sizeof(sa_seed_result)))) return rc;
+    if (ni)
+    {
+        HIP_TRY(hipMemcpy(s->d_items, si.items.data(), ni * sizeof(SeedItem), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_order, s->order.data(), ni * 4, hipMemcpyHostToDevice));
+    }
+    if (np) HIP_TRY(hipMemcpy(s->d_seed_pairs, si.pairs.data(), (size_t)np * sizeof(SeedPair), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
+    *out = s.release();
+    return SA_OK;
+}
+
+// the host pairs packed back to back into two arenas, as every host-pair function uploads them
+static int pack_host_pairs(const sa_host_pair *pairs, int64_t np, std::vector<sa_pair> *dp, std::vector<char> *ht, std::vector<char> *hp)
+{
+    dp->resize((size_t)np);
+    uint64_t tb = 0, pb = 0;
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
+            return fail(SA_ERR_INVALID, "sa_score_batch_seeds: null sequence");
+        (*dp)[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
+        tb += pairs[p].text_len;
+        pb += pairs[p].pattern_len;
+    }
+    ht->resize(tb);
+    hp->resize(pb);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if (pairs[p].text_len) std::memcpy(ht->data() + (*dp)[p].text_offset, pairs[p].text, pairs[p].text_len);
+        if (pairs[p].pattern_len) std::memcpy(hp->data() + (*dp)[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
+    }
     return SA_OK;
 }
 
@@ -337,6 +492,33 @@ int sa_scorer_create_extend(const sa_params *P, int32_t gap_open, int32_t gap_ex
     return create_scorer(P, &gapm, pairs, np, device, out, nullptr, false, nullptr, &xdrop);
 }
 
+int sa_scorer_create_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                           const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+{
+    return create_seeds_scorer(P, ScoreGap{gap_open, gap_extend}, xdrop, seeds, pairs, np, device, out);
+}
+
+int sa_score_batch_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                         const sa_host_pair *pairs, int64_t np, int device, sa_seed_result *out)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch_seeds: null argument");
+    std::vector<sa_pair> dp;
+    std::vector<char> ht, hp;
+    if (int rc = pack_host_pairs(pairs, np, &dp, &ht, &hp)) return rc;
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    sa_scorer *raw = nullptr;
+    if (int rc = create_seeds_scorer(P, ScoreGap{gap_open, gap_extend}, xdrop, seeds, dp.data(), np, device, &raw)) return rc;
+    std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
+    DevBuf<char> dt, dpat;
+    int rc;
+    if ((rc = dmalloc(&dt.p, ht.size())) || (rc = dmalloc(&dpat.p, hp.size()))) return rc;
+    if (!ht.empty()) HIP_TRY(hipMemcpy(dt.p, ht.data(), ht.size(), hipMemcpyHostToDevice));
+    if (!hp.empty()) HIP_TRY(hipMemcpy(dpat.p, hp.data(), hp.size(), hipMemcpyHostToDevice));
+    if ((rc = sa_scorer_run(s.get(), dt.p, dpat.p, nullptr))) return rc;
+    return sa_scorer_fetch_seeds(s.get(), out, nullptr);
+}
+
 int sa_scorer_destroy(sa_scorer *s)
 {
     free_scorer(s);
@@ -352,6 +534,44 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     // the run's first enqueued operation: the work counter and the bad-input flag at zero
     HIP_TRY(hipMemsetAsync(s->d_ctrl, 0, 256, st));
     s->ran = true;
+    if (s->seeds)
+    {
+        // the items' fill in one launch (both halves of every pair balance over the waves), then the combine
+        if (s->seed_pairs == 0) return SA_OK;
+        if (s->num_pairs)
+        {
+            ScoreArgs a;
+            a.text = (const int8_t *)d_text;
+            a.pattern = (const int8_t *)d_pattern;
+            a.pairs = nullptr;
+            a.order = s->d_order;
+            a.table = s->d_table;
+            a.rows = s->d_rows;
+            a.out = s->d_out;
+            a.ctrl = s->d_ctrl;
+            a.np = (int32_t)s->num_pairs;
+            a.A = s->A;
+            a.gap = s->gap;
+            a.key_rowbits = s->key_rowbits;
+            a.row_stride = s->row_stride;
+            if (s->affine) launch_score_seeds<true>(a, s->gap_extend, s->xdrop, s->d_items, s->R, s->A <= 4, s->grid, st);
+            else launch_score_seeds<false>(a, 0, s->xdrop, s->d_items, s->R, s->A <= 4, s->grid, st);
+            HIP_TRY(hipGetLastError());
+        }
+        SeedsCombineArgs c;
+        c.text = (const int8_t *)d_text;
+        c.pattern = (const int8_t *)d_pattern;
+        c.pairs = s->d_seed_pairs;
+        c.order = nullptr;
+        c.table = s->d_table;
+        c.item_out = s->d_out;
+        c.out = s->d_seed_out;
+        c.ctrl = s->d_ctrl;
+        c.A = s->A;
+        launch_seeds_combine(c, s->seed_pairs, st);
+        HIP_TRY(hipGetLastError());
+        return SA_OK;
+    }
     if (s->num_pairs == 0) return SA_OK;
     ScoreArgs a;
     a.text = (const int8_t *)d_text;
@@ -378,8 +598,34 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     return SA_OK;
 }
 
+int sa_scorer_fetch_seeds(sa_scorer *s, sa_seed_result *out, void *stream)
+{
+    if (!s || !s->seeds) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: not a seeds scorer");
+    if (!out && s->seed_pairs) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: null argument");
+    if (!s->ran) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: the scorer has not been run");
+    DeviceGuard dg(s->device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t ctrl[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(ctrl, s->d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
+    if (s->seed_pairs)
+        HIP_TRY(hipMemcpyAsync(out, s->d_seed_out, (size_t)s->seed_pairs * sizeof(sa_seed_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+    return SA_OK;
+}
+
 int sa_scorer_fetch(sa_scorer *s, sa_score_result *out, void *stream)
 {
+    if (s && s->seeds)
+    {
+        // a seeds scorer: the score with the absolute end cell
+        if (!out && s->seed_pairs) return fail(SA_ERR_INVALID, "sa_scorer_fetch: null argument");
+        std::vector<sa_seed_result> sr((size_t)s->seed_pairs);
+        if (int rc = sa_scorer_fetch_seeds(s, sr.data(), stream)) return rc;
+        for (int64_t p = 0; p < s->seed_pairs; ++p) out[p] = sa_score_result{sr[p].score, sr[p].status, sr[p].end_text, sr[p].end_pattern};
+        return SA_OK;
+    }
     if (!s || (!out && s->num_pairs)) return fail(SA_ERR_INVALID, "sa_scorer_fetch: null argument");
     if (!s->ran) return fail(SA_ERR_INVALID, "sa_scorer_fetch: the scorer has not been run");
     DeviceGuard dg(s->device);

@@ -21,7 +21,8 @@ const ScoreKnobs &score_knobs()
 }
 
 // the instance of each R with the most registers (local, alphabets up to 4): 53, 71, 101 and 165
-// VGPRs of the SIMD's 512; the extension instances, planned as local ones, take 49, 67, 95 and 129
+// VGPRs of the SIMD's 512; the extension instances, planned as local ones, take 49, 67, 95 and 129, and
+// so do the seeds instances, register for register (linear and affine)
 int score_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 7 : 8; }
 
 // score_affine_kernel: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4); extension: 59, 79, 114, 154
@@ -265,6 +266,61 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     const uint64_t per_pair = 24 /* descriptor */ + (bands ? 8 : 0) /* band */ + 4 /* order */ + sizeof(sa_score_result);
     pl.device_bytes = pl.input_bytes + (uint64_t)np * per_pair + (uint64_t)pl.grid * pl.row_stride * (affine ? 8 : 4) +
                       32 * 32 * 4 /* score table */ + 256 /* counter and flags */;
+    return SA_OK;
+}
+
+int make_seeds_score_plan(const sa_params *P, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
+                          const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err, const ScoreGap *affine,
+                          const ScoreExtend *extend)
+{
+    if (!items || !extend)
+    {
+        *err = "seeds scorer: null argument";
+        return SA_ERR_INVALID;
+    }
+    // the mode, the xdrop and the limits, on the whole pairs: the sum of the three scores of a pair stays
+    // under the bound of its (n, m), and so does every key
+    ScorePlan whole;
+    if (int rc = make_score_plan(P, pairs, np, num_cu, kn, &whole, err, affine, nullptr, nullptr, extend)) return rc;
+    if (np > 0 && !seeds)
+    {
+        *err = "seeds is null";
+        return SA_ERR_INVALID;
+    }
+    items->items.clear();
+    items->pairs.resize((size_t)np);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
+        const uint64_t ts = seeds[p].text_pos, ps = seeds[p].pattern_pos, L = seeds[p].length;
+        // n, m < 2^24: compared so that no sum wraps
+        if (ts > n || L > n - ts || ps > m || L > m - ps)
+        {
+            *err = "pair " + std::to_string(p) + ": seed {" + std::to_string(ts) + ", " + std::to_string(ps) + ", " + std::to_string(L) +
+                   "} does not lie inside " + std::to_string(n) + " text and " + std::to_string(m) + " pattern letters";
+            return SA_ERR_INVALID;
+        }
+        SeedPair &sp = items->pairs[p];
+        sp = SeedPair{pairs[p].text_offset + ts, pairs[p].pattern_offset + ps, ts, ps, L, -1, -1};
+        if (ts > 0 && ps > 0)
+        {
+            sp.left = (int32_t)items->items.size();
+            items->items.push_back(SeedItem{sp.text_seed - 1, sp.pattern_seed - 1, (uint32_t)ts, (uint32_t)ps, -1, (int32_t)p});
+        }
+        const uint64_t rn = n - ts - L, rm = m - ps - L;
+        if (rn > 0 && rm > 0)
+        {
+            sp.right = (int32_t)items->items.size();
+            items->items.push_back(SeedItem{sp.text_seed + L, sp.pattern_seed + L, (uint32_t)rn, (uint32_t)rm, 1, (int32_t)p});
+        }
+    }
+    // the items as extension pairs: cost, R, order by cells, grid and boundary rows
+    std::vector<sa_pair> ip(items->items.size());
+    for (size_t k = 0; k < ip.size(); ++k) ip[k] = sa_pair{0, items->items[k].n, 0, items->items[k].m};
+    if (int rc = make_score_plan(P, ip.data(), (int64_t)ip.size(), num_cu, kn, out, err, affine, nullptr, nullptr, extend)) return rc;
+    out->device_bytes += whole.input_bytes - out->input_bytes + (uint64_t)ip.size() * (sizeof(SeedItem) - 24) +
+                         (uint64_t)np * (sizeof(SeedPair) + sizeof(sa_seed_result));
+    out->input_bytes = whole.input_bytes;
     return SA_OK;
 }
 

@@ -172,6 +172,38 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
                     ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr, const int32_t *band = nullptr,
                     const sa_band *bands = nullptr, const ScoreExtend *extend = nullptr);
 
+// Seed extension (sa_hip.h sa_score_batch_seeds): a pair becomes up to two work items, the extension of
+// its left half read backwards and of its right half read forwards; an empty half is no item. The
+// kernels draw items, not pairs. text_off and pattern_off address the half's first-read letters in the
+// arenas: letter k of the half's text is arena[text_off + dir * k].
+struct SeedItem {
+    uint64_t text_off, pattern_off;
+    uint32_t n, m;   // columns and rows of the half
+    int32_t dir;     // +1 the right half, -1 the left half
+    int32_t pair;
+};
+// One pair of a seeds call as the combine and walk kernels take it: the arena offsets of the seed's first
+// letters, the seed, and the pair's items (-1: that half is empty).
+struct SeedPair {
+    uint64_t text_seed, pattern_seed;
+    uint64_t ts, ps, len;
+    int32_t left, right;
+};
+struct SeedItems {
+    std::vector<SeedItem> items;  // pair by pair, left before right
+    std::vector<SeedPair> pairs;
+};
+
+// Plans the seeds scorer: `seeds` null with pairs, ts + L > n and ps + L > m are SA_ERR_INVALID, the
+// message naming the first such pair; the mode, the xdrop and the limits are make_score_plan's for the
+// extension scorer on the whole pairs' (n, m). The plan is then make_score_plan's for the items as
+// extension pairs: costed by the local step model, ordered by cells (plan->order holds item indices and
+// plan->num_pairs the number of items). input_bytes is the whole pairs'; device_bytes adds the items'
+// 8 bytes above a pair descriptor and, per pair, a SeedPair and a sa_seed_result.
+int make_seeds_score_plan(const sa_params *P, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
+                          const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err, const ScoreGap *affine,
+                          const ScoreExtend *extend);
+
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).
 int score_waves_per_simd(int R);

@@ -139,6 +139,18 @@
 //    The walk starts at a cell of a row < i*, rows only fall along it, and those rows' strips stored
 //    every word: it never reads a word of a strip that did not run.
 //  - xdrop SA_NO_XDROP skips the test: every row counts, as with a drop that no score can reach.
+//
+// SEED (EXT: score_seeds_kernel, score_affine_seeds_kernel, align_seeds_kernel) is seed extension, sa_hip.h
+// sa_score_batch_seeds: the wave draws work items (SeedItem, sa_score_plan.h), a pair's left half or its
+// right half, where the other instances draw pairs, and `order`, `np`, `out` and TRACE's dir_off speak of
+// items. An item is an extension pair whose letter k lies at base[dir * k], base the address of the half's
+// first-read letter: the right half reads forwards from the seed's end, the left half backwards from the
+// letter before the seed, so column j of its matrix is t[ts - j] and row i is p[ps - i], the reversed
+// prefixes of sa_hip.h, with nothing reversed or copied. Only the two loads differ, text[dir * c0] per
+// body and pattern[dir * (row1 + r)] per strip; no step changes. Everything of SEED is under
+// `if constexpr (SEED)` or a constant condition, so the other instances compile to what they were. The
+// planner makes no item of an empty half, and the guards c0 < n and row1 + r < m keep a backward read at
+// or after the half's last letter, the pair's first.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -181,6 +193,14 @@ struct TraceArgs {
     const uint64_t *dir_off = nullptr;  // per pair, in words
 };
 
+// SEED: item `k` as the pair descriptor the wave program takes, and its direction
+__device__ __forceinline__ ScorePair seed_item_pair(const SeedItem *items, int k, int *dir)
+{
+    const SeedItem it = items[k];
+    *dir = uniform(it.dir);
+    return ScorePair{it.text_off, it.pattern_off, it.n, it.m};
+}
+
 // direction nibble of a cell: bits 0-1 the source of H (the reference's codes), bit 2 E extends,
 // bit 3 F extends
 enum { kDirLeft = 0, kDirDiag = 1, kDirTop = 2, kDirStop = 3, kDirEExt = 4, kDirFExt = 8 };
@@ -192,9 +212,10 @@ struct MaskedStep : std::true_type {
 // `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
 // registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
 template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false, bool BAT = false,
-          bool EXT = false>
+          bool EXT = false, bool SEED = false>
 __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs(),
-                                           int band = 0, int ends = 0, const Band *bands = nullptr, int xdrop = SA_NO_XDROP)
+                                           int band = 0, int ends = 0, const Band *bands = nullptr, int xdrop = SA_NO_XDROP,
+                                           const SeedItem *items = nullptr)
 {
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
@@ -202,6 +223,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
     static_assert(!ENDS || (MODE != SA_LOCAL && (BAT || !BAND)), "ends-free instances: the global or the fit program, no band but the caller's");
     static_assert(!BAT || (BAND && (ENDS || MODE == SA_LOCAL)), "band-at instances: banded; local, or ends-free (global and fit are two of its flag sets)");
     static_assert(!EXT || (MODE == SA_GLOBAL && !BAND && !ENDS), "extension instances: the global borders, no band, no free ends");
+    static_assert(!SEED || EXT, "seeds instances: extension alignment of a work item");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
     constexpr bool BEST = LOCAL || EXT;  // the result is the best cell: per-row running best and the key
     constexpr int SENT = kBandSentinel;
@@ -228,7 +250,8 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         w = uniform(w);
         if (w >= a.np) break;
         const int pi = uniform(a.order[w]);
-        const ScorePair pd = a.pairs[pi];
+        int sdir = 1;  // SEED: the item's direction, -1 for a left half
+        const ScorePair pd = SEED ? seed_item_pair(items, pi, &sdir) : a.pairs[pi];
         const int n = uniform((int)pd.n), m = uniform((int)pd.m);
         if constexpr (ENDS)
         {
@@ -342,7 +365,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 int c = 0;
                 if (row1 + r < m)
                 {
-                    c = pattern[row1 + r];
+                    c = SEED ? pattern[(row1 + r) * sdir] : pattern[row1 + r];
                     bad = bad || c < 0 || c >= A;
                     c = min(max(c, 0), A - 1);
                 }
@@ -527,7 +550,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                 tfeed = 0;
                 if (c0 < n)
                 {
-                    const int c = text[c0];
+                    const int c = SEED ? text[c0 * sdir] : text[c0];
                     bad = bad || c < 0 || c >= A;
                     tfeed = min(max(c, 0), A - 1);
                 }

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
 
 namespace sa {
 
@@ -73,6 +74,96 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
         pl.arena_bytes = std::max(pl.arena_bytes, used);
     }
     if (np > 0) pl.chunk_begin.push_back(np);
+    return SA_OK;
+}
+
+int make_seeds_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_pair *pairs,
+                          const sa_seed *seeds, int64_t np, int num_cu, const ScoreKnobs &kn, uint64_t budget,
+                          SeedTracePlan *out, std::string *err)
+{
+    if (!out)
+    {
+        *err = "aligner: null argument";
+        return SA_ERR_INVALID;
+    }
+    SeedTracePlan &pl = *out;
+    pl = SeedTracePlan();
+    const ScoreGap gapm = {gap_open, gap_extend};
+    ScoreKnobs k8 = kn;
+    k8.rows_per_lane = kTraceRows;
+    k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
+    const ScoreExtend ext = {xdrop, true};
+    if (int rc = make_seeds_score_plan(P, pairs, seeds, np, num_cu, k8, &pl.score, &pl.seeds, err, &gapm, &ext)) return rc;
+    pl.budget = budget;
+    pl.num_pairs = np;
+    const std::vector<SeedItem> &items = pl.seeds.items;
+    const int64_t ni = (int64_t)items.size();
+    pl.dir_bytes.resize((size_t)ni);
+    pl.dir_off.resize((size_t)ni);
+    for (int64_t k = 0; k < ni; ++k)
+    {
+        pl.dir_bytes[k] = trace_dir_bytes(items[k].n, items[k].m);
+        pl.total_dir_bytes += pl.dir_bytes[k];
+    }
+    // per pair: the directions and the cells of both halves, and the string slot
+    pl.slot_off.resize((size_t)np);
+    std::vector<uint64_t> pbytes((size_t)np, 0), pcells((size_t)np, 0);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const SeedPair &sp = pl.seeds.pairs[p];
+        for (int32_t k : {sp.left, sp.right})
+            if (k >= 0)
+            {
+                pbytes[p] += pl.dir_bytes[k];
+                pcells[p] += (uint64_t)items[k].n * items[k].m;
+            }
+        pl.slot_off[p] = pl.string_bytes;
+        pl.string_bytes += pairs[p].text_len + pairs[p].pattern_len;
+        if (pbytes[p] > budget)
+        {
+            *err = "pair " + std::to_string(p) + " needs " + std::to_string(pbytes[p]) +
+                   " direction bytes for its two halves, the arena budget is " + std::to_string(budget) + " (SA_TRACE_ARENA_BYTES)";
+            return SA_ERR_UNSUPPORTED;
+        }
+    }
+    pl.pair_order.resize((size_t)np);
+    for (int64_t p = 0; p < np; ++p) pl.pair_order[p] = (int32_t)p;
+    std::stable_sort(pl.pair_order.begin(), pl.pair_order.end(), [&](int32_t a, int32_t b) { return pcells[a] > pcells[b]; });
+    // consecutive chunks of the pair order, each as long as its directions fit the budget; a chunk's items
+    // in the order of their cells
+    std::vector<int32_t> &order = pl.score.order;
+    order.clear();
+    auto by_cells = [&](int32_t a, int32_t b) { return (uint64_t)items[a].n * items[a].m > (uint64_t)items[b].n * items[b].m; };
+    auto close_chunk = [&]() { std::stable_sort(order.begin() + pl.chunk_begin.back(), order.end(), by_cells); };
+    pl.chunk_begin.push_back(0);
+    pl.pair_chunk_begin.push_back(0);
+    uint64_t used = 0;
+    for (int64_t w = 0; w < np; ++w)
+    {
+        const int32_t p = pl.pair_order[w];
+        if (used + pbytes[p] > budget)
+        {
+            close_chunk();
+            pl.chunk_begin.push_back((int64_t)order.size());
+            pl.pair_chunk_begin.push_back(w);
+            used = 0;
+        }
+        const SeedPair &sp = pl.seeds.pairs[p];
+        for (int32_t k : {sp.left, sp.right})
+            if (k >= 0)
+            {
+                pl.dir_off[k] = used;
+                used += pl.dir_bytes[k];
+                order.push_back(k);
+            }
+        pl.arena_bytes = std::max(pl.arena_bytes, used);
+    }
+    close_chunk();
+    if (np > 0)
+    {
+        pl.chunk_begin.push_back((int64_t)order.size());
+        pl.pair_chunk_begin.push_back(np);
+    }
     return SA_OK;
 }
 

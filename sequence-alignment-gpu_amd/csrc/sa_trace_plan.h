@@ -96,4 +96,21 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
                     int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err,
                     const int32_t *band = nullptr, const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
 
+// The seeds aligner (sa_hip.h sa_align_pairs_seeds): the traced fill draws work items (SeedItems), the walk
+// pairs. dir_bytes and dir_off are per item, each half traced as a global pair of its shape, ps x ts and
+// (m - ps - L) x (n - ts - L), never the pair's n x m; slot_off is per pair, its text_len + pattern_len
+// bytes. The chunks are cut over the pairs, ordered by the cells of both halves together, so that a
+// pair's halves share a chunk: chunk c walks positions pair_chunk_begin[c] .. of pair_order and fills
+// positions chunk_begin[c] .. of score.order, that chunk's items, most cells first. A pair is
+// SA_ERR_UNSUPPORTED only when its two halves together exceed `budget`.
+struct SeedTracePlan : TracePlan {
+    SeedItems seeds;
+    std::vector<int32_t> pair_order;
+    std::vector<int64_t> pair_chunk_begin;
+    int64_t num_pairs = 0;
+};
+int make_seeds_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_pair *pairs,
+                          const sa_seed *seeds, int64_t np, int num_cu, const ScoreKnobs &kn, uint64_t budget,
+                          SeedTracePlan *out, std::string *err);
+
 }  // namespace sa

@@ -42,7 +42,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_scorer_create_affine", "sa_align_pairs_affine", "sa_search_affine", "sa_affine_last_stats",
            "sa_score_batch_banded", "sa_scorer_create_banded", "sa_align_pairs_banded",
            "sa_score_batch_band_at", "sa_scorer_create_band_at", "sa_align_pairs_band_at", "sa_band_reachable",
-           "sa_score_batch_extend", "sa_scorer_create_extend", "sa_align_pairs_extend")
+           "sa_score_batch_extend", "sa_scorer_create_extend", "sa_align_pairs_extend",
+           "sa_score_batch_seeds", "sa_scorer_create_seeds", "sa_scorer_fetch_seeds", "sa_align_pairs_seeds")
 
 
 class SaParams(ctypes.Structure):
@@ -149,6 +150,12 @@ def _load():
                                           ctypes.POINTER(P)]
     L.sa_align_pairs_extend.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.c_int64, I,
                                         ctypes.POINTER(SaResult), P, P]
+    L.sa_score_batch_seeds.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_seeds.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                         ctypes.POINTER(P)]
+    L.sa_scorer_fetch_seeds.argtypes = [P, P, P]
+    L.sa_align_pairs_seeds.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, ctypes.c_int64, I,
+                                       ctypes.POINTER(SaResult), P, P]
     L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
     L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -205,6 +212,26 @@ def _bands(bands, num_pairs: int) -> np.ndarray:
     if len(b) != num_pairs:
         raise ValueError(f"bands holds {len(b)} (lo, hi) pairs for {num_pairs} pairs")
     return b
+
+
+# numpy view of sa_seed_result (include/sa_hip.h): int32 score, int32 status, uint64 x 4
+SEED_DTYPE = np.dtype([("score", "<i4"), ("status", "<i4"), ("begin_text", "<u8"), ("begin_pattern", "<u8"),
+                       ("end_text", "<u8"), ("end_pattern", "<u8")])
+
+
+def _seeds(seeds, num_pairs: int, xdrop, band, bands) -> np.ndarray:
+    """`seeds` as the (num_pairs, 3) uint64 array of sa_seed the seeds functions take, after the checks the
+    three callers share: seeds= requires xdrop= (NO_XDROP for none) and takes no band."""
+    if band is not None or bands is not None:
+        raise ValueError("seeds= takes no band: seed extension inside a band is not built")
+    if xdrop is None:
+        raise ValueError("seeds= requires xdrop= (NO_XDROP for none)")
+    a = np.asarray(seeds, dtype=np.int64).reshape(-1, 3)
+    if (a < 0).any():
+        raise ValueError("seeds= holds a negative value")
+    if len(a) != num_pairs:
+        raise ValueError(f"seeds holds {len(a)} (text_pos, pattern_pos, length) triples for {num_pairs} pairs")
+    return np.ascontiguousarray(a, dtype=np.uint64)
 
 
 def band_reachable(mode: int, n: int, m: int, lo: int, hi: int) -> bool:
@@ -278,7 +305,7 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
                        gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None,
-                       bands=None, xdrop: int | None = None) -> list[dict]:
+                       bands=None, xdrop: int | None = None, seeds=None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
     ones. With gap_open == gap_extend == g every value is align_pair's for gap g. `mode` may also be FIT
@@ -288,12 +315,17 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
     `bands` (an (np, 2) int32 array or a list of (lo, hi), one per pair; not with `band`),
     sa_align_pairs_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode. With `xdrop`
     (NO_XDROP or 0 .. 2**30 - 1; mode SA_GLOBAL, no band), sa_align_pairs_extend: extension alignment, from
-    the origin to the best cell of the rows before the X-drop's stop row; both starts are 0."""
+    the origin to the best cell of the rows before the X-drop's stop row; both starts are 0. With `seeds`
+    (one (text_pos, pattern_pos, length) per pair; requires `xdrop`, mode SA_GLOBAL, no band),
+    sa_align_pairs_seeds: the extension to both sides of each pair's seed joined with the seed's letters;
+    start_text and start_pattern are the 0-based indices of the first aligned letters."""
     if band is not None and bands is not None:
         raise ValueError("band= and bands= exclude each other")
     if xdrop is not None and (band is not None or bands is not None):
         raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
-    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band, bands, xdrop)
+    if seeds is not None:
+        seeds = _seeds(seeds, len(texts), xdrop, band, bands)
+    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band, bands, xdrop, seeds)
 
 
 def affine_last_stats() -> dict:
@@ -305,7 +337,7 @@ def affine_last_stats() -> dict:
 
 
 def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings, band=None,
-                      bands=None, xdrop=None) -> list[dict]:
+                      bands=None, xdrop=None, seeds=None) -> list[dict]:
     """align_batch (gap_extend None) and align_pairs_affine (with `band`, sa_align_pairs_banded): one
     packing of the host pairs and buffers."""
     p, S_keep, alpha_keep = _params(mode, S, gap, alphabet, 0)
@@ -318,7 +350,10 @@ def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, devic
     at = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_t]) if strings else None
     ap = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_p]) if strings else None
     res = (SaResult * max(1, n))()
-    if xdrop is not None:
+    if seeds is not None:
+        _check(lib.sa_align_pairs_seeds(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, seeds.ctypes.data,
+                                        hp, n, device, res, at, ap))
+    elif xdrop is not None:
         _check(lib.sa_align_pairs_extend(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, hp, n, device,
                                          res, at, ap))
     elif gap_extend is None:
@@ -431,7 +466,7 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                bands=None, xdrop: int | None = None) -> np.ndarray:
+                bands=None, xdrop: int | None = None, seeds=None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
     the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
@@ -442,7 +477,10 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     `band`), sa_score_batch_band_at: pair k inside lo <= j - i <= hi of bands[k], in every mode; a pair
     without an alignment in its band fails the call (band_reachable). With `xdrop` (NO_XDROP or
     0 .. 2**30 - 1; mode SA_GLOBAL, no band), sa_score_batch_extend: extension alignment, the best cell of
-    the rows before the X-drop's stop row, anchored at the origin; without `gap_extend` the gap is linear."""
+    the rows before the X-drop's stop row, anchored at the origin; without `gap_extend` the gap is linear.
+    With `seeds` (one (text_pos, pattern_pos, length) per pair; requires `xdrop`, mode SA_GLOBAL, no band),
+    sa_score_batch_seeds: the extension to both sides of each pair's seed plus the seed's score, as a
+    SEED_DTYPE array (score, status, begin_text, begin_pattern, end_text, end_pattern)."""
     if band is not None and bands is not None:
         raise ValueError("band= and bands= exclude each other")
     if xdrop is not None and (band is not None or bands is not None):
@@ -452,6 +490,12 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
     n = len(ts)
     hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
+    if seeds is not None:
+        sd = _seeds(seeds, n, xdrop, band, bands)
+        res = np.zeros(max(1, n), SEED_DTYPE)
+        _check(lib.sa_score_batch_seeds(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, sd.ctypes.data, hp,
+                                        n, device, res.ctypes.data))
+        return res[:n]
     out = np.zeros(max(1, n), SCORE_DTYPE)
     if xdrop is not None:
         _check(lib.sa_score_batch_extend(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, hp, n, device,
@@ -475,12 +519,13 @@ class Scorer:
     With `gap_extend`, an affine scorer (sa_scorer_create_affine): `gap` is the gap-open penalty. With
     `band`, a banded scorer (sa_scorer_create_banded; without `gap_extend` the gap is linear). With
     `bands`, one (lo, hi) per pair, a band-at scorer (sa_scorer_create_band_at; not with `band`). With
-    `xdrop`, an extension scorer (sa_scorer_create_extend; mode SA_GLOBAL, no band). `mode` as score_batch
-    takes it."""
+    `xdrop`, an extension scorer (sa_scorer_create_extend; mode SA_GLOBAL, no band). With `seeds` (one
+    (text_pos, pattern_pos, length) per pair; requires `xdrop`), a seeds scorer (sa_scorer_create_seeds):
+    results() is then a SEED_DTYPE array. `mode` as score_batch takes it."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
                  device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                 bands=None, xdrop: int | None = None):
+                 bands=None, xdrop: int | None = None, seeds=None):
         if band is not None and bands is not None:
             raise ValueError("band= and bands= exclude each other")
         if xdrop is not None and (band is not None or bands is not None):
@@ -491,7 +536,12 @@ class Scorer:
         self.pairs = pairs
         self.device = device
         h = ctypes.c_void_p()
-        if xdrop is not None:
+        self.seeded = seeds is not None
+        if seeds is not None:
+            sd = _seeds(seeds, len(pairs), xdrop, band, bands)
+            _check(lib.sa_scorer_create_seeds(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, xdrop,
+                                              sd.ctypes.data, arr, len(pairs), device, ctypes.byref(h)))
+        elif xdrop is not None:
             _check(lib.sa_scorer_create_extend(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, xdrop,
                                                arr, len(pairs), device, ctypes.byref(h)))
         elif bands is not None:
@@ -524,7 +574,16 @@ class Scorer:
         _check(lib.sa_scorer_run(self.handle, d_text, d_pattern, stream))
 
     def results(self, stream: int | None = None) -> np.ndarray:
-        """Every pair's sa_score_result as one numpy structured array (SCORE_DTYPE); synchronises."""
+        """Every pair's sa_score_result as one numpy structured array (SCORE_DTYPE); synchronises. A seeds
+        scorer returns its sa_seed_result array (SEED_DTYPE); score_results() has its sa_score_result view."""
+        if self.seeded:
+            out = np.zeros(max(1, self.num_pairs), SEED_DTYPE)
+            _check(lib.sa_scorer_fetch_seeds(self.handle, out.ctypes.data, stream))
+            return out[: self.num_pairs]
+        return self.score_results(stream)
+
+    def score_results(self, stream: int | None = None) -> np.ndarray:
+        """sa_scorer_fetch: SCORE_DTYPE of every pair; on a seeds scorer the score with the absolute end cell."""
         out = np.zeros(max(1, self.num_pairs), SCORE_DTYPE)
         _check(lib.sa_scorer_fetch(self.handle, out.ctypes.data, stream))
         return out[: self.num_pairs]

@@ -58,7 +58,18 @@ the stop rows of a row-by-row numpy reference on a 16-pair subsample, whose resu
 equal. Then sa_align_pairs_extend on 64 of these pairs at X-drop 100 and without a drop: the device time
 of the traced fill and of the walk (sa_affine_last_stats).
 
+With --mode seeds the seeds scorer and aligner (sa_hip.h: sa_scorer_create_seeds, sa_align_pairs_seeds) on the
+reads of --mode mapped, each pair's seed the longest run of matching columns of its SA_FIT alignment under
+11 / 2, computed once on the host. Under gap 5 / 5 and 11 / 2, without a drop and at --xdrop, alternated round
+by round (7 rounds): (a) the seeds scorer, (b) two extension scorers over pre-reversed and sliced arenas of the
+same halves, run one after the other (the same cells and the same programs: the yardstick), (c) the unbanded
+SA_FIT scorer (under 5 / 5 the linear one, beside the linear kernels the others then run); the seeded scores are asserted equal to the composition of (b) at the timed size, and the
+report holds (a) / (b) with (b)'s own min-max spread and (a) / (c) beside the ratio of the planner's step
+costs. A second table has each window clipped to the read's span +- 32 letters. Then align_pairs_affine(seeds=)
+end to end on 4000 of the pairs beside the two-call host composition, whose strings it must equal.
+
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+    python3 tools/score_bench.py --mode seeds [--small] --out profiles/r18/score_seeds_bench.json
     python3 tools/score_bench.py --mode extend [--small] --out profiles/r17/score_extend_bench.json
     python3 tools/score_bench.py --mode ends [--small] --out profiles/r15/score_ends_bench.json
     python3 tools/score_bench.py --mode ends --tree ../parent --out profiles/r15/score_ends_bench_parent.json
@@ -530,6 +541,161 @@ def extend_early_exit_row(args, engine, w, dt, dp, go: int, ge: int, xdrop: int)
     return row
 
 
+def longest_match_seeds(engine, w, go: int, ge: int):
+    """Per pair the seed (text_pos, pattern_pos, length) of the longest run of matching columns of its SA_FIT
+    alignment (the first of the longest), and the text span [start, end) the alignment covers."""
+    pairs = w["pairs"]
+    seeds, spans = [], []
+    for lo in range(0, len(pairs), 4000):
+        part = pairs[lo:lo + 4000]
+        texts = [w["text"][p[0]:p[0] + p[1]] for p in part]
+        pats = [w["pattern"][p[2]:p[2] + p[3]] for p in part]
+        for r in engine.align_pairs_affine(2, texts, pats, w["S"], go, ge):
+            a = np.frombuffer(r["aligned_text"].encode(), dtype=np.uint8)
+            b = np.frombuffer(r["aligned_pattern"].encode(), dtype=np.uint8)
+            eq = np.concatenate([[0], (a == b).astype(np.int8), [0]])
+            edges = np.flatnonzero(np.diff(eq))  # run starts and ends, alternating
+            starts, ends = edges[0::2], edges[1::2]
+            k = int(np.argmax(ends - starts)) if len(starts) else -1
+            c0, L = (int(starts[k]), int(ends[k] - starts[k])) if k >= 0 else (0, 0)
+            tpos = int(r["start_text"]) + int((a[:c0] != ord("-")).sum())
+            ppos = int(r["start_pattern"]) + int((b[:c0] != ord("-")).sum())
+            seeds.append((tpos, ppos, L))
+            spans.append((int(r["start_text"]), int(r["start_text"]) + int((a != ord("-")).sum())))
+    return seeds, spans
+
+
+def clip_workload(w, seeds, spans, margin: int = 32):
+    """Every text window clipped to the read's span +- `margin` letters, as a mapper would clip it."""
+    pairs, texts, out, sd = w["pairs"], [], [], []
+    off = 0
+    for (to, n, po, m), (ts, ps, L), (a, b) in zip(pairs, seeds, spans):
+        lo, hi = max(0, a - margin), min(n, b + margin)
+        texts.append(w["text"][to + lo:to + hi])
+        out.append((off, hi - lo, po, m))
+        sd.append((ts - lo, ps, L))
+        off += hi - lo
+    return dict(w, name=w["name"] + "_clipped", text=np.concatenate(texts), pairs=out), sd
+
+
+def halves_workloads(w, seeds):
+    """The halves of every pair as two extension workloads: the left halves reversed on the host, the right
+    halves sliced; a half with an empty side stays as an empty pair."""
+    lt, lp, rt, rp = [], [], [], []
+    for (to, n, po, m), (ts, ps, L) in zip(w["pairs"], seeds):
+        lt.append(w["text"][to:to + ts][::-1]), lp.append(w["pattern"][po:po + ps][::-1])
+        rt.append(w["text"][to + ts + L:to + n]), rp.append(w["pattern"][po + ps + L:po + m])
+
+    def pack(ts_, ps_):
+        to = np.concatenate([[0], np.cumsum([len(x) for x in ts_])])
+        po = np.concatenate([[0], np.cumsum([len(x) for x in ps_])])
+        return {"text": np.ascontiguousarray(np.concatenate(ts_)), "pattern": np.ascontiguousarray(np.concatenate(ps_)),
+                "pairs": [(int(to[k]), len(ts_[k]), int(po[k]), len(ps_[k])) for k in range(len(ts_))]}
+    return pack(lt, lp), pack(rt, rp)
+
+
+def seeds_rows(args, engine, w, seeds, gap: int, gap_extend, xdrop) -> dict:
+    """(a) the seeds scorer, (b) two extension scorers over pre-reversed and sliced arenas of the same halves,
+    run one after the other, (c) the unbanded fit scorer; alternated round by round. The seeded scores are
+    asserted equal to the composition of (b) at the timed size."""
+    import torch
+    # gap open == gap extend is the linear recurrence: the extension and seeds scorers then run the linear
+    # kernels (S4), and the fit scorer beside them is the linear one
+    pairs, affine = w["pairs"], gap != gap_extend
+    x = engine.NO_XDROP if xdrop is None else xdrop
+    left, right = halves_workloads(w, seeds)
+    dev = {k: (torch.from_numpy(v["text"]).cuda(), torch.from_numpy(v["pattern"]).cuda()) for k, v in (("w", w), ("l", left), ("r", right))}
+    sc = {"seeds": engine.Scorer(0, w["S"], gap, pairs, gap_extend=gap_extend, xdrop=x, seeds=seeds),
+          "left": engine.Scorer(0, w["S"], gap, left["pairs"], gap_extend=gap_extend, xdrop=x),
+          "right": engine.Scorer(0, w["S"], gap, right["pairs"], gap_extend=gap_extend, xdrop=x),
+          "fit": engine.Scorer(2, w["S"], gap, pairs, gap_extend=gap_extend if affine else None)}
+    ptr = {"seeds": dev["w"], "fit": dev["w"], "left": dev["l"], "right": dev["r"]}
+    run = {k: (lambda k=k: sc[k].run(ptr[k][0].data_ptr(), ptr[k][1].data_ptr())) for k in sc}
+    row = {"name": w["name"] + ("_affine" if affine else "_linear") + ("_xdrop" if xdrop is not None else "_no_xdrop"),
+           "pairs": len(pairs), "cells": sum(p[1] * p[3] for p in pairs), "half_cells": sum(p[1] * p[3] for p in left["pairs"] + right["pairs"]),
+           "gap": gap, "gap_extend": gap_extend, "xdrop": xdrop, "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for _ in range(2):  # warm-up
+        for k in sc:
+            run[k]()
+            res[k] = sc[k].results().copy()
+    S = np.asarray(w["S"])
+    mid = np.array([int(S[w["pattern"][po + ps:po + ps + L], w["text"][to + ts:to + ts + L]].sum()) for (to, _, po, _), (ts, ps, L) in zip(pairs, seeds)])
+    sd = np.array(seeds, dtype=np.int64).reshape(-1, 3)
+    g, l, r = res["seeds"], res["left"], res["right"]
+    assert (g["score"] == l["score"] + mid + r["score"]).all(), "a seeded score differs from the composition"
+    assert (g["begin_text"] == sd[:, 0] - l["end_text"]).all() and (g["begin_pattern"] == sd[:, 1] - l["end_pattern"]).all()
+    assert (g["end_text"] == sd[:, 0] + sd[:, 2] + r["end_text"]).all() and (g["end_pattern"] == sd[:, 1] + sd[:, 2] + r["end_pattern"]).all()
+    row["seeded_scores_equal_the_composition"] = True
+    ms = {"seeds": [], "two_extend": [], "fit": []}
+
+    def both():
+        run["left"]()
+        run["right"]()
+    for _ in range(args.rounds):
+        ms["seeds"].append(timed(run["seeds"], lambda: sc["seeds"].results()))
+        ms["two_extend"].append(timed(both, lambda: (sc["left"].results(), sc["right"].results())))
+        ms["fit"].append(timed(run["fit"], lambda: sc["fit"].results()))
+    for k, v in ms.items():
+        row[k + "_run"] = stats(v)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    items = [(0, n, 0, m) for _, n, _, m in left["pairs"] + right["pairs"]]
+    model = model_cost(items, row["scorers"]["seeds"]["rows_per_lane"], True, affine) / model_cost(pairs, row["scorers"]["fit"]["rows_per_lane"], False, affine, True)
+    spread = max(ms["two_extend"]) - min(ms["two_extend"])
+    row["seeds_over_two_extend"] = round(med["seeds"] / med["two_extend"], 4)
+    row["two_extend_spread_ms"] = round(spread, 3)
+    row["seeds_below_two_extend_beyond_its_spread"] = bool(med["seeds"] < med["two_extend"] - spread)
+    row["seeds_over_fit"] = round(med["seeds"] / med["fit"], 4)
+    row["model_seeds_over_fit"] = round(model, 4)
+    for s in sc.values():
+        s.close()
+    return row
+
+
+def seeds_aligned_row(args, engine, w, seeds, go: int, ge: int, xdrop) -> dict:
+    """sa_align_pairs_seeds end to end (wall clock, host arrays to host strings) on the first 4000 pairs beside
+    the two-call host composition: reverse the prefixes, two sa_align_pairs_extend calls, reverse the left
+    strings back and join the three pieces."""
+    import time
+    nal = min(len(w["pairs"]), 4000)
+    pairs, sd = w["pairs"][:nal], seeds[:nal]
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in pairs]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in pairs]
+    x = engine.NO_XDROP if xdrop is None else xdrop
+
+    def seeded():
+        return engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, xdrop=x, seeds=sd)
+
+    def composed():
+        lt = [np.ascontiguousarray(t[:s[0]][::-1]) for t, s in zip(texts, sd)]
+        lp = [np.ascontiguousarray(p[:s[1]][::-1]) for p, s in zip(pats, sd)]
+        rt = [t[s[0] + s[2]:] for t, s in zip(texts, sd)]
+        rp = [p[s[1] + s[2]:] for p, s in zip(pats, sd)]
+        la = engine.align_pairs_affine(0, lt, lp, w["S"], go, ge, xdrop=x)
+        ra = engine.align_pairs_affine(0, rt, rp, w["S"], go, ge, xdrop=x)
+        return [(a["aligned_text"][::-1] + "".join("ATCG"[c] for c in t[s[0]:s[0] + s[2]]) + b["aligned_text"],
+                 a["aligned_pattern"][::-1] + "".join("ATCG"[c] for c in p[s[1]:s[1] + s[2]]) + b["aligned_pattern"])
+                for a, b, t, p, s in zip(la, ra, texts, pats, sd)]
+    got, want = seeded(), composed()
+    assert [(g["aligned_text"], g["aligned_pattern"]) for g in got] == want, "a seeded alignment differs from the composition"
+    ms = {"seeds": [], "composition": []}
+    fill, walk = [], []
+    for _ in range(max(3, args.rounds // 2)):
+        t0 = time.perf_counter()
+        seeded()
+        ms["seeds"].append((time.perf_counter() - t0) * 1e3)
+        s2 = engine.affine_last_stats()
+        fill.append(s2["fill_ms"]), walk.append(s2["walk_ms"])
+        t0 = time.perf_counter()
+        composed()
+        ms["composition"].append((time.perf_counter() - t0) * 1e3)
+    return {"name": w["name"] + "_aligned", "pairs": nal, "gap_open": go, "gap_extend": ge, "xdrop": xdrop,
+            "alignments_equal_the_composition": True, "seeds_end_to_end_wall": stats(ms["seeds"]),
+            "composition_end_to_end_wall": stats(ms["composition"]), "seeds_traced_fill": stats(fill), "seeds_walk": stats(walk),
+            "seeds_arena_bytes": s2["arena_bytes"], "seeds_chunks": s2["num_chunks"],
+            "seeds_over_composition": round(statistics.median(ms["seeds"]) / statistics.median(ms["composition"]), 4)}
+
+
 def fit_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
     """The fit, global and local scorers of one gap model on the mapping workload, alternated."""
     cells = sum(p[1] * p[3] for p in w["pairs"])
@@ -704,26 +870,29 @@ def main() -> int:
     ap.add_argument("--exit-gap", type=int, nargs=2, default=[16, 4], metavar=("OPEN", "EXTEND"),
                     help="--mode extend: the penalties of the early-exit comparison")
     ap.add_argument("--xdrop", type=int, default=100, help="--mode extend: the X-drop of the early-exit comparison")
-    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend"], default=None,
+    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
                          "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload; "
                          "mapped: the band-at fit scorer around each read's true offset against the unbanded fit scorer "
                          "(profiles/r16/score_mapped_bench.json); "
                          "extend: the extension scorers against the local ones, with and without an X-drop "
-                         "(profiles/r17/score_extend_bench.json)")
+                         "(profiles/r17/score_extend_bench.json); "
+                         "seeds: the seeds scorer and aligner against two extension calls on host-reversed halves and "
+                         "against the fit scorer (profiles/r18/score_seeds_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--tree", default=None,
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
     if args.rounds is None:
-        args.rounds = 7 if args.mode == "extend" else 5
+        args.rounds = 7 if args.mode in ("extend", "seeds") else 5
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
                                                     ("r15", "score_ends_bench.json") if args.mode == "ends" else
                                                     ("r16", "score_mapped_bench.json") if args.mode == "mapped" else
-                                                    ("r17", "score_extend_bench.json") if args.mode == "extend" else ("r09", "score_bench.json")))
+                                                    ("r17", "score_extend_bench.json") if args.mode == "extend" else
+                                                    ("r18", "score_seeds_bench.json") if args.mode == "seeds" else ("r09", "score_bench.json")))
     if args.tree:
         sys.path.insert(0, os.path.join(os.path.abspath(args.tree), "sequence-alignment-gpu_amd", "python"))
     import torch
@@ -773,6 +942,22 @@ def main() -> int:
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
         del dt, dp
+    elif args.mode == "seeds":
+        w = mapped_workload(args.small)
+        ge = args.gap_extend if args.gap_extend is not None else 2
+        seeds, spans = longest_match_seeds(engine, w, args.gap_open, ge)
+        report["seed_length"] = {"mean": round(float(np.mean([s[2] for s in seeds])), 1), "min": int(min(s[2] for s in seeds)),
+                                 "max": int(max(s[2] for s in seeds))}
+        wc, seeds_c = clip_workload(w, seeds, spans)
+        for ww, sd in ((w, seeds), (wc, seeds_c)):
+            for gap, gx in ((5, 5), (args.gap_open, ge)):
+                for xdrop in (None, args.xdrop):
+                    row = seeds_rows(args, engine, ww, sd, gap, gx, xdrop)
+                    report["workloads"].append(row)
+                    print(json.dumps(row), flush=True)
+        row = seeds_aligned_row(args, engine, w, seeds, args.gap_open, ge, args.xdrop)
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
     elif args.mode == "ends":
         report["library_build_id"] = engine.lib.sa_build_id().decode()
         for w in (mapping_workload(args.small), overlap_workload(args.small)):
