@@ -40,7 +40,7 @@ int main(int argc, char **argv)
     sa_band at = {0, 0};
     bool extend = false;
     int32_t xdrop = SA_NO_XDROP;
-    ScoreGap gapm = {0, 0};
+    int32_t gap_extend = 0;
     std::vector<sa_pair> pairs;
     std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
     std::vector<size_t> shape_of;      // the shape argument of each pair
@@ -59,7 +59,7 @@ int main(int argc, char **argv)
         else if (a == "--gap-extend")
         {
             affine = true;
-            gapm.extend = std::atoi(value());
+            gap_extend = std::atoi(value());
         }
         else if (a == "--band")
         {
@@ -124,8 +124,6 @@ int main(int argc, char **argv)
     for (int c = 0; c < a; ++c) S[(size_t)c * a + c] = match;
     P.score_matrix = S.data();
 
-    gapm.open = P.gap_penalty;
-    const ScoreExtend ext = {xdrop, false};
     ScorePlan pl;
     std::string err;
     const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
@@ -139,11 +137,12 @@ int main(int argc, char **argv)
     std::vector<sa_seed> seeds;
     for (size_t i = 0; seeded && i < pairs.size(); ++i) seeds.push_back(shape_seeds[shape_seeds.size() == 1 ? 0 : shape_of[i]]);
     SeedItems si;
-    const int rc = seeded ? make_seeds_score_plan(&P, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &si, &err,
-                                                  affine ? &gapm : nullptr, &ext)
-                          : make_score_plan(&P, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err, affine ? &gapm : nullptr,
-                                            banded ? &band : nullptr, band_at ? bands.data() : nullptr,
-                                            extend || !shape_seeds.empty() ? &ext : nullptr);
+    WaveSpec spec = affine ? WaveSpec::gaps(P.gap_penalty, gap_extend) : WaveSpec();
+    if (banded) spec = spec.in_band(band);
+    if (band_at) spec = spec.in_bands(bands.data());
+    if (extend || !shape_seeds.empty()) spec = spec.extending(xdrop);
+    const int rc = seeded ? make_seeds_score_plan(&P, spec, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &si, &err)
+                          : make_score_plan(&P, spec, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -156,11 +155,11 @@ int main(int argc, char **argv)
                 (unsigned long long)pl.max_text, (unsigned long long)pl.row_stride, (unsigned long long)pl.input_bytes,
                 (unsigned long long)pl.device_bytes, (unsigned long long)pl.padded_cells, (unsigned long long)pl.cost[0],
                 (unsigned long long)pl.cost[1], (unsigned long long)pl.cost[2], (unsigned long long)pl.cost[3],
-                pl.affine ? "true" : "false", pl.gap_extend);
+                pl.spec.affine ? "true" : "false", pl.spec.gap_extend);
     // the order of a large batch is long: the first 64 entries
     for (size_t i = 0; i < pl.order.size() && i < 64; ++i) std::printf("%s%d", i ? ", " : "", pl.order[i]);
     std::printf("]");
-    if (extend || seeded) std::printf(", \"extend\": true, \"xdrop\": %d", pl.xdrop);
+    if (extend || seeded) std::printf(", \"extend\": true, \"xdrop\": %d", pl.spec.xdrop);
     if (seeded)
     {
         // the work items (the first 128): "order" above lists item indices, "num_pairs" counts items
@@ -177,7 +176,7 @@ int main(int argc, char **argv)
     }
     if (banded || band_at)
     {
-        std::printf(", \"band\": %d, \"band_cells\": %llu, \"bands\": [", pl.band, (unsigned long long)pl.band_cells);
+        std::printf(", \"band\": %d, \"band_cells\": %llu, \"bands\": [", pl.spec.banded ? pl.spec.band : -1, (unsigned long long)pl.band_cells);
         for (size_t i = 0; i < pairs.size() && i < 8; ++i)
         {
             const int64_t n = (int64_t)pairs[i].text_len, m = (int64_t)pairs[i].pattern_len, rows = 64 * pl.R;

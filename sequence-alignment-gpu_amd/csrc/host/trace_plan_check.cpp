@@ -129,8 +129,8 @@ int main(int argc, char **argv)
         std::vector<sa_seed> seeds;
         for (size_t i = 0; i < pairs.size(); ++i) seeds.push_back(shape_seeds[shape_seeds.size() == 1 ? 0 : shape_of[i]]);
         SeedTracePlan sp;
-        const int rc = make_seeds_trace_plan(&P, go, ge, xdrop, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), budget,
-                                             &sp, &err);
+        const int rc = make_seeds_trace_plan(&P, WaveSpec::gaps(go, ge).extending(xdrop), pairs.data(), seeds.data(), (int64_t)pairs.size(), cus,
+                                             score_knobs(), budget, &sp, &err);
         if (rc != SA_OK)
         {
             std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -139,9 +139,9 @@ int main(int argc, char **argv)
         std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"gap_extend\": %d, \"R\": %d, \"grid\": %d, \"num_pairs\": %lld, \"num_items\": %zu, "
                     "\"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, \"num_chunks\": %lld, "
                     "\"seeds\": true, \"xdrop\": %d, \"chunk_begin\": [",
-                    sp.score.mode, sp.score.A, sp.score.gap, sp.score.gap_extend, sp.score.R, sp.score.grid, (long long)sp.num_pairs,
+                    sp.score.mode, sp.score.A, sp.score.gap, sp.score.spec.gap_extend, sp.score.R, sp.score.grid, (long long)sp.num_pairs,
                     sp.seeds.items.size(), (unsigned long long)sp.budget, (unsigned long long)sp.arena_bytes,
-                    (unsigned long long)sp.total_dir_bytes, (unsigned long long)sp.string_bytes, (long long)sp.num_chunks(), sp.score.xdrop);
+                    (unsigned long long)sp.total_dir_bytes, (unsigned long long)sp.string_bytes, (long long)sp.num_chunks(), sp.score.spec.xdrop);
         for (size_t i = 0; i < sp.chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)sp.chunk_begin[i]);
         std::printf("], \"pair_chunk_begin\": [");
         for (size_t i = 0; i < sp.pair_chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)sp.pair_chunk_begin[i]);
@@ -168,8 +168,11 @@ int main(int argc, char **argv)
     if (!shape_seeds.empty()) extend = true;
     TracePlan pl;
     const std::vector<sa_band> bands(std::max<size_t>(pairs.size(), 1), at);
-    const int rc = make_trace_plan(&P, go, ge, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err,
-                                   banded ? &band : nullptr, band_at ? bands.data() : nullptr, extend ? &xdrop : nullptr);
+    WaveSpec spec = WaveSpec::gaps(go, ge);
+    if (banded) spec = spec.in_band(band);
+    if (band_at) spec = spec.in_bands(bands.data());
+    if (extend) spec = spec.extending(xdrop);
+    const int rc = make_trace_plan(&P, spec, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err);
     if (rc != SA_OK)
     {
         std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
@@ -178,7 +181,7 @@ int main(int argc, char **argv)
     std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"gap_extend\": %d, \"R\": %d, \"grid\": %d, \"num_pairs\": %lld, "
                 "\"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, "
                 "\"num_chunks\": %lld, \"chunk_begin\": [",
-                pl.score.mode, pl.score.A, pl.score.gap, pl.score.gap_extend, pl.score.R, pl.score.grid,
+                pl.score.mode, pl.score.A, pl.score.gap, pl.score.spec.gap_extend, pl.score.R, pl.score.grid,
                 (long long)pl.score.num_pairs, (unsigned long long)pl.budget, (unsigned long long)pl.arena_bytes,
                 (unsigned long long)pl.total_dir_bytes, (unsigned long long)pl.string_bytes, (long long)pl.num_chunks());
     for (size_t i = 0; i < pl.chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)pl.chunk_begin[i]);

@@ -9,16 +9,14 @@
 namespace sa {
 
 // Aligns `np` pairs addressed in the device arenas d_text / d_pattern (alphabet indices) on `device`
-// under gap_open / gap_extend: the traced Gotoh fill and the walk, chunk by chunk of the work order
+// under the gap model of `spec`: the traced Gotoh fill and the walk, chunk by chunk of the work order
 // (sa_trace_plan.h), on the null stream; synchronous. results: np entries. aligned_text /
 // aligned_pattern: both null, or np host buffers of at least text_len + pattern_len bytes each.
-// `band` non-null: inside the diagonal band of that half-width (sa_align_pairs_banded). `with_bands`:
-// inside bands[p] for pair p (sa_align_pairs_band_at; null bands with pairs is SA_ERR_INVALID). `xdrop`
-// non-null: extension alignment under that X-drop (sa_align_pairs_extend).
-int align_affine_device(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
-                        int device, const void *d_text, const void *d_pattern, sa_result *results,
-                        char *const *aligned_text, char *const *aligned_pattern, const int32_t *band = nullptr,
-                        bool with_bands = false, const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
+// `spec` banded: inside the diagonal band of that half-width (sa_align_pairs_banded); band_at: inside
+// bands[p] for pair p (sa_align_pairs_band_at; null bands with pairs is SA_ERR_INVALID); extend: extension
+// alignment under that X-drop (sa_align_pairs_extend).
+int align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
 
 // Seed extension (sa_hip.h sa_score_batch_seeds): seeds_combine_kernel (sa_score.hip), one wave per pair
 // after the items' fill, shared by the seeds scorer and the seeds aligner. It sums the seed's scores, flags
@@ -38,8 +36,8 @@ void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream);
 
 // sa_align_pairs_seeds on device arenas: the traced fill of the work items, the combine and the seeded walk,
 // chunk by chunk (sa_trace_plan.h SeedTracePlan); arguments as align_affine_device.
-int align_seeds_device(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
-                       const sa_pair *pairs, int64_t np, int device, const void *d_text, const void *d_pattern,
-                       sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
+int align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device,
+                       const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
+                       char *const *aligned_pattern);
 
 }  // namespace sa

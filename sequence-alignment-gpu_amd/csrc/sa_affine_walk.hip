@@ -1,9 +1,9 @@
 // Alignments under affine gap penalties (sa_hip.h: sa_align_pairs_affine; sa_search_affine in
-// sa_score.hip): align_affine_kernel<MODE, SMALL>, the traced instance of the affine wave program
-// (sa_score_wave.h, TRACE: four direction bits per cell), walk_affine_kernel, the traceback over the
-// three Gotoh states, and the host side that runs both chunk by chunk of the work order. What is run
-// is decided in sa_trace_plan.cpp (host only, no HIP). DESIGN.md §3.5 has the nibble, the walk and
-// its tie rules.
+// sa_score.hip): the traced instances of wave_kernel (sa_score_wave.h, kWaveTrace: four direction bits
+// per cell; affine, R = 8), launched through the table of sa_wave_launch.h, walk_affine_kernel, the
+// traceback over the three Gotoh states, and the host side that runs both chunk by chunk of the work
+// order. What is run is decided in sa_trace_plan.cpp (host only, no HIP). DESIGN.md §3.5 has the nibble,
+// the walk and its tie rules.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,80 +16,9 @@
 #include "sa_host.h"
 #include "sa_score_wave.h"
 #include "sa_trace_plan.h"
+#include "sa_wave_launch.h"
 
 namespace sa {
-
-struct AlignAffineArgs {
-    ScoreAffineArgs sa;
-    TraceArgs tr;
-};
-
-template <int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void align_affine_kernel(AlignAffineArgs a)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, MODE, SMALL, true>(a.sa.s, a.sa.gap_extend, tab, a.tr);
-}
-
-// align_affine_kernel inside a diagonal band of half-width `band` (sa_hip.h; sa_score_wave.h: BAND):
-// a strip stores direction words for the steps of its window only
-struct AlignBandArgs {
-    AlignAffineArgs a;
-    int32_t band;
-};
-
-template <int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void align_band_kernel(AlignBandArgs ba)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, MODE, SMALL, true, true>(ba.a.sa.s, ba.a.sa.gap_extend, tab, ba.a.tr, ba.band);
-}
-
-// align_affine_kernel with free ends (sa_hip.h SA_ENDS_FREE; sa_score_wave.h: ENDS): the nibbles are
-// unchanged, only the borders and the result cell differ
-struct AlignEndsArgs {
-    AlignAffineArgs a;
-    int32_t ends;
-};
-
-template <int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void align_ends_kernel(AlignEndsArgs ea)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, MODE, SMALL, true, false, true>(ea.a.sa.s, ea.a.sa.gap_extend, tab, ea.a.tr, 0, ea.ends);
-}
-
-// align_affine_kernel inside a band of the caller's, one per pair (sa_hip.h sa_align_pairs_band_at;
-// sa_score_wave.h: BAT): the local program, or with free ends the fit or the global one; a strip stores
-// the words of its window, an empty strip none
-struct AlignBandAtArgs {
-    AlignAffineArgs a;
-    int32_t ends;
-    const Band *bands;  // per pair, clipped (ScorePlan::bands)
-};
-
-template <int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void align_band_at_kernel(AlignBandAtArgs ba)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, MODE, SMALL, true, true, MODE != SA_LOCAL, true>(ba.a.sa.s, ba.a.sa.gap_extend, tab, ba.a.tr, 0, ba.ends,
-                                                                                  ba.bands);
-}
-
-// align_affine_kernel as extension alignment (sa_hip.h sa_align_pairs_extend; sa_score_wave.h: EXT): the
-// global nibbles; a fill that stops at its X-drop row stores no word below that row's strip
-struct AlignExtendArgs {
-    AlignAffineArgs a;
-    int32_t xdrop;
-};
-
-template <bool SMALL>
-__global__ __launch_bounds__(64) void align_extend_kernel(AlignExtendArgs xa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, SA_GLOBAL, SMALL, true, false, false, false, true>(xa.a.sa.s, xa.a.sa.gap_extend, tab, xa.a.tr, 0, 0, nullptr,
-                                                                                    xa.xdrop);
-}
 
 struct WalkArgs {
     const int8_t *text, *pattern;
@@ -282,21 +211,6 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     }
 }
 
-// align_extend_kernel on work items (sa_hip.h sa_align_pairs_seeds; sa_score_wave.h: SEED): a.order, a.np,
-// a.out and tr.dir_off speak of items; an item stores the words of a global pair of its shape
-struct AlignSeedsArgs {
-    AlignExtendArgs xa;
-    const SeedItem *items;
-};
-
-template <bool SMALL>
-__global__ __launch_bounds__(64) void align_seeds_kernel(AlignSeedsArgs sa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, kTraceRows, SA_GLOBAL, SMALL, true, false, false, false, true, true>(sa.xa.a.sa.s, sa.xa.a.sa.gap_extend, tab, sa.xa.a.tr, 0, 0,
-                                                                                         nullptr, sa.xa.xdrop, sa.items);
-}
-
 struct SeedWalkArgs {
     const int8_t *text, *pattern;
     const SeedItem *items;
@@ -483,98 +397,19 @@ struct Workspace {
     }
 };
 
-void launch_align(const AlignAffineArgs &a, int mode, bool small, int grid, hipStream_t st, int band, const Band *bands,
-                  const int32_t *xdrop = nullptr)
-{
-    if (xdrop)
-    {
-        const AlignExtendArgs xa = {a, *xdrop};
-        if (small) hipLaunchKernelGGL((align_extend_kernel<true>), dim3(grid), dim3(64), 0, st, xa);
-        else hipLaunchKernelGGL((align_extend_kernel<false>), dim3(grid), dim3(64), 0, st, xa);
-    }
-    else if (bands)  // SA_GLOBAL and SA_FIT as the ends-free modes they equal
-    {
-        const int fl = mode == SA_FIT ? SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END : mode & SA_ENDS_FREE ? mode & 15 : 0;
-        const AlignBandAtArgs ba = {a, fl, bands};
-        if (mode == SA_LOCAL)
-        {
-            if (small) hipLaunchKernelGGL((align_band_at_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, ba);
-            else hipLaunchKernelGGL((align_band_at_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, ba);
-        }
-        else if (fl & SA_FREE_TEXT_END)
-        {
-            if (small) hipLaunchKernelGGL((align_band_at_kernel<SA_FIT, true>), dim3(grid), dim3(64), 0, st, ba);
-            else hipLaunchKernelGGL((align_band_at_kernel<SA_FIT, false>), dim3(grid), dim3(64), 0, st, ba);
-        }
-        else
-        {
-            if (small) hipLaunchKernelGGL((align_band_at_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, ba);
-            else hipLaunchKernelGGL((align_band_at_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, ba);
-        }
-    }
-    else if (band >= 0)  // the planner admits global and local
-    {
-        const AlignBandArgs ba = {a, band};
-        if (mode == SA_LOCAL)
-        {
-            if (small) hipLaunchKernelGGL((align_band_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, ba);
-            else hipLaunchKernelGGL((align_band_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, ba);
-        }
-        else
-        {
-            if (small) hipLaunchKernelGGL((align_band_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, ba);
-            else hipLaunchKernelGGL((align_band_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, ba);
-        }
-    }
-    else if (mode == SA_LOCAL)
-    {
-        if (small) hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((align_affine_kernel<SA_LOCAL, false>), dim3(grid), dim3(64), 0, st, a);
-    }
-    else if (mode & SA_ENDS_FREE)  // the fit program when the text's end is free, else the global one
-    {
-        const AlignEndsArgs ea = {a, mode & 15};
-        if (mode & SA_FREE_TEXT_END)
-        {
-            if (small) hipLaunchKernelGGL((align_ends_kernel<SA_FIT, true>), dim3(grid), dim3(64), 0, st, ea);
-            else hipLaunchKernelGGL((align_ends_kernel<SA_FIT, false>), dim3(grid), dim3(64), 0, st, ea);
-        }
-        else
-        {
-            if (small) hipLaunchKernelGGL((align_ends_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, ea);
-            else hipLaunchKernelGGL((align_ends_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, ea);
-        }
-    }
-    else if (mode == SA_FIT)
-    {
-        if (small) hipLaunchKernelGGL((align_affine_kernel<SA_FIT, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((align_affine_kernel<SA_FIT, false>), dim3(grid), dim3(64), 0, st, a);
-    }
-    else
-    {
-        if (small) hipLaunchKernelGGL((align_affine_kernel<SA_GLOBAL, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((align_affine_kernel<SA_GLOBAL, false>), dim3(grid), dim3(64), 0, st, a);
-    }
-}
-
 }  // namespace
 
-int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa_pair *pairs, int64_t np, int device,
-                            const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
-                            char *const *aligned_pattern, const int32_t *band, bool with_bands, const sa_band *bands,
-                            const int32_t *xdrop)
+int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "affine aligner: null argument");
-    if (with_bands && !bands && np > 0) return fail(SA_ERR_INVALID, "sa_align_pairs_band_at: bands is null");
-    static const sa_band none = {0, 0};
-    if (with_bands && !bands) bands = &none;  // no pair reads it
+    if (spec.band_at && !spec.bands && np > 0) return fail(SA_ERR_INVALID, "sa_align_pairs_band_at: bands is null");
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     TracePlan pl;
     std::string err;
-    if (int rc = make_trace_plan(P, go, ge, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err, band, bands, xdrop))
-        return fail(rc, err);
+    if (int rc = make_trace_plan(P, spec, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err)) return fail(rc, err);
     if (!P->alphabet) return fail(SA_ERR_INVALID, "affine aligner: params->alphabet is null");
     g_stats = AffineStats();
     g_stats.arena_bytes = pl.arena_bytes;
@@ -600,7 +435,7 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     sa_result *d_results;
     Band *d_bands = nullptr;
     int rc;
-    if (with_bands)
+    if (spec.band_at)
     {
         if ((rc = ws.alloc(&d_bands, (size_t)np * sizeof(Band)))) return rc;
         HIP_TRY(hipMemcpy(d_bands, pl.score.bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
@@ -631,22 +466,14 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
         ws.events.push_back(ev);
     }
     HIP_TRY(hipMemsetAsync(d_ctrl, 0, 256, st));
-    AlignAffineArgs fa;
-    ScoreArgs &s = fa.sa.s;
-    s.text = (const int8_t *)d_text;
-    s.pattern = (const int8_t *)d_pattern;
-    s.pairs = d_pairs;
-    s.table = d_table;
-    s.rows = d_rows;
-    s.out = d_scores;
-    s.ctrl = d_ctrl;
-    s.A = A;
-    s.gap = go;
-    s.key_rowbits = pl.score.key_rowbits;
-    s.row_stride = pl.score.row_stride;
-    fa.sa.gap_extend = ge;
+    // the chunks differ in their part of the work order
+    TracedWaveArgs fa = {};
+    fa.sa = score_args(pl.score, d_text, d_pattern, d_pairs, d_order, 0, d_table, d_rows, d_scores, d_ctrl);
     fa.tr.dirs = d_dirs;
     fa.tr.dir_off = d_dir_off;
+    fa.bands = d_bands;
+    ScoreArgs &s = fa.sa.s;
+    const WaveChoice choice = wave_choice(pl.score.spec, pl.score.mode);
     WalkArgs wa;
     wa.text = s.text;
     wa.pattern = s.pattern;
@@ -661,8 +488,8 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     wa.results = d_results;
     wa.A = A;
     // an extension walks as SA_ENDS_FREE with no flag: from the fill's result cell to the origin
-    wa.mode = xdrop ? SA_ENDS_FREE : pl.score.mode;
-    wa.band = pl.score.band;
+    wa.mode = spec.extend ? SA_ENDS_FREE : pl.score.mode;
+    wa.band = spec.banded ? spec.band : -1;
     wa.bands = d_bands;
     uint32_t ctrl[2] = {0, 0};
     // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
@@ -677,7 +504,8 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
             s.np = (int32_t)count;
             wa.order = s.order;
             HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            launch_align(fa, wa.mode, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, wa.band, d_bands, xdrop);
+            if (!launch_wave<true>(choice, kTraceRows, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, fa))
+                return fail(SA_ERR_UNSUPPORTED, "affine aligner: the call's variant has no kernel instance");
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
             if (d_bands) hipLaunchKernelGGL(walk_affine_kernel<2>, dim3((unsigned)count), dim3(64), 0, st, wa);
@@ -726,79 +554,48 @@ int sa::align_affine_device(const sa_params *P, int32_t go, int32_t ge, const sa
     return SA_OK;
 }
 
-static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
-                            const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
-                            char *const *aligned_text, char *const *aligned_pattern, bool with_bands = false,
-                            const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
+// every sa_align_pairs_* but the seeds one: the host pairs packed into two arenas, then the device path
+static int align_host_pairs(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
+                            char *const *aligned_text, char *const *aligned_pattern)
+{
+    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
+        return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
+    HostArenas in;
+    if (int rc = upload_host_pairs("sa_align_pairs_affine", pairs, np, device, &in)) return rc;
+    return align_affine_device(P, spec, in.pairs.data(), np, device, in.text.p, in.pattern.p, results, aligned_text, aligned_pattern);
+}
 
 extern "C" {
 
 int sa_align_pairs_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_host_pair *pairs, int64_t np,
                           int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend), pairs, np, device, results, aligned_text, aligned_pattern);
 }
 
 int sa_align_pairs_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_host_pair *pairs,
                           int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, gap_open, gap_extend, &band, pairs, np, device, results, aligned_text, aligned_pattern);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).in_band(band), pairs, np, device, results, aligned_text, aligned_pattern);
 }
 
 int sa_align_pairs_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands, const sa_host_pair *pairs,
                            int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern, true, bands);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).in_bands(bands), pairs, np, device, results, aligned_text, aligned_pattern);
 }
 
 int sa_align_pairs_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_host_pair *pairs,
                           int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, gap_open, gap_extend, nullptr, pairs, np, device, results, aligned_text, aligned_pattern, false, nullptr,
-                            &xdrop);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), pairs, np, device, results, aligned_text, aligned_pattern);
 }
 
 }  // extern "C"
 
-// sa_align_pairs_affine and, with `band`, sa_align_pairs_banded, with `with_bands`, sa_align_pairs_band_at, with
-// `xdrop`, sa_align_pairs_extend: the host pairs packed into two arenas
-static int align_host_pairs(const sa_params *P, int32_t gap_open, int32_t gap_extend, const int32_t *band,
-                            const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
-                            char *const *aligned_text, char *const *aligned_pattern, bool with_bands, const sa_band *bands,
-                            const int32_t *xdrop)
-{
-    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
-        return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
-    std::vector<sa_pair> dp((size_t)np);
-    uint64_t tb = 0, pb = 0;
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
-            return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null sequence");
-        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
-        tb += pairs[p].text_len;
-        pb += pairs[p].pattern_len;
-    }
-    DeviceGuard dg(device);
-    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
-    std::vector<char> ht(tb), hp(pb);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
-        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
-    }
-    DevBuf<char> dt, dpat;
-    int rc;
-    if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
-    if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
-    if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
-    return align_affine_device(P, gap_open, gap_extend, dp.data(), np, device, dt.p, dpat.p, results, aligned_text,
-                               aligned_pattern, band, with_bands, bands, xdrop);
-}
-
-int sa::align_seeds_device(const sa_params *P, int32_t go, int32_t ge, int32_t xdrop, const sa_seed *seeds, const sa_pair *pairs,
-                           int64_t np, int device, const void *d_text, const void *d_pattern, sa_result *results,
-                           char *const *aligned_text, char *const *aligned_pattern)
+int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device,
+                           const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
+                           char *const *aligned_pattern)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "seeds aligner: null argument");
@@ -806,7 +603,7 @@ int sa::align_seeds_device(const sa_params *P, int32_t go, int32_t ge, int32_t x
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     SeedTracePlan pl;
     std::string err;
-    if (int rc = make_seeds_trace_plan(P, go, ge, xdrop, pairs, seeds, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err))
+    if (int rc = make_seeds_trace_plan(P, spec, pairs, seeds, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err))
         return fail(rc, err);
     if (!P->alphabet) return fail(SA_ERR_INVALID, "seeds aligner: params->alphabet is null");
     g_stats = AffineStats();
@@ -863,24 +660,13 @@ int sa::align_seeds_device(const sa_params *P, int32_t go, int32_t ge, int32_t x
         ws.events.push_back(ev);
     }
     HIP_TRY(hipMemsetAsync(d_ctrl, 0, 256, st));
-    AlignSeedsArgs fa;
-    ScoreArgs &s = fa.xa.a.sa.s;
-    s.text = (const int8_t *)d_text;
-    s.pattern = (const int8_t *)d_pattern;
-    s.pairs = nullptr;
-    s.table = d_table;
-    s.rows = d_rows;
-    s.out = d_scores;
-    s.ctrl = d_ctrl;
-    s.A = A;
-    s.gap = go;
-    s.key_rowbits = pl.score.key_rowbits;
-    s.row_stride = pl.score.row_stride;
-    fa.xa.a.sa.gap_extend = ge;
-    fa.xa.a.tr.dirs = d_dirs;
-    fa.xa.a.tr.dir_off = d_dir_off;
-    fa.xa.xdrop = xdrop;
+    TracedWaveArgs fa = {};
+    fa.sa = score_args(pl.score, d_text, d_pattern, nullptr, d_order, 0, d_table, d_rows, d_scores, d_ctrl);
+    fa.tr.dirs = d_dirs;
+    fa.tr.dir_off = d_dir_off;
     fa.items = d_items;
+    ScoreArgs &s = fa.sa.s;
+    const WaveChoice choice = wave_choice(pl.score.spec, pl.score.mode, true);
     SeedsCombineArgs ca;
     ca.text = s.text;
     ca.pattern = s.pattern;
@@ -922,8 +708,8 @@ int sa::align_seeds_device(const sa_params *P, int32_t go, int32_t ge, int32_t x
             if (count)
             {
                 const int grid = (int)std::min<int64_t>(count, pl.score.grid);
-                if (A <= 4) hipLaunchKernelGGL((align_seeds_kernel<true>), dim3(grid), dim3(64), 0, st, fa);
-                else hipLaunchKernelGGL((align_seeds_kernel<false>), dim3(grid), dim3(64), 0, st, fa);
+                if (!launch_wave<true>(choice, kTraceRows, A <= 4, grid, st, fa))
+                    return fail(SA_ERR_UNSUPPORTED, "seeds aligner: the call's variant has no kernel instance");
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
@@ -991,31 +777,10 @@ int sa_align_pairs_seeds(const sa_params *P, int32_t gap_open, int32_t gap_exten
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, "sa_align_pairs_seeds: null argument");
-    std::vector<sa_pair> dp((size_t)np);
-    uint64_t tb = 0, pb = 0;
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
-            return fail(SA_ERR_INVALID, "sa_align_pairs_seeds: null sequence");
-        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
-        tb += pairs[p].text_len;
-        pb += pairs[p].pattern_len;
-    }
-    DeviceGuard dg(device);
-    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
-    std::vector<char> ht(tb), hp(pb);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
-        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
-    }
-    DevBuf<char> dt, dpat;
-    int rc;
-    if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
-    if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
-    if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
-    return align_seeds_device(P, gap_open, gap_extend, xdrop, seeds, dp.data(), np, device, dt.p, dpat.p, results, aligned_text,
-                              aligned_pattern);
+    HostArenas in;
+    if (int rc = upload_host_pairs("sa_align_pairs_seeds", pairs, np, device, &in)) return rc;
+    return align_seeds_device(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), seeds, in.pairs.data(), np, device, in.text.p,
+                              in.pattern.p, results, aligned_text, aligned_pattern);
 }
 
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks)

@@ -1,8 +1,9 @@
 // Host-side helpers shared by the .hip files: error reporting, the current-device guard, device
-// allocation and the compute-unit count. Host only; nothing here is device code.
+// allocation, the upload of host pairs and the compute-unit count. Host only; nothing here is device code.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -65,6 +66,40 @@ int dmalloc(T **p, size_t bytes)
         *p = nullptr;
         return fail(SA_ERR_NOMEM, "device allocation of " + std::to_string(bytes) + " bytes failed");
     }
+    return SA_OK;
+}
+
+// The host pairs of a one-shot call packed back to back into two arenas, and the arenas on `device`:
+// what every function that takes sa_host_pair does before it plans. `fn` is the C ABI function, for
+// the message of a null sequence. The device is current only inside the call.
+struct HostArenas {
+    std::vector<sa_pair> pairs;  // the pairs as offsets into the arenas
+    DevBuf<char> text, pattern;
+};
+inline int upload_host_pairs(const char *fn, const sa_host_pair *pairs, int64_t np, int device, HostArenas *out)
+{
+    out->pairs.resize((size_t)np);
+    uint64_t tb = 0, pb = 0;
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
+            return fail(SA_ERR_INVALID, std::string(fn) + ": null sequence");
+        out->pairs[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
+        tb += pairs[p].text_len;
+        pb += pairs[p].pattern_len;
+    }
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    std::vector<char> ht(tb), hp(pb);
+    for (int64_t p = 0; p < np; ++p)
+    {
+        if (pairs[p].text_len) std::memcpy(ht.data() + out->pairs[p].text_offset, pairs[p].text, pairs[p].text_len);
+        if (pairs[p].pattern_len) std::memcpy(hp.data() + out->pairs[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
+    }
+    int rc;
+    if ((rc = dmalloc(&out->text.p, tb)) || (rc = dmalloc(&out->pattern.p, pb))) return rc;
+    if (tb) HIP_TRY(hipMemcpy(out->text.p, ht.data(), tb, hipMemcpyHostToDevice));
+    if (pb) HIP_TRY(hipMemcpy(out->pattern.p, hp.data(), pb, hipMemcpyHostToDevice));
     return SA_OK;
 }
 

@@ -1,9 +1,8 @@
 // Score-only path (sa_hip.h: sa_score_batch*, sa_scorer_*, sa_search*): the score of every pair and
 // the cell it is read from, without direction planes, strip descriptors, records or a traceback.
-// Here are the two kernels, score_kernel<R, MODE, SMALL> (linear gap) and
-// score_affine_kernel<R, MODE, SMALL> (gap open / gap extend), MODE one of sa_mode, both the one wave program of
-// sa_score_wave.h, their launcher, and the host side of both. What a scorer runs is decided in
-// sa_score_plan.cpp (host-only, no HIP).
+// The kernels are the untraced instances of wave_kernel<R, MODE, SMALL, F>, the one wave program of
+// sa_score_wave.h, launched through the table of sa_wave_launch.h; here are the combine kernel of the
+// seeds scorer and the host side. What a scorer runs is decided in sa_score_plan.cpp (host-only, no HIP).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,7 +10,6 @@
 #include <memory>
 #include <numeric>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "sa_affine.h"
@@ -19,117 +17,9 @@
 #include "sa_host.h"
 #include "sa_score_plan.h"
 #include "sa_score_wave.h"
+#include "sa_wave_launch.h"
 
 namespace sa {
-
-template <int R, int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void score_kernel(ScoreArgs a)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<false, R, MODE, SMALL>(a, 0, tab);
-}
-
-template <int R, int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void score_affine_kernel(ScoreAffineArgs aa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, MODE, SMALL>(aa.s, aa.gap_extend, tab);
-}
-
-// score_affine_kernel inside a diagonal band of half-width `band` (sa_hip.h; sa_score_wave.h: BAND)
-struct ScoreBandArgs {
-    ScoreAffineArgs sa;
-    int32_t band;
-};
-
-template <int R, int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void score_band_kernel(ScoreBandArgs ba)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, MODE, SMALL, false, true>(ba.sa.s, ba.sa.gap_extend, tab, TraceArgs(), ba.band);
-}
-
-// score_kernel and score_affine_kernel with free ends (sa_hip.h SA_ENDS_FREE; sa_score_wave.h: ENDS):
-// MODE is the program, SA_FIT when the text's end is free and SA_GLOBAL otherwise, `ends` the flags
-struct ScoreEndsArgs {
-    ScoreAffineArgs sa;
-    int32_t ends;
-};
-
-template <int R, int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void score_ends_kernel(ScoreEndsArgs ea)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<false, R, MODE, SMALL, false, false, true>(ea.sa.s, 0, tab, TraceArgs(), 0, ea.ends);
-}
-
-template <int R, int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void score_affine_ends_kernel(ScoreEndsArgs ea)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, MODE, SMALL, false, false, true>(ea.sa.s, ea.sa.gap_extend, tab, TraceArgs(), 0, ea.ends);
-}
-
-// score_affine_kernel inside a band of the caller's, one per pair (sa_hip.h sa_score_batch_band_at;
-// sa_score_wave.h: BAT). MODE is the program: SA_LOCAL, or with free ends SA_FIT when the text's end is
-// free and SA_GLOBAL otherwise; global and fit alignment run as the ends-free modes they equal.
-struct ScoreBandAtArgs {
-    ScoreAffineArgs sa;
-    int32_t ends;
-    const Band *bands;  // per pair, clipped (ScorePlan::bands)
-};
-
-template <int R, int MODE, bool SMALL>
-__global__ __launch_bounds__(64) void score_band_at_kernel(ScoreBandAtArgs ba)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, MODE, SMALL, false, true, MODE != SA_LOCAL, true>(ba.sa.s, ba.sa.gap_extend, tab, TraceArgs(), 0, ba.ends, ba.bands);
-}
-
-// score_kernel and score_affine_kernel as extension alignment (sa_hip.h sa_score_batch_extend;
-// sa_score_wave.h: EXT): the global borders, the best interior cell before the stop row of `xdrop`
-struct ScoreExtendArgs {
-    ScoreAffineArgs sa;
-    int32_t xdrop;
-};
-
-template <int R, bool SMALL>
-__global__ __launch_bounds__(64) void score_extend_kernel(ScoreExtendArgs xa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<false, R, SA_GLOBAL, SMALL, false, false, false, false, true>(xa.sa.s, 0, tab, TraceArgs(), 0, 0, nullptr, xa.xdrop);
-}
-
-template <int R, bool SMALL>
-__global__ __launch_bounds__(64) void score_affine_extend_kernel(ScoreExtendArgs xa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, SA_GLOBAL, SMALL, false, false, false, false, true>(xa.sa.s, xa.sa.gap_extend, tab, TraceArgs(), 0, 0, nullptr,
-                                                                            xa.xdrop);
-}
-
-// the extension kernels on work items (sa_hip.h sa_score_batch_seeds; sa_score_wave.h: SEED): a.order, a.np
-// and a.out speak of items, a.pairs is unused
-struct ScoreSeedsArgs {
-    ScoreExtendArgs xa;
-    const SeedItem *items;
-};
-
-template <int R, bool SMALL>
-__global__ __launch_bounds__(64) void score_seeds_kernel(ScoreSeedsArgs sa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<false, R, SA_GLOBAL, SMALL, false, false, false, false, true, true>(sa.xa.sa.s, 0, tab, TraceArgs(), 0, 0, nullptr, sa.xa.xdrop,
-                                                                                   sa.items);
-}
-
-template <int R, bool SMALL>
-__global__ __launch_bounds__(64) void score_affine_seeds_kernel(ScoreSeedsArgs sa)
-{
-    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
-    score_wave<true, R, SA_GLOBAL, SMALL, false, false, false, false, true, true>(sa.xa.sa.s, sa.xa.sa.gap_extend, tab, TraceArgs(), 0, 0,
-                                                                                  nullptr, sa.xa.xdrop, sa.items);
-}
 
 // One wave per pair, after the items' fill: the seed's substitution scores, summed by the lanes in a strided
 // loop and over the wave by a prefix sum, the bad-letter flag for the seed's letters, and the pair's
@@ -180,116 +70,11 @@ void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream)
 // ==================================================================================================
 using namespace sa;
 
-namespace {
-
-// score_kernel or, with AFFINE, score_affine_kernel on `grid` one-wave workgroups: the one place that
-// picks <R, MODE, SMALL>. R is 1, 2, 4 or 8; mode is one of sa_mode (the planner has checked it);
-// a.gap is the linear penalty or the gap-open penalty. BAND (affine, global or local; band >= 0) is
-// score_band_kernel. A mode with SA_ENDS_FREE is score_ends_kernel or score_affine_ends_kernel, the fit
-// program when the text's end is free and the global one otherwise.
-// `bands` non-null (BAND): score_band_at_kernel on the per-pair bands; SA_GLOBAL and SA_FIT launch as
-// SA_ENDS_FREE with no flags and with the text's two.
-// score_extend_kernel or, with AFFINE, score_affine_extend_kernel: <R, SMALL> as launch_score picks them
-template <bool AFFINE>
-void launch_score_extend(const ScoreArgs &a, int gap_extend, int xdrop, int R, bool small, int grid, hipStream_t st)
-{
-    const ScoreExtendArgs xa = {{a, gap_extend}, xdrop};
-    auto launch = [&](auto rc, auto smallc) {
-        constexpr int RR = decltype(rc)::value;
-        constexpr bool SMALL = decltype(smallc)::value;
-        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_extend_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, xa);
-        else hipLaunchKernelGGL((score_extend_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, xa);
-    };
-    auto with_r = [&](auto rc) { small ? launch(rc, std::true_type{}) : launch(rc, std::false_type{}); };
-    switch (R)
-    {
-    case 1: with_r(std::integral_constant<int, 1>{}); break;
-    case 2: with_r(std::integral_constant<int, 2>{}); break;
-    case 4: with_r(std::integral_constant<int, 4>{}); break;
-    default: with_r(std::integral_constant<int, 8>{}); break;
-    }
-}
-
-// score_seeds_kernel or, with AFFINE, score_affine_seeds_kernel on the work items
-template <bool AFFINE>
-void launch_score_seeds(const ScoreArgs &a, int gap_extend, int xdrop, const SeedItem *items, int R, bool small, int grid, hipStream_t st)
-{
-    const ScoreSeedsArgs sa = {{{a, gap_extend}, xdrop}, items};
-    auto launch = [&](auto rc, auto smallc) {
-        constexpr int RR = decltype(rc)::value;
-        constexpr bool SMALL = decltype(smallc)::value;
-        if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_seeds_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, sa);
-        else hipLaunchKernelGGL((score_seeds_kernel<RR, SMALL>), dim3(grid), dim3(64), 0, st, sa);
-    };
-    auto with_r = [&](auto rc) { small ? launch(rc, std::true_type{}) : launch(rc, std::false_type{}); };
-    switch (R)
-    {
-    case 1: with_r(std::integral_constant<int, 1>{}); break;
-    case 2: with_r(std::integral_constant<int, 2>{}); break;
-    case 4: with_r(std::integral_constant<int, 4>{}); break;
-    default: with_r(std::integral_constant<int, 8>{}); break;
-    }
-}
-
-template <bool AFFINE, bool BAND = false>
-void launch_score(const ScoreArgs &a, int gap_extend, int R, int mode, bool small, int grid, hipStream_t st, int band = 0,
-                  const Band *bands = nullptr)
-{
-    if (bands && mode == SA_GLOBAL) mode = SA_ENDS_FREE;
-    if (bands && mode == SA_FIT) mode = SA_ENDS_FREE | SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END;
-    const ScoreAffineArgs aa = {a, gap_extend};
-    const ScoreBandArgs ba = {aa, band};
-    const bool ends = (mode & SA_ENDS_FREE) != 0;
-    const ScoreEndsArgs ea = {aa, mode & 15};
-    const ScoreBandAtArgs bat = {aa, mode & 15, bands};
-    const int shape = !ends ? mode : mode & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL;
-    auto launch = [&](auto rc, auto modec, auto smallc) {
-        constexpr int RR = decltype(rc)::value, MODE = decltype(modec)::value;
-        constexpr bool SMALL = decltype(smallc)::value;
-        if constexpr (BAND)
-        {
-            if (bands)
-            {
-                hipLaunchKernelGGL((score_band_at_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, bat);
-                return;
-            }
-            if constexpr (MODE != SA_FIT) hipLaunchKernelGGL((score_band_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ba);
-        }
-        else if (ends)
-        {
-            if constexpr (MODE == SA_LOCAL) return;
-            else if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_ends_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ea);
-            else hipLaunchKernelGGL((score_ends_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, ea);
-        }
-        else if constexpr (AFFINE) hipLaunchKernelGGL((score_affine_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, aa);
-        else hipLaunchKernelGGL((score_kernel<RR, MODE, SMALL>), dim3(grid), dim3(64), 0, st, a);
-    };
-    auto with_r = [&](auto rc) {
-        const std::true_type yes;
-        const std::false_type no;
-        const std::integral_constant<int, SA_GLOBAL> global;
-        const std::integral_constant<int, SA_LOCAL> local;
-        const std::integral_constant<int, SA_FIT> fit;
-        if (shape == SA_LOCAL) small ? launch(rc, local, yes) : launch(rc, local, no);
-        else if (shape == SA_FIT) small ? launch(rc, fit, yes) : launch(rc, fit, no);
-        else small ? launch(rc, global, yes) : launch(rc, global, no);
-    };
-    switch (R)
-    {
-    case 1: with_r(std::integral_constant<int, 1>{}); break;
-    case 2: with_r(std::integral_constant<int, 2>{}); break;
-    case 4: with_r(std::integral_constant<int, 4>{}); break;
-    default: with_r(std::integral_constant<int, 8>{}); break;
-    }
-}
-
-}  // namespace
-
 struct sa_scorer : ScorePlan {
     int device = 0;
     ScorePair *d_pairs = nullptr;
     int32_t *d_order = nullptr, *d_table = nullptr, *d_rows = nullptr;
-    Band *d_bands = nullptr;  // band-at scorer: ScorePlan::bands
+    Band *d_bands = nullptr;  // band-at scorer (spec.band_at): ScorePlan::bands
     sa_score_result *d_out = nullptr;
     uint32_t *d_ctrl = nullptr;
     bool ran = false;
@@ -315,26 +100,18 @@ void free_scorer(sa_scorer *s)
 
 }  // namespace
 
-// sa_scorer_create, sa_scorer_create_affine, sa_scorer_create_banded and sa_scorer_create_band_at:
-// `gapm` null is the linear scorer, `band` non-null the banded one, `with_bands` the band-at one on `bands`,
-// `xdrop` non-null the extension scorer (sa_scorer_create_extend)
-static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair *pairs, int64_t np, int device, sa_scorer **out,
-                         const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr,
-                         const int32_t *xdrop = nullptr)
+// every sa_scorer_create* but the seeds one: `spec` is the variant the function stands for
+static int create_scorer(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
     if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create: null argument");
     *out = nullptr;
-    if (with_bands && !bands && np > 0) return fail(SA_ERR_INVALID, "sa_scorer_create_band_at: bands is null");
-    static const sa_band none = {0, 0};
-    if (with_bands && !bands) bands = &none;  // no pair reads it
+    if (spec.band_at && !spec.bands && np > 0) return fail(SA_ERR_INVALID, "sa_scorer_create_band_at: bands is null");
     DeviceGuard dg(device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    const ScoreExtend ext = {xdrop ? *xdrop : SA_NO_XDROP, false};
-    if (int rc = make_score_plan(P, pairs, np, device_cus(device), score_knobs(), s.get(), &err, gapm, band, bands, xdrop ? &ext : nullptr))
-        return fail(rc, err);
+    if (int rc = make_score_plan(P, spec, pairs, np, device_cus(device), score_knobs(), s.get(), &err)) return fail(rc, err);
     std::vector<ScorePair> h((size_t)np);
     for (int64_t p = 0; p < np; ++p)
         h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
@@ -343,11 +120,11 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
     if ((rc = dmalloc(&s->d_pairs, h.size() * sizeof(ScorePair)))) return rc;
     if ((rc = dmalloc(&s->d_order, (size_t)np * 4))) return rc;
     if ((rc = dmalloc(&s->d_table, 32 * 32 * 4))) return rc;
-    if ((rc = dmalloc(&s->d_rows, (size_t)s->grid * s->row_stride * (s->affine ? 8 : 4)))) return rc;
+    if ((rc = dmalloc(&s->d_rows, (size_t)s->grid * s->row_stride * (s->spec.affine ? 8 : 4)))) return rc;
     if ((rc = dmalloc(&s->d_out, (size_t)np * sizeof(sa_score_result)))) return rc;
     if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
-    if (with_bands && (rc = dmalloc(&s->d_bands, std::max<size_t>((size_t)np, 1) * sizeof(Band)))) return rc;
-    if (with_bands && np) HIP_TRY(hipMemcpy(s->d_bands, s->bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
+    if (spec.band_at && (rc = dmalloc(&s->d_bands, std::max<size_t>((size_t)np, 1) * sizeof(Band)))) return rc;
+    if (spec.band_at && np) HIP_TRY(hipMemcpy(s->d_bands, s->bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
     if (np)
     {
         HIP_TRY(hipMemcpy(s->d_pairs, h.data(), h.size() * sizeof(ScorePair), hipMemcpyHostToDevice));
@@ -360,8 +137,8 @@ static int create_scorer(const sa_params *P, const ScoreGap *gapm, const sa_pair
 
 // sa_scorer_create_seeds: the extension scorer of the work items, with the items, the pairs' seeds and the
 // pairs' results beside it
-static int create_seeds_scorer(const sa_params *P, const ScoreGap &gapm, int32_t xdrop, const sa_seed *seeds, const sa_pair *pairs,
-                               int64_t np, int device, sa_scorer **out)
+static int create_seeds_scorer(const sa_params *P, const WaveSpec &spec, const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device,
+                               sa_scorer **out)
 {
     if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create_seeds: null argument");
     *out = nullptr;
@@ -370,10 +147,8 @@ static int create_seeds_scorer(const sa_params *P, const ScoreGap &gapm, int32_t
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    const ScoreExtend ext = {xdrop, false};
     SeedItems si;
-    if (int rc = make_seeds_score_plan(P, pairs, seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err, &gapm, &ext))
-        return fail(rc, err);
+    if (int rc = make_seeds_score_plan(P, spec, pairs, seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err)) return fail(rc, err);
     s->seeds = true;
     s->seed_pairs = np;
     const size_t ni = si.items.size();
@@ -382,7 +157,7 @@ static int create_seeds_scorer(const sa_params *P, const ScoreGap &gapm, int32_t
     if ((rc = dmalloc(&s->d_items, std::max<size_t>(ni, 1) * sizeof(SeedItem)))) return rc;
     if ((rc = dmalloc(&s->d_order, std::max<size_t>(ni, 1) * 4))) return rc;
     if ((rc = dmalloc(&s->d_table, 32 * 32 * 4))) return rc;
-    if ((rc = dmalloc(&s->d_rows, std::max<size_t>((size_t)s->grid * s->row_stride * (s->affine ? 8 : 4), 8)))) return rc;
+    if ((rc = dmalloc(&s->d_rows, std::max<size_t>((size_t)s->grid * s->row_stride * (s->spec.affine ? 8 : 4), 8)))) return rc;
     if ((rc = dmalloc(&s->d_out, std::max<size_t>(ni, 1) * sizeof(sa_score_result)))) return rc;
     if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
     if ((rc = dmalloc(&s->d_seed_pairs, std::max<size_t>((size_t)np, 1) * sizeof(SeedPair)))) return rc;
@@ -398,62 +173,16 @@ static int create_seeds_scorer(const sa_params *P, const ScoreGap &gapm, int32_t
     return SA_OK;
 }
 
-// the host pairs packed back to back into two arenas, as every host-pair function uploads them
-static int pack_host_pairs(const sa_host_pair *pairs, int64_t np, std::vector<sa_pair> *dp, std::vector<char> *ht, std::vector<char> *hp)
-{
-    dp->resize((size_t)np);
-    uint64_t tb = 0, pb = 0;
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
-            return fail(SA_ERR_INVALID, "sa_score_batch_seeds: null sequence");
-        (*dp)[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
-        tb += pairs[p].text_len;
-        pb += pairs[p].pattern_len;
-    }
-    ht->resize(tb);
-    hp->resize(pb);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if (pairs[p].text_len) std::memcpy(ht->data() + (*dp)[p].text_offset, pairs[p].text, pairs[p].text_len);
-        if (pairs[p].pattern_len) std::memcpy(hp->data() + (*dp)[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
-    }
-    return SA_OK;
-}
-
-// sa_score_batch, sa_score_batch_affine and sa_score_batch_banded
-static int score_batch(const sa_params *P, const ScoreGap *gapm, const sa_host_pair *pairs, int64_t np, int device,
-                       sa_score_result *out, const int32_t *band = nullptr, bool with_bands = false, const sa_band *bands = nullptr,
-                       const int32_t *xdrop = nullptr)
+// every sa_score_batch* but the seeds one
+static int score_batch(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch: null argument");
-    std::vector<sa_pair> dp((size_t)np);
-    uint64_t tb = 0, pb = 0;
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if ((pairs[p].text_len && !pairs[p].text) || (pairs[p].pattern_len && !pairs[p].pattern))
-            return fail(SA_ERR_INVALID, "sa_score_batch: null sequence");
-        dp[p] = sa_pair{tb, pairs[p].text_len, pb, pairs[p].pattern_len};
-        tb += pairs[p].text_len;
-        pb += pairs[p].pattern_len;
-    }
-    DeviceGuard dg(device);
-    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    HostArenas in;
+    if (int rc = upload_host_pairs("sa_score_batch", pairs, np, device, &in)) return rc;
     sa_scorer *raw = nullptr;
-    if (int rc = create_scorer(P, gapm, dp.data(), np, device, &raw, band, with_bands, bands, xdrop)) return rc;
+    if (int rc = create_scorer(P, spec, in.pairs.data(), np, device, &raw)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
-    std::vector<char> ht(tb), hp(pb);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        if (pairs[p].text_len) std::memcpy(ht.data() + dp[p].text_offset, pairs[p].text, pairs[p].text_len);
-        if (pairs[p].pattern_len) std::memcpy(hp.data() + dp[p].pattern_offset, pairs[p].pattern, pairs[p].pattern_len);
-    }
-    DevBuf<char> dt, dpat;
-    int rc;
-    if ((rc = dmalloc(&dt.p, tb)) || (rc = dmalloc(&dpat.p, pb))) return rc;
-    if (tb) HIP_TRY(hipMemcpy(dt.p, ht.data(), tb, hipMemcpyHostToDevice));
-    if (pb) HIP_TRY(hipMemcpy(dpat.p, hp.data(), pb, hipMemcpyHostToDevice));
-    if ((rc = sa_scorer_run(s.get(), dt.p, dpat.p, nullptr))) return rc;
+    if (int rc = sa_scorer_run(s.get(), in.text.p, in.pattern.p, nullptr)) return rc;
     return sa_scorer_fetch(s.get(), out, nullptr);
 }
 
@@ -461,61 +190,49 @@ extern "C" {
 
 int sa_scorer_create(const sa_params *P, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
-    return create_scorer(P, nullptr, pairs, np, device, out);
+    return create_scorer(P, WaveSpec(), pairs, np, device, out);
 }
 
 int sa_scorer_create_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
                             int device, sa_scorer **out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return create_scorer(P, &gapm, pairs, np, device, out);
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend), pairs, np, device, out);
 }
 
 int sa_scorer_create_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_pair *pairs,
                             int64_t np, int device, sa_scorer **out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return create_scorer(P, &gapm, pairs, np, device, out, &band);
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).in_band(band), pairs, np, device, out);
 }
 
 int sa_scorer_create_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands, const sa_pair *pairs,
                              int64_t np, int device, sa_scorer **out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return create_scorer(P, &gapm, pairs, np, device, out, nullptr, true, bands);
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).in_bands(bands), pairs, np, device, out);
 }
 
 int sa_scorer_create_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_pair *pairs,
                             int64_t np, int device, sa_scorer **out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return create_scorer(P, &gapm, pairs, np, device, out, nullptr, false, nullptr, &xdrop);
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), pairs, np, device, out);
 }
 
 int sa_scorer_create_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
                            const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
-    return create_seeds_scorer(P, ScoreGap{gap_open, gap_extend}, xdrop, seeds, pairs, np, device, out);
+    return create_seeds_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), seeds, pairs, np, device, out);
 }
 
 int sa_score_batch_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
                          const sa_host_pair *pairs, int64_t np, int device, sa_seed_result *out)
 {
     if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch_seeds: null argument");
-    std::vector<sa_pair> dp;
-    std::vector<char> ht, hp;
-    if (int rc = pack_host_pairs(pairs, np, &dp, &ht, &hp)) return rc;
-    DeviceGuard dg(device);
-    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
+    HostArenas in;
+    if (int rc = upload_host_pairs("sa_score_batch_seeds", pairs, np, device, &in)) return rc;
     sa_scorer *raw = nullptr;
-    if (int rc = create_seeds_scorer(P, ScoreGap{gap_open, gap_extend}, xdrop, seeds, dp.data(), np, device, &raw)) return rc;
+    if (int rc = create_seeds_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), seeds, in.pairs.data(), np, device, &raw)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
-    DevBuf<char> dt, dpat;
-    int rc;
-    if ((rc = dmalloc(&dt.p, ht.size())) || (rc = dmalloc(&dpat.p, hp.size()))) return rc;
-    if (!ht.empty()) HIP_TRY(hipMemcpy(dt.p, ht.data(), ht.size(), hipMemcpyHostToDevice));
-    if (!hp.empty()) HIP_TRY(hipMemcpy(dpat.p, hp.data(), hp.size(), hipMemcpyHostToDevice));
-    if ((rc = sa_scorer_run(s.get(), dt.p, dpat.p, nullptr))) return rc;
+    if (int rc = sa_scorer_run(s.get(), in.text.p, in.pattern.p, nullptr)) return rc;
     return sa_scorer_fetch_seeds(s.get(), out, nullptr);
 }
 
@@ -534,30 +251,21 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     // the run's first enqueued operation: the work counter and the bad-input flag at zero
     HIP_TRY(hipMemsetAsync(s->d_ctrl, 0, 256, st));
     s->ran = true;
+    // a seeds scorer: the plan is the work items', filled in one launch (both halves of every pair balance
+    // over the waves), then the combine of the pairs
+    if ((s->seeds ? s->seed_pairs : s->num_pairs) == 0) return SA_OK;
+    if (s->num_pairs)
+    {
+        WaveArgs a = {};
+        a.sa = score_args(*s, d_text, d_pattern, s->d_pairs, s->d_order, s->num_pairs, s->d_table, s->d_rows, s->d_out, s->d_ctrl);
+        if (s->seeds) a.items = s->d_items;
+        else a.bands = s->d_bands;
+        if (!launch_wave<false>(wave_choice(s->spec, s->mode, s->seeds), s->R, s->A <= 4, s->grid, st, a))
+            return fail(SA_ERR_UNSUPPORTED, "sa_scorer_run: the scorer's variant has no kernel instance");
+        HIP_TRY(hipGetLastError());
+    }
     if (s->seeds)
     {
-        // the items' fill in one launch (both halves of every pair balance over the waves), then the combine
-        if (s->seed_pairs == 0) return SA_OK;
-        if (s->num_pairs)
-        {
-            ScoreArgs a;
-            a.text = (const int8_t *)d_text;
-            a.pattern = (const int8_t *)d_pattern;
-            a.pairs = nullptr;
-            a.order = s->d_order;
-            a.table = s->d_table;
-            a.rows = s->d_rows;
-            a.out = s->d_out;
-            a.ctrl = s->d_ctrl;
-            a.np = (int32_t)s->num_pairs;
-            a.A = s->A;
-            a.gap = s->gap;
-            a.key_rowbits = s->key_rowbits;
-            a.row_stride = s->row_stride;
-            if (s->affine) launch_score_seeds<true>(a, s->gap_extend, s->xdrop, s->d_items, s->R, s->A <= 4, s->grid, st);
-            else launch_score_seeds<false>(a, 0, s->xdrop, s->d_items, s->R, s->A <= 4, s->grid, st);
-            HIP_TRY(hipGetLastError());
-        }
         SeedsCombineArgs c;
         c.text = (const int8_t *)d_text;
         c.pattern = (const int8_t *)d_pattern;
@@ -570,31 +278,7 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
         c.A = s->A;
         launch_seeds_combine(c, s->seed_pairs, st);
         HIP_TRY(hipGetLastError());
-        return SA_OK;
     }
-    if (s->num_pairs == 0) return SA_OK;
-    ScoreArgs a;
-    a.text = (const int8_t *)d_text;
-    a.pattern = (const int8_t *)d_pattern;
-    a.pairs = s->d_pairs;
-    a.order = s->d_order;
-    a.table = s->d_table;
-    a.rows = s->d_rows;
-    a.out = s->d_out;
-    a.ctrl = s->d_ctrl;
-    a.np = (int32_t)s->num_pairs;
-    a.A = s->A;
-    a.gap = s->gap;
-    a.key_rowbits = s->key_rowbits;
-    a.row_stride = s->row_stride;
-    const bool small = s->A <= 4;
-    if (s->extend && s->affine) launch_score_extend<true>(a, s->gap_extend, s->xdrop, s->R, small, s->grid, st);
-    else if (s->extend) launch_score_extend<false>(a, 0, s->xdrop, s->R, small, s->grid, st);
-    else if (s->d_bands) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, 0, s->d_bands);
-    else if (s->band >= 0) launch_score<true, true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st, s->band);
-    else if (s->affine) launch_score<true>(a, s->gap_extend, s->R, s->mode, small, s->grid, st);
-    else launch_score<false>(a, 0, s->R, s->mode, small, s->grid, st);
-    HIP_TRY(hipGetLastError());
     return SA_OK;
 }
 
@@ -651,35 +335,31 @@ int sa_scorer_info(const sa_scorer *s, int64_t *num_waves, int32_t *rows_per_lan
 
 int sa_score_batch(const sa_params *P, const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
 {
-    return score_batch(P, nullptr, pairs, np, device, out);
+    return score_batch(P, WaveSpec(), pairs, np, device, out);
 }
 
 int sa_score_batch_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_host_pair *pairs, int64_t np,
                           int device, sa_score_result *out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return score_batch(P, &gapm, pairs, np, device, out);
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend), pairs, np, device, out);
 }
 
 int sa_score_batch_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_host_pair *pairs,
                           int64_t np, int device, sa_score_result *out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return score_batch(P, &gapm, pairs, np, device, out, &band);
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).in_band(band), pairs, np, device, out);
 }
 
 int sa_score_batch_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands,
                            const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return score_batch(P, &gapm, pairs, np, device, out, nullptr, true, bands);
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).in_bands(bands), pairs, np, device, out);
 }
 
 int sa_score_batch_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_host_pair *pairs,
                           int64_t np, int device, sa_score_result *out)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return score_batch(P, &gapm, pairs, np, device, out, nullptr, false, nullptr, &xdrop);
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), pairs, np, device, out);
 }
 
 }  // extern "C"
@@ -715,9 +395,9 @@ static int align_hits_linear(const sa_params *P, const std::vector<sa_pair> &hp,
     return SA_OK;
 }
 
-// sa_search and sa_search_affine: `gapm` null is the linear search. They differ in the scorer they
+// sa_search and sa_search_affine: `spec` without the affine gap model is the linear search. They differ in the scorer they
 // create and in the aligner of the hits.
-static int search(const sa_params *P, const ScoreGap *gapm, const char *query, uint64_t m, const char *const *texts,
+static int search(const sa_params *P, const WaveSpec &spec, const char *query, uint64_t m, const char *const *texts,
                   const uint64_t *text_lens, int64_t nt, int k, int device, sa_score_result *scores, int64_t *hit_index,
                   sa_result *hit_results, char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits)
 {
@@ -741,7 +421,7 @@ static int search(const sa_params *P, const ScoreGap *gapm, const char *query, u
     int rc;
     {
         sa_scorer *raw = nullptr;
-        if ((rc = create_scorer(P, gapm, dp.data(), nt, device, &raw))) return rc;
+        if ((rc = create_scorer(P, spec, dp.data(), nt, device, &raw))) return rc;
         std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
         std::vector<char> ht(tb);
         for (int64_t i = 0; i < nt; ++i)
@@ -766,11 +446,10 @@ static int search(const sa_params *P, const ScoreGap *gapm, const char *query, u
     for (int64_t h = 0; h < nh; ++h) hp[h] = dp[rank[h]];
     // the plans have no fit and no ends-free modes: a linear search in one of them aligns through the
     // traced path with gap_open = gap_extend = gap_penalty, which is the linear recurrence
-    const ScoreGap lin = {P->gap_penalty, P->gap_penalty};
-    const ScoreGap *const hg = gapm ? gapm : P->mode == SA_FIT || (P->mode & SA_ENDS_FREE) ? &lin : nullptr;
-    rc = hg ? align_affine_device(P, hg->open, hg->extend, hp.data(), nh, device, dt.p, dq.p, hit_results, aligned_text,
-                                  aligned_pattern)
-            : align_hits_linear(P, hp, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern);
+    const bool traced = spec.affine || P->mode == SA_FIT || (P->mode & SA_ENDS_FREE);
+    const WaveSpec hs = spec.affine ? spec : WaveSpec::gaps(P->gap_penalty, P->gap_penalty);
+    rc = traced ? align_affine_device(P, hs, hp.data(), nh, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern)
+                : align_hits_linear(P, hp, device, dt.p, dq.p, hit_results, aligned_text, aligned_pattern);
     if (rc) return rc;
     for (int64_t h = 0; h < nh; ++h) hit_index[h] = rank[h];
     *num_hits = nh;
@@ -783,7 +462,7 @@ int sa_search(const sa_params *P, const char *query, uint64_t m, const char *con
               int64_t nt, int k, int device, sa_score_result *scores, int64_t *hit_index, sa_result *hit_results,
               char *const *aligned_text, char *const *aligned_pattern, int64_t *num_hits)
 {
-    return search(P, nullptr, query, m, texts, text_lens, nt, k, device, scores, hit_index, hit_results, aligned_text,
+    return search(P, WaveSpec(), query, m, texts, text_lens, nt, k, device, scores, hit_index, hit_results, aligned_text,
                   aligned_pattern, num_hits);
 }
 
@@ -792,8 +471,7 @@ int sa_search_affine(const sa_params *P, int32_t gap_open, int32_t gap_extend, c
                      sa_score_result *scores, int64_t *hit_index, sa_result *hit_results, char *const *aligned_text,
                      char *const *aligned_pattern, int64_t *num_hits)
 {
-    const ScoreGap gapm = {gap_open, gap_extend};
-    return search(P, &gapm, query, m, texts, text_lens, nt, k, device, scores, hit_index, hit_results, aligned_text,
+    return search(P, WaveSpec::gaps(gap_open, gap_extend), query, m, texts, text_lens, nt, k, device, scores, hit_index, hit_results, aligned_text,
                   aligned_pattern, num_hits);
 }
 

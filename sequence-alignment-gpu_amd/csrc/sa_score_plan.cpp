@@ -25,7 +25,7 @@ const ScoreKnobs &score_knobs()
 // so do the seeds instances, register for register (linear and affine)
 int score_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 7 : 8; }
 
-// score_affine_kernel: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4); extension: 59, 79, 114, 154
+// the affine instances: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4); extension: 59, 79, 114, 154
 int score_affine_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 5 : 8; }
 
 namespace {
@@ -77,9 +77,8 @@ extern "C" int sa_band_reachable(int32_t mode, uint64_t text_len, uint64_t patte
     return 0;
 }
 
-int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine, const int32_t *band, const sa_band *bands,
-                    const ScoreExtend *extend)
+int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                    ScorePlan *out, std::string *err)
 {
     auto fail = [&](int code, const char *msg) { *err = msg; return code; };
     if (!P || !out || np < 0 || (np > 0 && !pairs) || !P->score_matrix) return fail(SA_ERR_INVALID, "scorer: null argument");
@@ -89,30 +88,33 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     if (P->mode != SA_GLOBAL && P->mode != SA_LOCAL && P->mode != SA_FIT && !ends)
         return fail(SA_ERR_INVALID, "mode must be SA_GLOBAL, SA_LOCAL, SA_FIT or SA_ENDS_FREE with its flags");
     if (np > INT32_MAX) return fail(SA_ERR_UNSUPPORTED, "more than 2^31-1 pairs");
-    if (band)
+    bool affine = spec.affine;
+    const sa_band *const bands = spec.bands;
+    if (spec.banded)
     {
         if (!affine) return fail(SA_ERR_INVALID, "a band takes gap_open and gap_extend");
-        if (*band < 0) return fail(SA_ERR_INVALID, "band must be >= 0");
+        if (spec.band < 0) return fail(SA_ERR_INVALID, "band must be >= 0");
         if (P->mode == SA_FIT) return fail(SA_ERR_UNSUPPORTED, "SA_FIT takes no band");
         if (ends) return fail(SA_ERR_UNSUPPORTED, "SA_ENDS_FREE takes no band");
     }
-    if (bands && (!affine || band)) return fail(SA_ERR_INVALID, "per-pair bands take gap_open and gap_extend and no half-width");
-    if (extend)
+    if (spec.band_at && (!affine || spec.banded)) return fail(SA_ERR_INVALID, "per-pair bands take gap_open and gap_extend and no half-width");
+    if (spec.band_at && !bands && np > 0) return fail(SA_ERR_INVALID, "scorer: null argument");
+    if (spec.extend)
     {
         if (!affine) return fail(SA_ERR_INVALID, "extension alignment takes gap_open and gap_extend");
         if (P->mode != SA_GLOBAL) return fail(SA_ERR_INVALID, "extension alignment takes mode SA_GLOBAL: its borders are global's");
-        if (extend->xdrop < SA_NO_XDROP || extend->xdrop >= (1 << 30)) return fail(SA_ERR_INVALID, "xdrop must be SA_NO_XDROP or 0 .. 2^30 - 1");
-        if (band || bands) return fail(SA_ERR_UNSUPPORTED, "extension alignment inside a band (band or bands with xdrop) is not built");
+        if (spec.xdrop < SA_NO_XDROP || spec.xdrop >= (1 << 30)) return fail(SA_ERR_INVALID, "xdrop must be SA_NO_XDROP or 0 .. 2^30 - 1");
+        if (spec.banded || spec.band_at) return fail(SA_ERR_UNSUPPORTED, "extension alignment inside a band (band or bands with xdrop) is not built");
     }
     // gap open == gap extend is the linear recurrence of that penalty: the linear instances, step costs and
     // boundary row, with the penalty in the place of P->gap_penalty
     int64_t g = P->gap_penalty;
-    if (extend && !extend->traced && affine->open == affine->extend)
+    if (spec.extend && !spec.traced && spec.gap_open == spec.gap_extend)
     {
-        g = affine->open;
-        affine = nullptr;
+        g = spec.gap_open;
+        affine = false;
     }
-    const bool banded = band || bands;
+    const bool banded = spec.banded || spec.band_at;
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
     if (R == 16 || R == 32) R = 8;  // a params struct shared with a plan: the scorer's tallest strip
@@ -122,8 +124,8 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     // |open| and |extend|, and as negative if either is ----
     if (affine)
     {
-        g = std::max(std::llabs((long long)affine->open), std::llabs((long long)affine->extend));
-        if (affine->open < 0 || affine->extend < 0) g = -g;
+        g = std::max(std::llabs((long long)spec.gap_open), std::llabs((long long)spec.gap_extend));
+        if (spec.gap_open < 0 || spec.gap_extend < 0) g = -g;
     }
     int64_t smax = INT32_MIN, sabs = 0;
     for (int e = 0; e < A * A; ++e)
@@ -151,7 +153,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     }
     // ---- the band-at scorer: every pair's band is a band and admits an alignment; the kernels take the
     // clipped bands and rely on both ----
-    if (bands)
+    if (spec.band_at)
     {
         pl.bands.resize((size_t)np);
         for (int64_t p = 0; p < np; ++p)
@@ -173,20 +175,19 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     }
     // a pair's band and the window of one of its strips: band_window_at is band_window on the bands of band_of
     auto pair_band = [&](int64_t p) {
-        return bands ? pl.bands[p] : band_of((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, *band);
+        return spec.band_at ? pl.bands[p] : band_of((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, spec.band);
     };
     pl.key_rowbits = std::max(1, bitlen(lmax + 1));
-    if ((P->mode == SA_LOCAL || extend) && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * pl.key_rowbits))
+    if ((P->mode == SA_LOCAL || spec.extend) && (bitlen(hmax_local) > 26 || bitlen(hmax_local) > 64 - 2 * pl.key_rowbits))
         return fail(SA_ERR_UNSUPPORTED, "local scores may exceed the best-cell key range");
 
     pl.mode = P->mode;
     pl.A = A;
-    pl.gap = affine ? affine->open : (int)g;
-    pl.affine = affine != nullptr;
-    pl.gap_extend = affine ? affine->extend : 0;
-    pl.band = band ? *band : -1;
-    pl.extend = extend != nullptr;
-    pl.xdrop = extend ? extend->xdrop : SA_NO_XDROP;
+    pl.gap = affine ? spec.gap_open : (int)g;
+    pl.spec = spec;
+    pl.spec.affine = affine;
+    pl.spec.gap_extend = affine ? spec.gap_extend : 0;
+    pl.spec.bands = nullptr;  // the caller's; the plan keeps the clipped copy
     pl.num_pairs = np;
     pl.num_cu = kn.max_cus > 0 ? std::min(num_cu, kn.max_cus) : num_cu;
 
@@ -214,7 +215,7 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
     static const int kR[4] = {1, 2, 4, 8};
     const bool fit = P->mode == SA_FIT || (ends && (P->mode & SA_FREE_TEXT_END));
     const int step_base = (affine ? kScoreAffineStepBase : kScoreStepBase) + (fit ? kScoreFitStepBest - kScoreFitStepSelect : 0);
-    const int step_row = (P->mode == SA_LOCAL || extend ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
+    const int step_row = (P->mode == SA_LOCAL || spec.extend ? (affine ? kScoreAffineStepRowLocal : kScoreStepRowLocal)
                                               : (affine ? kScoreAffineStepRowGlobal : kScoreStepRowGlobal)) +
                          (fit ? kScoreFitStepSelect : 0);
     int best = 0;
@@ -263,17 +264,16 @@ int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int nu
                         : affine ? score_affine_waves_per_simd(pl.R) : score_waves_per_simd(pl.R);
     pl.grid = (int)std::min<int64_t>(np, (int64_t)pl.num_cu * 4 * pl.waves_per_simd);
     pl.row_stride = (pl.max_text + 63) / 64 * 64 + 64;
-    const uint64_t per_pair = 24 /* descriptor */ + (bands ? 8 : 0) /* band */ + 4 /* order */ + sizeof(sa_score_result);
+    const uint64_t per_pair = 24 /* descriptor */ + (spec.band_at ? 8 : 0) /* band */ + 4 /* order */ + sizeof(sa_score_result);
     pl.device_bytes = pl.input_bytes + (uint64_t)np * per_pair + (uint64_t)pl.grid * pl.row_stride * (affine ? 8 : 4) +
                       32 * 32 * 4 /* score table */ + 256 /* counter and flags */;
     return SA_OK;
 }
 
-int make_seeds_score_plan(const sa_params *P, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
-                          const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err, const ScoreGap *affine,
-                          const ScoreExtend *extend)
+int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
+                          const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err)
 {
-    if (!items || !extend)
+    if (!items || !spec.extend)
     {
         *err = "seeds scorer: null argument";
         return SA_ERR_INVALID;
@@ -281,7 +281,7 @@ int make_seeds_score_plan(const sa_params *P, const sa_pair *pairs, const sa_see
     // the mode, the xdrop and the limits, on the whole pairs: the sum of the three scores of a pair stays
     // under the bound of its (n, m), and so does every key
     ScorePlan whole;
-    if (int rc = make_score_plan(P, pairs, np, num_cu, kn, &whole, err, affine, nullptr, nullptr, extend)) return rc;
+    if (int rc = make_score_plan(P, spec, pairs, np, num_cu, kn, &whole, err)) return rc;
     if (np > 0 && !seeds)
     {
         *err = "seeds is null";
@@ -317,7 +317,7 @@ int make_seeds_score_plan(const sa_params *P, const sa_pair *pairs, const sa_see
     // the items as extension pairs: cost, R, order by cells, grid and boundary rows
     std::vector<sa_pair> ip(items->items.size());
     for (size_t k = 0; k < ip.size(); ++k) ip[k] = sa_pair{0, items->items[k].n, 0, items->items[k].m};
-    if (int rc = make_score_plan(P, ip.data(), (int64_t)ip.size(), num_cu, kn, out, err, affine, nullptr, nullptr, extend)) return rc;
+    if (int rc = make_score_plan(P, spec, ip.data(), (int64_t)ip.size(), num_cu, kn, out, err)) return rc;
     out->device_bytes += whole.input_bytes - out->input_bytes + (uint64_t)ip.size() * (sizeof(SeedItem) - 24) +
                          (uint64_t)np * (sizeof(SeedPair) + sizeof(sa_seed_result));
     out->input_bytes = whole.input_bytes;

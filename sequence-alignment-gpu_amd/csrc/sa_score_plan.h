@@ -22,15 +22,15 @@ struct ScoreKnobs {
 };
 const ScoreKnobs &score_knobs();
 
-// Instruction counts of score_kernel's steady loop (sa_score.hip, counted in the gfx950 assembly;
+// Instruction counts of the linear instances' steady loop (wave_kernel, kVarLinear; counted in the gfx950 assembly;
 // DESIGN.md §3.4): one step of a wave costs kScoreStepBase + R * kScoreStepRow* instructions (the
 // lane shifts and the loop; per row the score, the three-way maximum and, for local pairs, the
 // clamp at zero and the running best) and advances 64 R cells.
 constexpr int kScoreStepBase = 14;
 constexpr int kScoreStepRowGlobal = 6;
 constexpr int kScoreStepRowLocal = 10;
-// The same of score_affine_kernel's steady loop (sa_score_affine.hip): eight lane shifts where the
-// linear kernel has five, and per row the two extra states E and F (two subtractions and a maximum
+// The same of the affine instances' steady loop (kVarAffine): eight lane shifts where the
+// linear instances have five, and per row the two extra states E and F (two subtractions and a maximum
 // each, where the linear row has two subtractions).
 constexpr int kScoreAffineStepBase = 18;
 constexpr int kScoreAffineStepRowGlobal = 10;
@@ -43,17 +43,50 @@ constexpr int kScoreAffineStepRowLocal = 14;
 constexpr int kScoreFitStepBest = 5;
 constexpr int kScoreFitStepSelect = 1;
 
-// The affine gap model of a scorer: a gap of k cells costs open + (k - 1) * extend. With it,
-// sa_params.gap_penalty is ignored.
-struct ScoreGap {
-    int32_t open, extend;
-};
+// What a call asks of the wave program (sa_score_wave.h) beyond its sa_params: the variant, as a value. The
+// C ABI functions build one, the planners check it against the mode and the pairs, the plan records the
+// one it runs, and the launch table (sa_wave_launch.h) turns that into an instance.
+struct WaveSpec {
+    bool affine = false;           // a gap of k cells costs gap_open + (k - 1) * gap_extend, and
+    int32_t gap_open = 0;          // sa_params.gap_penalty is ignored
+    int32_t gap_extend = 0;
+    bool banded = false;           // inside the diagonal band of one half-width (sa_hip.h)
+    int32_t band = 0;
+    bool band_at = false;          // inside a band of the caller's per pair (sa_hip.h sa_band)
+    const sa_band *bands = nullptr;
+    bool extend = false;           // extension alignment (sa_hip.h sa_score_batch_extend) under
+    int32_t xdrop = SA_NO_XDROP;   // this X-drop, SA_NO_XDROP for none
+    bool traced = false;           // the aligners' instances: direction words, affine whatever the penalties
 
-// Extension alignment (sa_hip.h sa_score_batch_extend): the X-drop of the call, SA_NO_XDROP for none.
-// `traced` is set by the trace planner: the traced instance is the affine one whatever the penalties.
-struct ScoreExtend {
-    int32_t xdrop;
-    bool traced;
+    static WaveSpec gaps(int32_t open, int32_t extend)
+    {
+        WaveSpec s;
+        s.affine = true;
+        s.gap_open = open;
+        s.gap_extend = extend;
+        return s;
+    }
+    WaveSpec in_band(int32_t half_width) const
+    {
+        WaveSpec s = *this;
+        s.banded = true;
+        s.band = half_width;
+        return s;
+    }
+    WaveSpec in_bands(const sa_band *per_pair) const
+    {
+        WaveSpec s = *this;
+        s.band_at = true;
+        s.bands = per_pair;
+        return s;
+    }
+    WaveSpec extending(int32_t x) const
+    {
+        WaveSpec s = *this;
+        s.extend = true;
+        s.xdrop = x;
+        return s;
+    }
 };
 
 #if defined(__HIPCC__)
@@ -135,12 +168,9 @@ constexpr uint64_t kBandScoreLimit = 1ull << 29;
 
 struct ScorePlan {
     int mode = 0, A = 0, gap = 0, R = 1, key_rowbits = 1;  // gap: the linear penalty, or gap open
-    bool affine = false;           // score_affine_kernel: gap, gap_extend
-    int gap_extend = 0;
-    int band = -1;                 // banded scorer (affine only): the half-width; -1: the whole rectangle
-    std::vector<Band> bands;       // band-at scorer (affine only): every pair's band, clipped (band_clip); band is -1
-    bool extend = false;           // extension scorer: mode is SA_GLOBAL, the program local's; affine iff open != extend
-    int xdrop = SA_NO_XDROP;       // its X-drop
+    WaveSpec spec;                 // the variant the scorer runs: the call's, but affine false where the linear
+                                   // instances serve (an extension with gap open == gap extend) and bands null
+    std::vector<Band> bands;       // band-at scorer: every pair's band, clipped (band_clip)
     int num_cu = 0, waves_per_simd = 0, grid = 0;
     int64_t num_pairs = 0;
     uint64_t max_text = 0;         // longest text
@@ -155,22 +185,22 @@ struct ScorePlan {
 };
 
 // Plans `np` pairs for a device of `num_cu` compute units. Returns SA_OK, or the SA_ERR_* code with
-// its message in *err. `affine` null: the linear gap P->gap_penalty; else the affine gap model.
-// `band` non-null: the banded scorer of that half-width (affine only, global or local): a strip is
-// charged the steps of its window, the work order and padded_cells count band cells, and the score
-// limit is kBandScoreLimit.
-// `bands` non-null (and `band` null): the band-at scorer (sa_hip.h sa_score_batch_band_at), bands[p] the
-// band of pair p, in every mode: lo > hi and a pair that sa_band_reachable denies are SA_ERR_INVALID, the
-// message naming the pair; the rest as with `band`, on the clipped bands (ScorePlan::bands), and the
-// descriptors count 8 more bytes per pair.
-// `extend` non-null: the extension scorer (sa_hip.h sa_score_batch_extend), which takes `affine`, the mode
-// SA_GLOBAL and an xdrop of SA_NO_XDROP .. 2^30 - 1 (else SA_ERR_INVALID) and no band of either kind
-// (SA_ERR_UNSUPPORTED). Cost, R, grid and bytes are the local program's, the linear one when gap open
-// equals gap extend (unless `traced`); xdrop changes nothing, the stop rows are not known beforehand. The
-// limits are the int32 one and the local best-cell key's.
-int make_score_plan(const sa_params *P, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
-                    ScorePlan *out, std::string *err, const ScoreGap *affine = nullptr, const int32_t *band = nullptr,
-                    const sa_band *bands = nullptr, const ScoreExtend *extend = nullptr);
+// its message in *err. `spec` says what the call asks for:
+//  - affine false: the linear gap P->gap_penalty; else the affine gap model.
+//  - banded: the banded scorer of that half-width (affine only, global or local): a strip is charged the
+//    steps of its window, the work order and padded_cells count band cells, and the score limit is
+//    kBandScoreLimit.
+//  - band_at (and not banded): the band-at scorer (sa_hip.h sa_score_batch_band_at), bands[p] the band of pair
+//    p, in every mode: lo > hi and a pair that sa_band_reachable denies are SA_ERR_INVALID, the message
+//    naming the pair; the rest as with `banded`, on the clipped bands (ScorePlan::bands), and the
+//    descriptors count 8 more bytes per pair. `bands` may be null when there is no pair.
+//  - extend: the extension scorer (sa_hip.h sa_score_batch_extend), which takes the affine gap model, the mode
+//    SA_GLOBAL and an xdrop of SA_NO_XDROP .. 2^30 - 1 (else SA_ERR_INVALID) and no band of either kind
+//    (SA_ERR_UNSUPPORTED). Cost, R, grid and bytes are the local program's, the linear one when gap open
+//    equals gap extend (unless `traced`); xdrop changes nothing, the stop rows are not known beforehand. The
+//    limits are the int32 one and the local best-cell key's.
+int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                    ScorePlan *out, std::string *err);
 
 // Seed extension (sa_hip.h sa_score_batch_seeds): a pair becomes up to two work items, the extension of
 // its left half read backwards and of its right half read forwards; an empty half is no item. The
@@ -194,15 +224,14 @@ struct SeedItems {
     std::vector<SeedPair> pairs;
 };
 
-// Plans the seeds scorer: `seeds` null with pairs, ts + L > n and ps + L > m are SA_ERR_INVALID, the
+// Plans the seeds scorer (`spec` an extension's): `seeds` null with pairs, ts + L > n and ps + L > m are SA_ERR_INVALID, the
 // message naming the first such pair; the mode, the xdrop and the limits are make_score_plan's for the
 // extension scorer on the whole pairs' (n, m). The plan is then make_score_plan's for the items as
 // extension pairs: costed by the local step model, ordered by cells (plan->order holds item indices and
 // plan->num_pairs the number of items). input_bytes is the whole pairs'; device_bytes adds the items'
 // 8 bytes above a pair descriptor and, per pair, a SeedPair and a sa_seed_result.
-int make_seeds_score_plan(const sa_params *P, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
-                          const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err, const ScoreGap *affine,
-                          const ScoreExtend *extend);
+int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
+                          const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err);
 
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).

@@ -1,5 +1,27 @@
-// The wave program of the score-only kernels (sa_score.hip): score_kernel (linear gap) and
-// score_affine_kernel (gap open / gap extend) are both score_wave, without and with AFFINE.
+// The wave program of the score-only path (sa_score.hip) and of the traced fill of the affine aligners
+// (sa_affine_walk.hip): score_wave<R, MODE, SMALL, F>, every instance of it the kernel
+// wave_kernel<R, MODE, SMALL, F>. R is the rows per lane, MODE the program (SA_GLOBAL, SA_LOCAL or SA_FIT),
+// SMALL an alphabet of at most four letters, and F the variant, a mask of the kWave* flags below. The
+// variants that exist, the programs they run and what they read from the kernel argument (WaveArgs;
+// traced, TracedWaveArgs with the direction arena `tr`):
+//
+//   variant            flags                           programs             reads
+//   kVarLinear         -                               global, local, fit   -
+//   kVarAffine         Affine                          global, local, fit   gap_extend
+//   kVarBand           Affine Band                     global, local        gap_extend, band
+//   kVarEnds           Ends                            global, fit          ends
+//   kVarAffineEnds     Affine Ends                     global, fit          gap_extend, ends
+//   kVarBandAtLocal    Affine Band BandAt              local                gap_extend, bands
+//   kVarBandAt         Affine Band BandAt Ends         global, fit          gap_extend, ends, bands
+//   kVarExtend         Extend                          global               xdrop
+//   kVarAffineExtend   Affine Extend                   global               gap_extend, xdrop
+//   kVarSeeds          Extend Seed                     global               xdrop, items
+//   kVarAffineSeeds    Affine Extend Seed              global               gap_extend, xdrop, items
+//
+// Untraced, every row exists at R = 1, 2, 4, 8; with Trace added, the affine rows exist at R = 8. The
+// static_asserts of score_wave are the rule for a legal combination, the table of sa_wave_launch.h is the
+// set that is instantiated, and the sections below say what each flag does (AFFINE, TRACE, BAND, ENDS, BAT,
+// EXT and SEED are the names the program gives its flags).
 //
 // The kernels are persistent with one wave per workgroup. A wave draws the next pair of the work
 // order (sa_score_plan.cpp: most cells first) with one atomicAdd and runs the pair's strips of 64 R
@@ -39,13 +61,13 @@
 // DESIGN.md §3.4 has the resource usage of the instances, the rule for R and the step costs the
 // planner uses.
 //
-// TRACE (AFFINE, R = 8: align_affine_kernel, sa_affine_walk.hip) also records, per cell, where H came
+// TRACE (AFFINE, R = 8: the instances of sa_affine_walk.hip) also records, per cell, where H came
 // from and whether E and F extend a run: a nibble per row, so a lane's eight rows are one dword per
 // step, stored at dirs[(strip * steps + t) * 64 + lane] of the pair's directions, steps = 64 nbodies.
 // Every step stores, the predicated ones too; the words of lanes outside columns 1..n and the nibbles
 // of rows past m are never read. DESIGN.md §3.5 has the nibble and the walk that reads it.
 //
-// BAND (AFFINE, global or local: score_band_kernel, align_band_kernel) keeps to the diagonal band of
+// BAND (AFFINE, global or local: kVarBand) keeps to the diagonal band of
 // sa_hip.h: cell (i, j) is in band iff lo <= j - i <= hi, and H, E and F of every other cell are
 // kBandSentinel. Everything banded is under `if constexpr (BAND)` or MASK; the other instances compile
 // to what they were. A strip runs only the bodies of its window (band_window, sa_score_plan.h), with
@@ -76,7 +98,7 @@
 //  - TRACE stores a word only for the steps the strip runs: the pair's directions are the strips'
 //    windows one after another, 64 (b1 - b0) steps of 64 words each (trace_band_dir_bytes).
 //
-// ENDS (MODE SA_GLOBAL or SA_FIT; score_ends_kernel, score_affine_ends_kernel, align_ends_kernel) is
+// ENDS (MODE SA_GLOBAL or SA_FIT; kVarEnds, kVarAffineEnds) is
 // ends-free alignment, sa_hip.h SA_ENDS_FREE: `ends` holds the flags, TB, TE, PB and PE for short.
 // TE decides the program: unset it is the global program, set it is the fit program (the running best
 // of row m), and the host launches MODE accordingly. The other three flags are wave-uniform values and
@@ -93,8 +115,7 @@
 //  - An empty side: every candidate is a border cell; the early-out compares the border values at
 //    0, 1 and the side's length, as a gap's cost need not grow with its length.
 //
-// BAT (BAND; MODE SA_LOCAL, or ENDS with the global or the fit program: score_band_at_kernel,
-// align_band_at_kernel) is the band program on a band of the caller's, sa_hip.h sa_band: `bands` holds
+// BAT (BAND; MODE SA_LOCAL, or ENDS with the global or the fit program: kVarBandAtLocal, kVarBandAt) is the band program on a band of the caller's, sa_hip.h sa_band: `bands` holds
 // one (lo, hi) per pair, clipped to [-m, n] by the planner and read once per pair as a wave-uniform
 // value. Neither lo <= 0 <= hi nor "every row has an in-band cell" holds any more; the planner admits
 // only pairs with an alignment inside their band (sa_band_reachable), and in such a pair every in-band
@@ -115,8 +136,7 @@
 //    counts H[0][n] and H[m][0] only in band; reachability leaves at least one candidate.
 //  - An empty side: the candidates are the border's in-band cells.
 //
-// EXT (MODE SA_GLOBAL, no band, no free ends: score_extend_kernel, score_affine_extend_kernel,
-// align_extend_kernel) is extension alignment, sa_hip.h sa_score_batch_extend: the start anchored at the
+// EXT (MODE SA_GLOBAL, no band, no free ends: kVarExtend, kVarAffineExtend) is extension alignment, sa_hip.h sa_score_batch_extend: the start anchored at the
 // origin, the end at the best interior cell of the rows before the stop row i*, `xdrop` a wave-uniform
 // kernel argument. It is the local program's result on the global program's cells; everything of EXT is
 // under `if constexpr (EXT)` or a constant condition, so the other instances compile to what they were.
@@ -140,7 +160,7 @@
 //    every word: it never reads a word of a strip that did not run.
 //  - xdrop SA_NO_XDROP skips the test: every row counts, as with a drop that no score can reach.
 //
-// SEED (EXT: score_seeds_kernel, score_affine_seeds_kernel, align_seeds_kernel) is seed extension, sa_hip.h
+// SEED (EXT: kVarSeeds, kVarAffineSeeds) is seed extension, sa_hip.h
 // sa_score_batch_seeds: the wave draws work items (SeedItem, sa_score_plan.h), a pair's left half or its
 // right half, where the other instances draw pairs, and `order`, `np`, `out` and TRACE's dir_off speak of
 // items. An item is an extension pair whose letter k lies at base[dir * k], base the address of the half's
@@ -154,6 +174,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -209,14 +230,80 @@ enum { kDirLeft = 0, kDirDiag = 1, kDirTop = 2, kDirStop = 3, kDirEExt = 4, kDir
 struct MaskedStep : std::true_type {
 };
 
-// `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row sit in
-// registers); `gap_extend` is read only by AFFINE, `tr` only by TRACE.
-template <bool AFFINE, int R, int MODE, bool SMALL, bool TRACE = false, bool BAND = false, bool ENDS = false, bool BAT = false,
-          bool EXT = false, bool SEED = false>
-__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr = TraceArgs(),
-                                           int band = 0, int ends = 0, const Band *bands = nullptr, int xdrop = SA_NO_XDROP,
-                                           const SeedItem *items = nullptr)
+// The variant of an instance, one bit per feature of the header comment. The legal combinations are the
+// static_asserts of score_wave; the named composites are the variants that exist (sa_wave_launch.h
+// has the table that instantiates them).
+enum : unsigned {
+    kWaveAffine = 1u << 0,
+    kWaveTrace = 1u << 1,
+    kWaveBand = 1u << 2,
+    kWaveEnds = 1u << 3,
+    kWaveBandAt = 1u << 4,
+    kWaveExtend = 1u << 5,
+    kWaveSeed = 1u << 6,
+};
+constexpr unsigned kVarLinear = 0, kVarAffine = kWaveAffine;
+constexpr unsigned kVarBand = kWaveAffine | kWaveBand;
+constexpr unsigned kVarEnds = kWaveEnds, kVarAffineEnds = kWaveAffine | kWaveEnds;
+constexpr unsigned kVarBandAtLocal = kWaveAffine | kWaveBand | kWaveBandAt;  // the local program
+constexpr unsigned kVarBandAt = kVarBandAtLocal | kWaveEnds;                 // the global and the fit program
+constexpr unsigned kVarExtend = kWaveExtend, kVarAffineExtend = kWaveAffine | kWaveExtend;
+constexpr unsigned kVarSeeds = kVarExtend | kWaveSeed, kVarAffineSeeds = kVarAffineExtend | kWaveSeed;
+
+// The kernel argument of every instance: the base arguments, then (traced instances) the direction arena,
+// then one int and one pointer whose meaning is the variant's. The static_asserts of score_wave make the
+// union members mutually exclusive; an instance loads only the fields of its flags.
+struct WaveArgs {
+    ScoreAffineArgs sa;
+    union {
+        int32_t band;   // kWaveBand without kWaveBandAt: the half-width
+        int32_t ends;   // kWaveEnds: the SA_FREE_* flags
+        int32_t xdrop;  // kWaveExtend
+    };
+    union {
+        const Band *bands;      // kWaveBandAt: per pair, clipped (ScorePlan::bands)
+        const SeedItem *items;  // kWaveSeed: a.order, a.np and a.out speak of items, a.pairs is unused
+    };
+};
+struct TracedWaveArgs {
+    ScoreAffineArgs sa;
+    TraceArgs tr;
+    union {
+        int32_t band, ends, xdrop;
+    };
+    union {
+        const Band *bands;
+        const SeedItem *items;
+    };
+};
+// the offsets the instances were compiled against before the variants shared one struct
+static_assert(offsetof(WaveArgs, sa.gap_extend) == 88 && offsetof(WaveArgs, band) == 96 && offsetof(WaveArgs, bands) == 104 &&
+                  sizeof(WaveArgs) == 112,
+              "untraced kernel arguments: gap_extend, the variant's int, the variant's pointer");
+static_assert(offsetof(TracedWaveArgs, tr.dirs) == 96 && offsetof(TracedWaveArgs, tr.dir_off) == 104 &&
+                  offsetof(TracedWaveArgs, band) == 112 && offsetof(TracedWaveArgs, bands) == 120 && sizeof(TracedWaveArgs) == 128,
+              "traced kernel arguments: the direction arena before the variant's fields");
+// (through a class template, so that a kernel's mangled name spells F and not the expression on it)
+template <unsigned F>
+struct WaveArgsFor {
+    using type = std::conditional_t<(F & kWaveTrace) != 0, TracedWaveArgs, WaveArgs>;
+};
+template <unsigned F>
+using ArgsOf = typename WaveArgsFor<F>::type;
+
+// The program. `tab` is the kernel's LDS copy of the score table (SMALL: unused, the four scores of a row
+// sit in registers). The variant's values arrive as function arguments, unpacked by wave_kernel below,
+// its only caller, and not as loads from the argument struct inside the body: the optimizer ranks an
+// argument and a loaded value differently when it orders operands, and one more level of inlining moves
+// code as well; the instances are to stay what they were (profiles/r19/score_disasm_compare.md).
+template <int R, int MODE, bool SMALL, unsigned F>
+__device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr, int band, int ends,
+                                           const Band *bands, int xdrop, const SeedItem *items)
 {
+    // static: the generic lambda `step` below would capture an automatic variable that it names in an
+    // expression depending on its parameter, and one more capture reorders the instances' code
+    static constexpr bool AFFINE = (F & kWaveAffine) != 0, TRACE = (F & kWaveTrace) != 0, BAND = (F & kWaveBand) != 0, ENDS = (F & kWaveEnds) != 0,
+                          BAT = (F & kWaveBandAt) != 0, EXT = (F & kWaveExtend) != 0, SEED = (F & kWaveSeed) != 0;
     static_assert(!TRACE || (AFFINE && R == 8), "traced instances: affine, eight rows per lane");
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
     static_assert(!BAND || (AFFINE && (BAT || MODE != SA_FIT)), "banded instances: affine; on the half-width, global or local");
@@ -771,6 +858,22 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         if (lane == 0) a.out[pi] = res;
     }
     if (bad) __hip_atomic_store(&a.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Every instance of the program as a kernel, one wave per workgroup, and the one place that unpacks the
+// kernel argument: a variant's field is read only where its flag is set. sa_score.hip instantiates the
+// untraced instances and sa_affine_walk.hip the traced ones, both through the table of sa_wave_launch.h.
+template <int R, int MODE, bool SMALL, unsigned F>
+__global__ __launch_bounds__(64) void wave_kernel(ArgsOf<F> w)
+{
+    __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
+    constexpr bool BAT = (F & kWaveBandAt) != 0;
+    const int gap_extend = F & kWaveAffine ? w.sa.gap_extend : 0;
+    const int band = (F & kWaveBand) && !BAT ? w.band : 0, ends = F & kWaveEnds ? w.ends : 0, xdrop = F & kWaveExtend ? w.xdrop : SA_NO_XDROP;
+    const Band *const bands = BAT ? w.bands : nullptr;
+    const SeedItem *const items = F & kWaveSeed ? w.items : nullptr;
+    if constexpr ((F & kWaveTrace) != 0) score_wave<R, MODE, SMALL, F>(w.sa.s, gap_extend, tab, w.tr, band, ends, bands, xdrop, items);
+    else score_wave<R, MODE, SMALL, F>(w.sa.s, gap_extend, tab, TraceArgs(), band, ends, bands, xdrop, items);
 }
 
 }  // namespace sa

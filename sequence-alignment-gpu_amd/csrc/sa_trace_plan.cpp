@@ -18,9 +18,19 @@ uint64_t trace_arena_budget()
     return b;
 }
 
-int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
-                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err, const int32_t *band,
-                    const sa_band *bands, const int32_t *xdrop)
+// the limits and the work order are the affine scorer's; the traced instances exist at R = 8 only.
+// SA_SCORE_WAVES is tuned for the untraced kernels: here it may lower the grid, not raise it past what the
+// traced instances' registers admit
+static ScoreKnobs traced_knobs(const ScoreKnobs &kn)
+{
+    ScoreKnobs k8 = kn;
+    k8.rows_per_lane = kTraceRows;
+    k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
+    return k8;
+}
+
+int make_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                    uint64_t budget, TracePlan *out, std::string *err)
 {
     if (!out)
     {
@@ -29,15 +39,9 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
     }
     TracePlan &pl = *out;
     pl = TracePlan();
-    // the limits and the work order are the affine scorer's; the traced instances exist at R = 8 only
-    const ScoreGap gapm = {gap_open, gap_extend};
-    ScoreKnobs k8 = kn;
-    k8.rows_per_lane = kTraceRows;
-    // SA_SCORE_WAVES is tuned for the untraced kernels: here it may lower the grid, not raise it past
-    // what the traced instances' registers admit
-    k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
-    const ScoreExtend ext = {xdrop ? *xdrop : SA_NO_XDROP, true};
-    if (int rc = make_score_plan(P, pairs, np, num_cu, k8, &pl.score, err, &gapm, band, bands, xdrop ? &ext : nullptr)) return rc;
+    WaveSpec traced = spec;
+    traced.traced = true;
+    if (int rc = make_score_plan(P, traced, pairs, np, num_cu, traced_knobs(kn), &pl.score, err)) return rc;
     pl.budget = budget;
     pl.dir_bytes.resize((size_t)np);
     pl.dir_off.resize((size_t)np);
@@ -45,9 +49,9 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
     for (int64_t p = 0; p < np; ++p)
     {
         const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
-        pl.dir_bytes[p] = bands  ? trace_band_at_dir_bytes(n, m, pl.score.bands[p])
-                          : band ? trace_band_dir_bytes(n, m, *band)
-                                 : trace_dir_bytes(n, m);
+        pl.dir_bytes[p] = spec.band_at  ? trace_band_at_dir_bytes(n, m, pl.score.bands[p])
+                          : spec.banded ? trace_band_dir_bytes(n, m, spec.band)
+                                        : trace_dir_bytes(n, m);
         pl.total_dir_bytes += pl.dir_bytes[p];
         pl.slot_off[p] = pl.string_bytes;
         pl.string_bytes += n + m;
@@ -77,9 +81,8 @@ int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, co
     return SA_OK;
 }
 
-int make_seeds_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_pair *pairs,
-                          const sa_seed *seeds, int64_t np, int num_cu, const ScoreKnobs &kn, uint64_t budget,
-                          SeedTracePlan *out, std::string *err)
+int make_seeds_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
+                          const ScoreKnobs &kn, uint64_t budget, SeedTracePlan *out, std::string *err)
 {
     if (!out)
     {
@@ -88,12 +91,9 @@ int make_seeds_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_exte
     }
     SeedTracePlan &pl = *out;
     pl = SeedTracePlan();
-    const ScoreGap gapm = {gap_open, gap_extend};
-    ScoreKnobs k8 = kn;
-    k8.rows_per_lane = kTraceRows;
-    k8.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, kTraceWavesPerSimd) : kTraceWavesPerSimd;
-    const ScoreExtend ext = {xdrop, true};
-    if (int rc = make_seeds_score_plan(P, pairs, seeds, np, num_cu, k8, &pl.score, &pl.seeds, err, &gapm, &ext)) return rc;
+    WaveSpec traced = spec;
+    traced.traced = true;
+    if (int rc = make_seeds_score_plan(P, traced, pairs, seeds, np, num_cu, traced_knobs(kn), &pl.score, &pl.seeds, err)) return rc;
     pl.budget = budget;
     pl.num_pairs = np;
     const std::vector<SeedItem> &items = pl.seeds.items;

@@ -84,17 +84,17 @@ struct TracePlan {
     int64_t num_chunks() const { return (int64_t)chunk_begin.size() - 1; }
 };
 
-// Plans `np` pairs. Returns SA_OK, or the SA_ERR_* code with its message in *err: make_score_plan's
-// for the affine gap model, or SA_ERR_UNSUPPORTED for a pair whose directions exceed `budget`.
-// `band` non-null: the banded aligner; a pair's directions are its band's (trace_band_dir_bytes), the
-// chunks are cut by them, and a pair is refused only when its band exceeds the budget.
-// `bands` non-null (and `band` null): the band-at aligner, bands[p] the band of pair p
-// (make_score_plan's checks; trace_band_at_dir_bytes of the clipped band).
-// `xdrop` non-null: the extension aligner (sa_hip.h sa_align_pairs_extend; make_score_plan's checks). A pair
-// is planned with the directions of a global pair: where its fill stops is not known beforehand.
-int make_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_pair *pairs, int64_t np,
-                    int num_cu, const ScoreKnobs &kn, uint64_t budget, TracePlan *out, std::string *err,
-                    const int32_t *band = nullptr, const sa_band *bands = nullptr, const int32_t *xdrop = nullptr);
+// Plans `np` pairs for `spec`, the call's WaveSpec with its gap model (the planner sets `traced`). Returns
+// SA_OK, or the SA_ERR_* code with its message in *err: make_score_plan's for the spec, or
+// SA_ERR_UNSUPPORTED for a pair whose directions exceed `budget`.
+//  - banded: the banded aligner; a pair's directions are its band's (trace_band_dir_bytes), the chunks are
+//    cut by them, and a pair is refused only when its band exceeds the budget.
+//  - band_at: the band-at aligner, bands[p] the band of pair p (make_score_plan's checks;
+//    trace_band_at_dir_bytes of the clipped band).
+//  - extend: the extension aligner (sa_hip.h sa_align_pairs_extend; make_score_plan's checks). A pair is
+//    planned with the directions of a global pair: where its fill stops is not known beforehand.
+int make_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                    uint64_t budget, TracePlan *out, std::string *err);
 
 // The seeds aligner (sa_hip.h sa_align_pairs_seeds): the traced fill draws work items (SeedItems), the walk
 // pairs. dir_bytes and dir_off are per item, each half traced as a global pair of its shape, ps x ts and
@@ -109,8 +109,7 @@ struct SeedTracePlan : TracePlan {
     std::vector<int64_t> pair_chunk_begin;
     int64_t num_pairs = 0;
 };
-int make_seeds_trace_plan(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_pair *pairs,
-                          const sa_seed *seeds, int64_t np, int num_cu, const ScoreKnobs &kn, uint64_t budget,
-                          SeedTracePlan *out, std::string *err);
+int make_seeds_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
+                          const ScoreKnobs &kn, uint64_t budget, SeedTracePlan *out, std::string *err);
 
 }  // namespace sa

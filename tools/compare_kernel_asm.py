@@ -5,9 +5,15 @@ registers, LDS, scratch) in the second. Basic-block labels carry the function's 
 shifts when instances are added, so the index is dropped from them; comments and debug directives are
 ignored. Prints one line per kernel and a summary; exit status 0 iff every kernel of the first listing is
 in the second with identical text.
-    compare_kernel_asm.py parent.s new.s [--markdown]
+    compare_kernel_asm.py parent.s new.s [--markdown] [--map FILE]
 With --markdown the per-kernel lines are a table, and the kernels only the second listing has are listed
-with their VGPR, SGPR and scratch figures."""
+with their VGPR, SGPR and scratch figures.
+With --map FILE a kernel of the first listing is looked up in the second under another name: the file has
+lines `old_mangled_name new_mangled_name` (a kernel without a line keeps its name). Every mapped kernel's own
+name inside its text is rewritten before the comparison, two old names must not share a new one, and a kernel
+of the second listing that no kernel of the first accounts for fails the comparison. Under a map the kernels
+take other argument structs, so .amdhsa_kernarg_size is left out of the descriptor comparison, and nothing
+else is."""
 from __future__ import annotations
 
 import re
@@ -23,7 +29,7 @@ def kernels(path):
         s = line.split(";")[0].strip()
         if not s:
             continue
-        m = re.match(r"^(_Z\w+):", s)
+        m = re.match(r"^(_Z[\w$.]+):", s)
         if m and name is None:
             name, body = m.group(1), []
             continue
@@ -52,10 +58,33 @@ def figure(desc, key):
     return "?"
 
 
+def read_map(path):
+    """{old name: new name} of a map file; a new name taken twice is an error."""
+    names = {}
+    for line in open(path):
+        if line.strip() and not line.startswith("#"):
+            old, new = line.split()
+            names[old] = new
+    if len(set(names.values())) != len(names):
+        sys.exit(f"{path}: two kernels map to one name")
+    return names
+
+
 def main(argv):
     md = "--markdown" in argv
+    names = {}
+    if "--map" in argv:
+        i = argv.index("--map")
+        names = read_map(argv[i + 1])
+        argv = argv[:i] + argv[i + 2:]
     a, b = [x for x in argv if not x.startswith("--")]
     old, new = kernels(a), kernels(b)
+    if names:
+        # a kernel's text names the kernel itself (its kernarg symbol, its end label's size expression)
+        old = {names.get(k, k): ([s.replace(k, names.get(k, k)) for s in v[0]], v[1]) for k, v in old.items()}
+        drop = lambda desc: [d for d in desc if not d.startswith(".amdhsa_kernarg_size ")]  # noqa: E731
+        old = {k: (v[0], drop(v[1])) for k, v in old.items()}
+        new = {k: (v[0], drop(v[1])) for k, v in new.items()}
     bad = 0
     if md:
         print("| kernel | instructions | same text | same descriptor |\n|---|---|---|---|")
@@ -78,7 +107,7 @@ def main(argv):
         print(f"| `{name}` | {row[0]} | {row[1]} | {row[2]} | {row[3]} |" if md else f"new {name}: {row}")
     print(f"\n{len(old)} kernels in the first listing, {len(old) - bad} identical in the second, {bad} different or missing, "
           f"{len(added)} new")
-    return 1 if bad else 0
+    return 1 if bad or (names and added) else 0
 
 
 if __name__ == "__main__":
