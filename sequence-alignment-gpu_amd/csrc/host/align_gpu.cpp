@@ -53,6 +53,41 @@ bool endsFlagsOk(int freeEnds, const char *name)
     return false;
 }
 
+// Fresh Response buffers for a request (the callee allocates); what a Response held before is released
+bool allocResponse(const SequenceAlignment::Request &rq, SequenceAlignment::Response &rs)
+{
+    const uint64_t cap = std::max<uint64_t>(1, std::max(2 * rq.textNumBytes, rq.textNumBytes + rq.patternNumBytes));
+    delete[] rs.alignedTextBytes;
+    delete[] rs.alignedPatternBytes;
+    rs.alignedTextBytes = rs.alignedPatternBytes = nullptr;
+    try
+    {
+        rs.alignedTextBytes = new char[cap];
+        rs.alignedPatternBytes = new char[cap];
+    }
+    catch (const std::bad_alloc &)
+    {
+        std::cout << SequenceAlignment::MEM_ERROR;
+        return false;
+    }
+    return true;
+}
+
+// a failed C ABI call: its message on stdout (a failed allocation as MEM_ERROR), and the 1 the caller returns
+uint64_t reportFailure(int rc, bool memError = true)
+{
+    std::cout << (rc == SA_ERR_NOMEM && memError ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
+    return 1;
+}
+
+void storeResult(const sa_result &res, SequenceAlignment::Response &rs)
+{
+    rs.score = res.score;
+    rs.numAlignmentBytes = res.num_alignment_bytes;
+    rs.startInAlignedText = res.start_text;
+    rs.startInAlignedPattern = res.start_pattern;
+}
+
 uint64_t runGPU(const SequenceAlignment::Request &request, SequenceAlignment::Response *response, bool fillOnly)
 {
     sa_params params;
@@ -76,31 +111,11 @@ uint64_t runGPU(const SequenceAlignment::Request &request, SequenceAlignment::Re
         }
         return std::max<uint64_t>(1, (uint64_t)(fillMicros + 0.5));
     }
-    delete[] response->alignedTextBytes;
-    delete[] response->alignedPatternBytes;
-    response->alignedTextBytes = nullptr;
-    response->alignedPatternBytes = nullptr;
-    try
-    {
-        response->alignedTextBytes = new char[cap];
-        response->alignedPatternBytes = new char[cap];
-    }
-    catch (const std::bad_alloc &)
-    {
-        std::cout << SequenceAlignment::MEM_ERROR;
-        return 1;
-    }
+    if (!allocResponse(request, *response)) return 1;  // `cap` bytes each
     const int rc = sa_align_pair(&params, request.textBytes, n, request.patternBytes, m, deviceFromEnv(), &result,
                                  response->alignedTextBytes, response->alignedPatternBytes, cap, nullptr);
-    if (rc != SA_OK)
-    {
-        std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
-        return 1;
-    }
-    response->score = result.score;
-    response->numAlignmentBytes = result.num_alignment_bytes;
-    response->startInAlignedText = result.start_text;
-    response->startInAlignedPattern = result.start_pattern;
+    if (rc != SA_OK) return reportFailure(rc);
+    storeResult(result, *response);
     return 0;
 }
 
@@ -111,33 +126,6 @@ bool sameScheme(const sa_params &a, const sa_params &b)
            std::memcmp(a.score_matrix, b.score_matrix, sizeof(int) * a.alphabet_size * a.alphabet_size) == 0;
 }
 
-// Fresh Response buffers for a request of a batch call (the callee allocates, as alignSequenceGPU does)
-bool allocResponse(const SequenceAlignment::Request &rq, SequenceAlignment::Response &rs)
-{
-    const uint64_t cap = std::max<uint64_t>(1, std::max(2 * rq.textNumBytes, rq.textNumBytes + rq.patternNumBytes));
-    delete[] rs.alignedTextBytes;
-    delete[] rs.alignedPatternBytes;
-    rs.alignedTextBytes = rs.alignedPatternBytes = nullptr;
-    try
-    {
-        rs.alignedTextBytes = new char[cap];
-        rs.alignedPatternBytes = new char[cap];
-    }
-    catch (const std::bad_alloc &)
-    {
-        std::cout << SequenceAlignment::MEM_ERROR;
-        return false;
-    }
-    return true;
-}
-
-void storeResult(const sa_result &res, SequenceAlignment::Response &rs)
-{
-    rs.score = res.score;
-    rs.numAlignmentBytes = res.num_alignment_bytes;
-    rs.startInAlignedText = res.start_text;
-    rs.startInAlignedPattern = res.start_pattern;
-}
 }  // namespace
 
 uint64_t SequenceAlignment::alignSequenceGPUBatch(const Request *requests, Response *responses, uint64_t numRequests,
@@ -172,11 +160,7 @@ uint64_t SequenceAlignment::alignSequenceGPUBatch(const Request *requests, Respo
         }
         const int rc = sa_align_batch(&params[lead], pairs.data(), (int64_t)pairs.size(), std::max(1, numGpus),
                                       res.data(), at.data(), ap.data());
-        if (rc != SA_OK)
-        {
-            std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
-            return 1;
-        }
+        if (rc != SA_OK) return reportFailure(rc);
         for (size_t q = 0; q < group.size(); ++q)
         {
             storeResult(res[q], responses[group[q]]);
@@ -198,73 +182,103 @@ uint64_t SequenceAlignment::alignSequenceGPUFillMicros(const Request &request, R
 
 namespace
 {
-// scoreSequencesGPU, scoreSequencesGPUAffine and scoreSequencesGPUBanded: `gap` null is the requests'
-// linear gapPenalty, else {gap open, gap extend} and gapPenalty is ignored; `band` non-null is the
-// band's half-width; `ends` non-null is scoreSequencesGPUEndsFree with these flags; `lo` and `hi` non-null
-// are scoreSequencesGPUBandAt's per-request bands; `xdrop` non-null is scoreSequencesGPUExtend (the mode is
-// SA_GLOBAL, whose borders an extension has, and Request::alignmentType is ignored); `seeds` non-null (with
-// `xdrop`) is scoreSequencesGPUSeeds
-uint64_t scoreRequests(const SequenceAlignment::Request *requests, uint64_t numRequests, int device, const int *gap,
-                       int *scores, const char *name, const int *band = nullptr, const int *ends = nullptr,
-                       const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr,
-                       const std::vector<sa_seed> *seeds = nullptr)
+using SequenceAlignment::Request;
+using SequenceAlignment::Response;
+
+// What one of the batch functions below asks for, as a value; a null pointer is "not asked for".
+struct Variant {
+    const char *name;                 // the public function, for the messages
+    bool affine;                      // gap open and gap extend, and Request::gapPenalty is ignored; else the linear gapPenalty
+    int gapOpen, gapExtend;
+    const int *band = nullptr;        // the band's half-width
+    const int *ends = nullptr;        // the SA_FREE_* flags: the mode is SA_ENDS_FREE with them, Request::alignmentType is ignored
+    const int *lo = nullptr, *hi = nullptr;       // the per-request bands of the ...BandAt functions
+    const int *xdrop = nullptr;       // extension: the mode is SA_GLOBAL, whose borders an extension has, whatever alignmentType says
+    const std::vector<sa_seed> *seeds = nullptr;  // with xdrop: the ...Seeds functions
+    explicit Variant(const char *n) : name(n), affine(false), gapOpen(0), gapExtend(0) {}
+    Variant(const char *n, int open, int extend) : name(n), affine(true), gapOpen(open), gapExtend(extend) {}
+};
+
+// The requests of a call as the C ABI takes them. With `responses` (the aligners), each request's Response
+// gets its fresh buffers as soon as the request has passed, and at / ap point at them.
+struct Packed {
+    std::vector<sa_params> params;  // one scheme: params[0] is the call's
+    std::vector<sa_host_pair> pairs;
+    std::vector<sa_band> bands;
+    std::vector<char *> at, ap;
+};
+bool pack(const Variant &v, const Request *requests, Response *responses, uint64_t numRequests, Packed *k)
 {
-    if (numRequests == 0) return 0;
-    std::vector<sa_params> params(numRequests);
-    std::vector<sa_host_pair> pairs(numRequests);
+    k->params.resize(numRequests);
+    k->pairs.resize(numRequests);
     for (uint64_t i = 0; i < numRequests; ++i)
     {
         const int none = 0;
-        if (!toParams(requests[i], &params[i], true, xdrop ? &none : ends))
+        if (!toParams(requests[i], &k->params[i], true, v.xdrop ? &none : v.ends))
         {
-            std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
-            return 1;
+            std::cout << "error: " << v.name << " takes global, local and semi-global alignments\n";
+            return false;
         }
-        if (xdrop) params[i].mode = SA_GLOBAL;
-        if (gap) params[i].gap_penalty = 0;
-        if (!sameScheme(params[0], params[i]))
+        if (v.xdrop) k->params[i].mode = SA_GLOBAL;
+        if (v.affine) k->params[i].gap_penalty = 0;
+        if (!sameScheme(k->params[0], k->params[i]))
         {
-            std::cout << "error: " << name << " needs one scoring scheme for all requests\n";
-            return 1;
+            std::cout << "error: " << v.name << " needs one scoring scheme for all requests\n";
+            return false;
         }
-        pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
-                                requests[i].patternNumBytes};
+        k->pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
+                                   requests[i].patternNumBytes};
+        if (!responses) continue;
+        if (!allocResponse(requests[i], responses[i])) return false;
+        k->at.push_back(responses[i].alignedTextBytes);
+        k->ap.push_back(responses[i].alignedPatternBytes);
     }
+    for (uint64_t i = 0; v.lo && i < numRequests; ++i) k->bands.push_back(sa_band{v.lo[i], v.hi[i]});
+    return true;
+}
+
+// every score...GPU... function
+uint64_t scoreRequests(const Variant &v, const Request *requests, uint64_t numRequests, int device, int *scores)
+{
+    if (numRequests == 0) return 0;
+    Packed k;
+    if (!pack(v, requests, nullptr, numRequests, &k)) return 1;
+    const sa_params *P = &k.params[0];
+    const sa_host_pair *pairs = k.pairs.data();
+    const int64_t n = (int64_t)numRequests;
     std::vector<sa_score_result> res(numRequests);
-    std::vector<sa_band> bands;
-    for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
-    if (seeds)
-    {
-        std::vector<sa_seed_result> sres(numRequests);
-        if (sa_score_batch_seeds(&params[0], gap[0], gap[1], *xdrop, seeds->data(), pairs.data(), (int64_t)numRequests, device, sres.data()) != SA_OK)
-        {
-            std::cout << "error: " + std::string(sa_last_error()) + "\n";
-            return 1;
-        }
-        for (uint64_t i = 0; i < numRequests; ++i) scores[i] = sres[i].score;
-        return 0;
-    }
-    const int rc = xdrop ? sa_score_batch_extend(&params[0], gap[0], gap[1], *xdrop, pairs.data(), (int64_t)numRequests, device, res.data())
-                   : lo ? sa_score_batch_band_at(&params[0], gap[0], gap[1], bands.data(), pairs.data(), (int64_t)numRequests, device, res.data())
-                   : band ? sa_score_batch_banded(&params[0], gap[0], gap[1], *band, pairs.data(), (int64_t)numRequests, device, res.data())
-                   : gap ? sa_score_batch_affine(&params[0], gap[0], gap[1], pairs.data(), (int64_t)numRequests, device, res.data())
-                         : sa_score_batch(&params[0], pairs.data(), (int64_t)numRequests, device, res.data());
-    if (rc != SA_OK)
-    {
-        std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
-        return 1;
-    }
-    for (uint64_t i = 0; i < numRequests; ++i) scores[i] = res[i].score;
+    std::vector<sa_seed_result> sres(v.seeds ? numRequests : 0);
+    const int rc = v.seeds    ? sa_score_batch_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, sres.data())
+                   : v.xdrop  ? sa_score_batch_extend(P, v.gapOpen, v.gapExtend, *v.xdrop, pairs, n, device, res.data())
+                   : v.lo     ? sa_score_batch_band_at(P, v.gapOpen, v.gapExtend, k.bands.data(), pairs, n, device, res.data())
+                   : v.band   ? sa_score_batch_banded(P, v.gapOpen, v.gapExtend, *v.band, pairs, n, device, res.data())
+                   : v.affine ? sa_score_batch_affine(P, v.gapOpen, v.gapExtend, pairs, n, device, res.data())
+                              : sa_score_batch(P, pairs, n, device, res.data());
+    if (rc != SA_OK) return reportFailure(rc, !v.seeds);  // scoreSequencesGPUSeeds has never said MEM_ERROR
+    for (uint64_t i = 0; i < numRequests; ++i) scores[i] = v.seeds ? sres[i].score : res[i].score;
     return 0;
 }
 
-// alignSequencesGPUAffine and, with `band`, alignSequencesGPUBanded; with `ends`, alignSequencesGPUEndsFree;
-// with `lo` and `hi`, alignSequencesGPUBandAt; with `xdrop`, alignSequencesGPUExtend; with `seeds` too,
-// alignSequencesGPUSeeds
-uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
-                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name,
-                       const int *ends = nullptr, const int *lo = nullptr, const int *hi = nullptr, const int *xdrop = nullptr,
-                       const std::vector<sa_seed> *seeds = nullptr);
+// every align...GPU... function that takes a gap model
+uint64_t alignRequests(const Variant &v, const Request *requests, Response *responses, uint64_t numRequests, int device)
+{
+    if (numRequests == 0) return 0;
+    Packed k;
+    if (!pack(v, requests, responses, numRequests, &k)) return 1;
+    const sa_params *P = &k.params[0];
+    const sa_host_pair *pairs = k.pairs.data();
+    const int64_t n = (int64_t)numRequests;
+    std::vector<sa_result> res(numRequests);
+    char **at = k.at.data(), **ap = k.ap.data();
+    const int rc = v.seeds   ? sa_align_pairs_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, res.data(), at, ap)
+                   : v.xdrop ? sa_align_pairs_extend(P, v.gapOpen, v.gapExtend, *v.xdrop, pairs, n, device, res.data(), at, ap)
+                   : v.lo    ? sa_align_pairs_band_at(P, v.gapOpen, v.gapExtend, k.bands.data(), pairs, n, device, res.data(), at, ap)
+                   : v.band  ? sa_align_pairs_banded(P, v.gapOpen, v.gapExtend, *v.band, pairs, n, device, res.data(), at, ap)
+                             : sa_align_pairs_affine(P, v.gapOpen, v.gapExtend, pairs, n, device, res.data(), at, ap);
+    if (rc != SA_OK) return reportFailure(rc);
+    for (uint64_t i = 0; i < numRequests; ++i) storeResult(res[i], responses[i]);
+    return 0;
+}
 
 // the seeds of the ...Seeds functions: three arrays, one entry per request
 bool seedsOk(const uint64_t *textPos, const uint64_t *patternPos, const uint64_t *length, uint64_t numRequests, const char *name,
@@ -291,35 +305,93 @@ bool bandAtArgsOk(int freeEnds, const int *lo, const int *hi, uint64_t numReques
 }
 }  // namespace
 
+uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
+{
+    return scoreRequests(Variant("scoreSequencesGPU"), requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUAffine(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                    int gapExtend, int *scores)
+{
+    return scoreRequests(Variant("scoreSequencesGPUAffine", gapOpen, gapExtend), requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Response *responses, uint64_t numRequests,
+                                                    int device, int gapOpen, int gapExtend)
+{
+    return alignRequests(Variant("alignSequencesGPUAffine", gapOpen, gapExtend), requests, responses, numRequests, device);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUBanded(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                    int gapExtend, int band, int *scores)
+{
+    Variant v("scoreSequencesGPUBanded", gapOpen, gapExtend);
+    v.band = &band;
+    return scoreRequests(v, requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUBanded(const Request *requests, Response *responses, uint64_t numRequests,
+                                                    int device, int gapOpen, int gapExtend, int band)
+{
+    Variant v("alignSequencesGPUBanded", gapOpen, gapExtend);
+    v.band = &band;
+    return alignRequests(v, requests, responses, numRequests, device);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUEndsFree(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                      int gapExtend, int freeEnds, int *scores)
+{
+    if (!endsFlagsOk(freeEnds, "scoreSequencesGPUEndsFree")) return 1;
+    Variant v("scoreSequencesGPUEndsFree", gapOpen, gapExtend);
+    v.ends = &freeEnds;
+    return scoreRequests(v, requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUEndsFree(const Request *requests, Response *responses, uint64_t numRequests,
+                                                      int device, int gapOpen, int gapExtend, int freeEnds)
+{
+    if (!endsFlagsOk(freeEnds, "alignSequencesGPUEndsFree")) return 1;
+    Variant v("alignSequencesGPUEndsFree", gapOpen, gapExtend);
+    v.ends = &freeEnds;
+    return alignRequests(v, requests, responses, numRequests, device);
+}
+
 uint64_t SequenceAlignment::scoreSequencesGPUBandAt(const Request *requests, uint64_t numRequests, int device, int gapOpen,
                                                     int gapExtend, int freeEnds, const int *bandLo, const int *bandHi, int *scores)
 {
     if (!bandAtArgsOk(freeEnds, bandLo, bandHi, numRequests, "scoreSequencesGPUBandAt")) return 1;
-    const int gap[2] = {gapOpen, gapExtend};
-    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUBandAt", nullptr,
-                         freeEnds < 0 ? nullptr : &freeEnds, bandLo, bandHi);
+    Variant v("scoreSequencesGPUBandAt", gapOpen, gapExtend);
+    v.ends = freeEnds < 0 ? nullptr : &freeEnds;
+    v.lo = bandLo;
+    v.hi = bandHi;
+    return scoreRequests(v, requests, numRequests, device, scores);
 }
 
 uint64_t SequenceAlignment::alignSequencesGPUBandAt(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                                     int gapOpen, int gapExtend, int freeEnds, const int *bandLo, const int *bandHi)
 {
     if (!bandAtArgsOk(freeEnds, bandLo, bandHi, numRequests, "alignSequencesGPUBandAt")) return 1;
-    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUBandAt",
-                         freeEnds < 0 ? nullptr : &freeEnds, bandLo, bandHi);
+    Variant v("alignSequencesGPUBandAt", gapOpen, gapExtend);
+    v.ends = freeEnds < 0 ? nullptr : &freeEnds;
+    v.lo = bandLo;
+    v.hi = bandHi;
+    return alignRequests(v, requests, responses, numRequests, device);
 }
 
 uint64_t SequenceAlignment::scoreSequencesGPUExtend(const Request *requests, uint64_t numRequests, int device, int gapOpen,
                                                     int gapExtend, int xdrop, int *scores)
 {
-    const int gap[2] = {gapOpen, gapExtend};
-    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUExtend", nullptr, nullptr, nullptr, nullptr, &xdrop);
+    Variant v("scoreSequencesGPUExtend", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    return scoreRequests(v, requests, numRequests, device, scores);
 }
 
 uint64_t SequenceAlignment::alignSequencesGPUExtend(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                                     int gapOpen, int gapExtend, int xdrop)
 {
-    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUExtend", nullptr, nullptr,
-                         nullptr, &xdrop);
+    Variant v("alignSequencesGPUExtend", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    return alignRequests(v, requests, responses, numRequests, device);
 }
 
 uint64_t SequenceAlignment::scoreSequencesGPUSeeds(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
@@ -328,9 +400,10 @@ uint64_t SequenceAlignment::scoreSequencesGPUSeeds(const Request *requests, uint
 {
     std::vector<sa_seed> seeds;
     if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "scoreSequencesGPUSeeds", &seeds)) return 1;
-    const int gap[2] = {gapOpen, gapExtend};
-    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUSeeds", nullptr, nullptr, nullptr, nullptr, &xdrop,
-                         &seeds);
+    Variant v("scoreSequencesGPUSeeds", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.seeds = &seeds;
+    return scoreRequests(v, requests, numRequests, device, scores);
 }
 
 uint64_t SequenceAlignment::alignSequencesGPUSeeds(const Request *requests, Response *responses, uint64_t numRequests, int device,
@@ -339,106 +412,8 @@ uint64_t SequenceAlignment::alignSequencesGPUSeeds(const Request *requests, Resp
 {
     std::vector<sa_seed> seeds;
     if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "alignSequencesGPUSeeds", &seeds)) return 1;
-    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUSeeds", nullptr, nullptr,
-                         nullptr, &xdrop, &seeds);
+    Variant v("alignSequencesGPUSeeds", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.seeds = &seeds;
+    return alignRequests(v, requests, responses, numRequests, device);
 }
-
-uint64_t SequenceAlignment::scoreSequencesGPU(const Request *requests, uint64_t numRequests, int device, int *scores)
-{
-    return scoreRequests(requests, numRequests, device, nullptr, scores, "scoreSequencesGPU");
-}
-
-uint64_t SequenceAlignment::scoreSequencesGPUAffine(const Request *requests, uint64_t numRequests, int device, int gapOpen,
-                                                    int gapExtend, int *scores)
-{
-    const int gap[2] = {gapOpen, gapExtend};
-    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUAffine");
-}
-
-uint64_t SequenceAlignment::scoreSequencesGPUBanded(const Request *requests, uint64_t numRequests, int device, int gapOpen,
-                                                    int gapExtend, int band, int *scores)
-{
-    const int gap[2] = {gapOpen, gapExtend};
-    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUBanded", &band);
-}
-
-uint64_t SequenceAlignment::alignSequencesGPUAffine(const Request *requests, Response *responses, uint64_t numRequests,
-                                                    int device, int gapOpen, int gapExtend)
-{
-    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUAffine");
-}
-
-uint64_t SequenceAlignment::alignSequencesGPUBanded(const Request *requests, Response *responses, uint64_t numRequests,
-                                                    int device, int gapOpen, int gapExtend, int band)
-{
-    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, &band, "alignSequencesGPUBanded");
-}
-
-uint64_t SequenceAlignment::scoreSequencesGPUEndsFree(const Request *requests, uint64_t numRequests, int device, int gapOpen,
-                                                      int gapExtend, int freeEnds, int *scores)
-{
-    if (!endsFlagsOk(freeEnds, "scoreSequencesGPUEndsFree")) return 1;
-    const int gap[2] = {gapOpen, gapExtend};
-    return scoreRequests(requests, numRequests, device, gap, scores, "scoreSequencesGPUEndsFree", nullptr, &freeEnds);
-}
-
-uint64_t SequenceAlignment::alignSequencesGPUEndsFree(const Request *requests, Response *responses, uint64_t numRequests,
-                                                      int device, int gapOpen, int gapExtend, int freeEnds)
-{
-    if (!endsFlagsOk(freeEnds, "alignSequencesGPUEndsFree")) return 1;
-    return alignRequests(requests, responses, numRequests, device, gapOpen, gapExtend, nullptr, "alignSequencesGPUEndsFree", &freeEnds);
-}
-
-namespace
-{
-uint64_t alignRequests(const SequenceAlignment::Request *requests, SequenceAlignment::Response *responses, uint64_t numRequests,
-                       int device, int gapOpen, int gapExtend, const int *band, const std::string &name, const int *ends,
-                       const int *lo, const int *hi, const int *xdrop, const std::vector<sa_seed> *seeds)
-{
-    if (numRequests == 0) return 0;
-    std::vector<sa_params> params(numRequests);
-    std::vector<sa_host_pair> pairs(numRequests);
-    std::vector<char *> at(numRequests), ap(numRequests);
-    for (uint64_t i = 0; i < numRequests; ++i)
-    {
-        const int none = 0;
-        if (!toParams(requests[i], &params[i], true, xdrop ? &none : ends))
-        {
-            std::cout << "error: " << name << " takes global, local and semi-global alignments\n";
-            return 1;
-        }
-        if (xdrop) params[i].mode = SA_GLOBAL;
-        params[i].gap_penalty = 0;
-        if (!sameScheme(params[0], params[i]))
-        {
-            std::cout << "error: " << name << " needs one scoring scheme for all requests\n";
-            return 1;
-        }
-        pairs[i] = sa_host_pair{requests[i].textBytes, requests[i].textNumBytes, requests[i].patternBytes,
-                                requests[i].patternNumBytes};
-        if (!allocResponse(requests[i], responses[i])) return 1;
-        at[i] = responses[i].alignedTextBytes;
-        ap[i] = responses[i].alignedPatternBytes;
-    }
-    std::vector<sa_result> res(numRequests);
-    std::vector<sa_band> bands;
-    for (uint64_t i = 0; lo && i < numRequests; ++i) bands.push_back(sa_band{lo[i], hi[i]});
-    const int rc = seeds ? sa_align_pairs_seeds(&params[0], gapOpen, gapExtend, *xdrop, seeds->data(), pairs.data(), (int64_t)numRequests,
-                                                device, res.data(), at.data(), ap.data())
-                   : xdrop ? sa_align_pairs_extend(&params[0], gapOpen, gapExtend, *xdrop, pairs.data(), (int64_t)numRequests, device,
-                                                 res.data(), at.data(), ap.data())
-                   : lo ? sa_align_pairs_band_at(&params[0], gapOpen, gapExtend, bands.data(), pairs.data(), (int64_t)numRequests, device,
-                                                 res.data(), at.data(), ap.data())
-                   : band ? sa_align_pairs_banded(&params[0], gapOpen, gapExtend, *band, pairs.data(), (int64_t)numRequests, device,
-                                                res.data(), at.data(), ap.data())
-                        : sa_align_pairs_affine(&params[0], gapOpen, gapExtend, pairs.data(), (int64_t)numRequests, device,
-                                                res.data(), at.data(), ap.data());
-    if (rc != SA_OK)
-    {
-        std::cout << (rc == SA_ERR_NOMEM ? SequenceAlignment::MEM_ERROR : "error: " + std::string(sa_last_error()) + "\n");
-        return 1;
-    }
-    for (uint64_t i = 0; i < numRequests; ++i) storeResult(res[i], responses[i]);
-    return 0;
-}
-}  // namespace

@@ -14,7 +14,7 @@ namespace sa {
 // aligned_pattern: both null, or np host buffers of at least text_len + pattern_len bytes each.
 // `spec` banded: inside the diagonal band of that half-width (sa_align_pairs_banded); band_at: inside
 // bands[p] for pair p (sa_align_pairs_band_at; null bands with pairs is SA_ERR_INVALID); extend: extension
-// alignment under that X-drop (sa_align_pairs_extend).
+// alignment under that X-drop (sa_align_pairs_extend); seeded: align_seeds_device below.
 int align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
                         const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
 
@@ -35,9 +35,8 @@ struct SeedsCombineArgs {
 void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream);
 
 // sa_align_pairs_seeds on device arenas: the traced fill of the work items, the combine and the seeded walk,
-// chunk by chunk (sa_trace_plan.h SeedTracePlan); arguments as align_affine_device.
-int align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device,
-                       const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
-                       char *const *aligned_pattern);
+// chunk by chunk (sa_trace_plan.h SeedTracePlan); arguments as align_affine_device, the seeds are spec.seeds.
+int align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                       const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
 
 }  // namespace sa

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -395,127 +396,108 @@ struct Workspace {
         bufs.push_back(*p);
         return SA_OK;
     }
+    // a buffer of the size of `h`, holding it
+    template <typename T>
+    int upload(T **p, const std::vector<T> &h)
+    {
+        if (int rc = alloc(p, h.size() * sizeof(T))) return rc;
+        if (!h.empty()) HIP_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+        return SA_OK;
+    }
 };
 
-}  // namespace
+// What an aligner is called with, and its words for the messages
+struct TracedCall {
+    const char *who, *walk, *moves;  // "<who>: null argument", "<walk> of pair 3 did not end within <moves>"
+    const sa_params *P;
+    const sa_pair *pairs;
+    int64_t np;
+    int device;
+    const void *d_text, *d_pattern;
+    sa_result *results;
+    char *const *aligned_text, *const *aligned_pattern;
+};
 
-int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+// The device side of one traced run. The driver owns what every aligner has; the aligner's setup adds its
+// descriptors through `ws` and says what a chunk launches.
+struct TracedRun {
+    Workspace ws;
+    hipStream_t st = nullptr;
+    int A = 0;
+    int32_t *d_table, *d_rows;
+    uint32_t *d_ctrl, *d_dirs;
+    char *d_ot = nullptr, *d_op = nullptr, *d_alpha;  // the string arenas are null for a call without strings
+    sa_result *d_results;
+    // from the setup: chunk c's order slices and traced fill (between the chunk's first two events), then its walk
+    // kernel(s) (before the third); and where the walk leaves each pair's tail length, null when every string is
+    // all tail
+    std::function<int(int64_t)> fill, walk;
+    const uint64_t *d_tail = nullptr;
+};
+
+// The traced run both aligners are: the checks, `plan` (which fills `pl`), the statistics, the common buffers,
+// `setup`, then chunk after chunk a traced fill and a walk that reuses the arena, timed by three events, and the
+// results and strings brought back. A pair's string is a head piece at the start of its slot and a tail piece at
+// the slot's end.
+template <typename PLAN, typename SETUP>
+int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
 {
-    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
-        return fail(SA_ERR_INVALID, "affine aligner: null argument");
-    if (spec.band_at && !spec.bands && np > 0) return fail(SA_ERR_INVALID, "sa_align_pairs_band_at: bands is null");
-    DeviceGuard dg(device);
+    const std::string who = c.who;
+    const int64_t np = c.np;
+    if (!c.P || np < 0 || (np > 0 && (!c.pairs || !c.results)) || ((c.aligned_text == nullptr) != (c.aligned_pattern == nullptr)))
+        return fail(SA_ERR_INVALID, who + ": null argument");
+    DeviceGuard dg(c.device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
-    TracePlan pl;
     std::string err;
-    if (int rc = make_trace_plan(P, spec, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err)) return fail(rc, err);
-    if (!P->alphabet) return fail(SA_ERR_INVALID, "affine aligner: params->alphabet is null");
+    if (int rc = plan(&err)) return fail(rc, err);
+    if (!c.P->alphabet) return fail(SA_ERR_INVALID, who + ": params->alphabet is null");
     g_stats = AffineStats();
     g_stats.arena_bytes = pl.arena_bytes;
     g_stats.chunks = (int32_t)pl.num_chunks();
     if (np == 0) return SA_OK;
-    if ((!d_text || !d_pattern) && pl.score.input_bytes) return fail(SA_ERR_INVALID, "affine aligner: null arena");
-    const int A = pl.score.A;
+    if ((!c.d_text || !c.d_pattern) && pl.score.input_bytes) return fail(SA_ERR_INVALID, who + ": null arena");
 
-    std::vector<ScorePair> hpairs((size_t)np);
-    std::vector<uint64_t> dir_words((size_t)np);
-    for (int64_t p = 0; p < np; ++p)
-    {
-        hpairs[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
-        dir_words[p] = pl.dir_off[p] / 4;
-    }
-    Workspace ws;
-    ScorePair *d_pairs;
-    int32_t *d_order, *d_table, *d_rows;
-    sa_score_result *d_scores;
-    uint32_t *d_ctrl, *d_dirs;
-    uint64_t *d_dir_off, *d_slot_off;
-    char *d_ot = nullptr, *d_op = nullptr, *d_alpha;
-    sa_result *d_results;
-    Band *d_bands = nullptr;
+    TracedRun r;
+    r.A = pl.score.A;
+    const bool strings = c.aligned_text != nullptr;
     int rc;
-    if (spec.band_at)
-    {
-        if ((rc = ws.alloc(&d_bands, (size_t)np * sizeof(Band)))) return rc;
-        HIP_TRY(hipMemcpy(d_bands, pl.score.bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
-    }
-    if ((rc = ws.alloc(&d_pairs, (size_t)np * sizeof(ScorePair))) || (rc = ws.alloc(&d_order, (size_t)np * 4)) ||
-        (rc = ws.alloc(&d_table, 32 * 32 * 4)) || (rc = ws.alloc(&d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) ||
-        (rc = ws.alloc(&d_scores, (size_t)np * sizeof(sa_score_result))) || (rc = ws.alloc(&d_ctrl, 256)) ||
-        (rc = ws.alloc(&d_dirs, pl.arena_bytes)) || (rc = ws.alloc(&d_dir_off, (size_t)np * 8)) ||
-        (rc = ws.alloc(&d_slot_off, (size_t)np * 8)) || (rc = ws.alloc(&d_alpha, 64)) ||
-        (rc = ws.alloc(&d_results, (size_t)np * sizeof(sa_result))))
+    if ((rc = r.ws.alloc(&r.d_table, 32 * 32 * 4)) || (rc = r.ws.alloc(&r.d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) ||
+        (rc = r.ws.alloc(&r.d_ctrl, 256)) || (rc = r.ws.alloc(&r.d_dirs, pl.arena_bytes)) || (rc = r.ws.alloc(&r.d_alpha, 64)) ||
+        (rc = r.ws.alloc(&r.d_results, (size_t)np * sizeof(sa_result))))
         return rc;
-    const bool strings = aligned_text != nullptr;
-    if (strings && ((rc = ws.alloc(&d_ot, pl.string_bytes)) || (rc = ws.alloc(&d_op, pl.string_bytes)))) return rc;
-    HIP_TRY(hipMemcpy(d_pairs, hpairs.data(), (size_t)np * sizeof(ScorePair), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_order, pl.score.order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_dir_off, dir_words.data(), (size_t)np * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_slot_off, pl.slot_off.data(), (size_t)np * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_alpha, P->alphabet, (size_t)A + 1, hipMemcpyHostToDevice));
+    if (strings && ((rc = r.ws.alloc(&r.d_ot, pl.string_bytes)) || (rc = r.ws.alloc(&r.d_op, pl.string_bytes)))) return rc;
+    HIP_TRY(hipMemcpy(r.d_table, c.P->score_matrix, (size_t)r.A * r.A * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.d_alpha, c.P->alphabet, (size_t)r.A + 1, hipMemcpyHostToDevice));
+    if ((rc = setup(r))) return rc;
 
-    hipStream_t st = nullptr;
+    hipStream_t st = r.st;
     const int64_t nchunks = pl.num_chunks();
-    ws.events.reserve((size_t)nchunks * 3);
+    std::vector<hipEvent_t> &ev = r.ws.events;
+    ev.reserve((size_t)nchunks * 3);
     for (int64_t e = 0; e < nchunks * 3; ++e)
     {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        ws.events.push_back(ev);
+        hipEvent_t one;
+        HIP_TRY(hipEventCreate(&one));
+        ev.push_back(one);
     }
-    HIP_TRY(hipMemsetAsync(d_ctrl, 0, 256, st));
-    // the chunks differ in their part of the work order
-    TracedWaveArgs fa = {};
-    fa.sa = score_args(pl.score, d_text, d_pattern, d_pairs, d_order, 0, d_table, d_rows, d_scores, d_ctrl);
-    fa.tr.dirs = d_dirs;
-    fa.tr.dir_off = d_dir_off;
-    fa.bands = d_bands;
-    ScoreArgs &s = fa.sa.s;
-    const WaveChoice choice = wave_choice(pl.score.spec, pl.score.mode);
-    WalkArgs wa;
-    wa.text = s.text;
-    wa.pattern = s.pattern;
-    wa.pairs = d_pairs;
-    wa.scores = d_scores;
-    wa.dirs = d_dirs;
-    wa.dir_off = d_dir_off;
-    wa.slot_off = d_slot_off;
-    wa.out_text = d_ot;
-    wa.out_pattern = d_op;
-    wa.alphabet = d_alpha;
-    wa.results = d_results;
-    wa.A = A;
-    // an extension walks as SA_ENDS_FREE with no flag: from the fill's result cell to the origin
-    wa.mode = spec.extend ? SA_ENDS_FREE : pl.score.mode;
-    wa.band = spec.banded ? spec.band : -1;
-    wa.bands = d_bands;
+    HIP_TRY(hipMemsetAsync(r.d_ctrl, 0, 256, st));
     uint32_t ctrl[2] = {0, 0};
+    std::vector<uint64_t> tail((size_t)np, UINT64_MAX);
     // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
-    // copies into `results` and `ctrl` pending when this function returns
+    // copies into `results`, `ctrl` and `tail` pending when this function returns
     auto enqueue = [&]() -> int {
-        for (int64_t c = 0; c < nchunks; ++c)
+        for (int64_t k = 0; k < nchunks; ++k)
         {
-            // one traced fill and one walk per chunk; the next chunk's fill reuses the arena after the walk
-            const int64_t begin = pl.chunk_begin[c], count = pl.chunk_begin[c + 1] - begin;
-            if (c) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 4, st));  // the work counter; the bad-input flag stays
-            s.order = d_order + begin;
-            s.np = (int32_t)count;
-            wa.order = s.order;
-            HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            if (!launch_wave<true>(choice, kTraceRows, A <= 4, (int)std::min<int64_t>(count, pl.score.grid), st, fa))
-                return fail(SA_ERR_UNSUPPORTED, "affine aligner: the call's variant has no kernel instance");
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
-            if (d_bands) hipLaunchKernelGGL(walk_affine_kernel<2>, dim3((unsigned)count), dim3(64), 0, st, wa);
-            else if (wa.band >= 0) hipLaunchKernelGGL(walk_affine_kernel<1>, dim3((unsigned)count), dim3(64), 0, st, wa);
-            else hipLaunchKernelGGL(walk_affine_kernel<0>, dim3((unsigned)count), dim3(64), 0, st, wa);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ws.events[3 * c + 2], st));
+            if (k) HIP_TRY(hipMemsetAsync(r.d_ctrl, 0, 4, st));  // the work counter; the bad-input flag stays
+            HIP_TRY(hipEventRecord(ev[3 * k], st));
+            if (int rc = r.fill(k)) return rc;
+            HIP_TRY(hipEventRecord(ev[3 * k + 1], st));
+            if (int rc = r.walk(k)) return rc;
+            HIP_TRY(hipEventRecord(ev[3 * k + 2], st));
         }
-        HIP_TRY(hipMemcpyAsync(ctrl, d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(results, d_results, (size_t)np * sizeof(sa_result), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctrl, r.d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c.results, r.d_results, (size_t)np * sizeof(sa_result), hipMemcpyDeviceToHost, st));
+        if (r.d_tail) HIP_TRY(hipMemcpyAsync(tail.data(), r.d_tail, (size_t)np * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return SA_OK;
     };
@@ -524,44 +506,137 @@ int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_p
         (void)hipStreamSynchronize(st);
         return rc;
     }
-    for (int64_t c = 0; c < nchunks; ++c)
+    for (int64_t k = 0; k < nchunks; ++k)
     {
         float f = 0, w = 0;
-        HIP_TRY(hipEventElapsedTime(&f, ws.events[3 * c], ws.events[3 * c + 1]));
-        HIP_TRY(hipEventElapsedTime(&w, ws.events[3 * c + 1], ws.events[3 * c + 2]));
+        HIP_TRY(hipEventElapsedTime(&f, ev[3 * k], ev[3 * k + 1]));
+        HIP_TRY(hipEventElapsedTime(&w, ev[3 * k + 1], ev[3 * k + 2]));
         g_stats.fill_ms += f;
         g_stats.walk_ms += w;
     }
     if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
     for (int64_t p = 0; p < np; ++p)
-        if (results[p].status != SA_OK)
-            return fail(SA_ERR_HIP, "affine walk of pair " + std::to_string(p) + " did not end within text_len + pattern_len moves");
+        if (c.results[p].status != SA_OK)
+            return fail(SA_ERR_HIP, std::string(c.walk) + " of pair " + std::to_string(p) + " did not end within " + c.moves);
     if (strings && pl.string_bytes)
     {
         std::vector<char> ht(pl.string_bytes), hp(pl.string_bytes);
-        HIP_TRY(hipMemcpy(ht.data(), d_ot, pl.string_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hp.data(), d_op, pl.string_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ht.data(), r.d_ot, pl.string_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hp.data(), r.d_op, pl.string_bytes, hipMemcpyDeviceToHost));
         for (int64_t p = 0; p < np; ++p)
         {
-            // written backwards from the end of the slot: the forward string is the slot's tail
-            const uint64_t cap = pairs[p].text_len + pairs[p].pattern_len;
-            const uint64_t L = std::min<uint64_t>(results[p].num_alignment_bytes, cap);
-            if (!L) continue;
-            std::memcpy(aligned_text[p], ht.data() + pl.slot_off[p] + cap - L, L);
-            std::memcpy(aligned_pattern[p], hp.data() + pl.slot_off[p] + cap - L, L);
+            // the head piece (a seeded pair's left half and seed) forwards from the start of the slot; the tail
+            // piece (its right half; of any other pair, the whole string) written backwards from the slot's end
+            const uint64_t cap = c.pairs[p].text_len + c.pairs[p].pattern_len;
+            const uint64_t L = std::min<uint64_t>(c.results[p].num_alignment_bytes, cap), tl = std::min<uint64_t>(tail[p], L), hl = L - tl;
+            if (hl)
+            {
+                std::memcpy(c.aligned_text[p], ht.data() + pl.slot_off[p], hl);
+                std::memcpy(c.aligned_pattern[p], hp.data() + pl.slot_off[p], hl);
+            }
+            if (tl)
+            {
+                std::memcpy(c.aligned_text[p] + hl, ht.data() + pl.slot_off[p] + cap - tl, tl);
+                std::memcpy(c.aligned_pattern[p] + hl, hp.data() + pl.slot_off[p] + cap - tl, tl);
+            }
         }
     }
     return SA_OK;
 }
 
-// every sa_align_pairs_* but the seeds one: the host pairs packed into two arenas, then the device path
+}  // namespace
+
+int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    if (spec.seeded) return align_seeds_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern);
+    TracePlan pl;
+    TracedWaveArgs fa = {};
+    WalkArgs wa;
+    WaveChoice choice = {};
+    int32_t *d_order;
+    auto plan = [&](std::string *err) -> int {
+        if (spec.band_at && !spec.bands && np > 0)
+        {
+            *err = "sa_align_pairs_band_at: bands is null";
+            return SA_ERR_INVALID;
+        }
+        return make_trace_plan(P, spec, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, err);
+    };
+    auto setup = [&](TracedRun &r) -> int {
+        std::vector<ScorePair> hpairs((size_t)np);
+        std::vector<uint64_t> dir_words((size_t)np);
+        for (int64_t p = 0; p < np; ++p)
+        {
+            hpairs[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
+            dir_words[p] = pl.dir_off[p] / 4;
+        }
+        ScorePair *d_pairs;
+        sa_score_result *d_scores;
+        uint64_t *d_dir_off, *d_slot_off;
+        Band *d_bands = nullptr;
+        int rc;
+        if (spec.band_at && (rc = r.ws.upload(&d_bands, pl.score.bands))) return rc;
+        if ((rc = r.ws.upload(&d_pairs, hpairs)) || (rc = r.ws.upload(&d_order, pl.score.order)) ||
+            (rc = r.ws.alloc(&d_scores, (size_t)np * sizeof(sa_score_result))) || (rc = r.ws.upload(&d_dir_off, dir_words)) ||
+            (rc = r.ws.upload(&d_slot_off, pl.slot_off)))
+            return rc;
+        fa.sa = score_args(pl.score, d_text, d_pattern, d_pairs, d_order, 0, r.d_table, r.d_rows, d_scores, r.d_ctrl);
+        fa.tr.dirs = r.d_dirs;
+        fa.tr.dir_off = d_dir_off;
+        fa.bands = d_bands;
+        choice = wave_choice(pl.score.spec, pl.score.mode);
+        wa.text = fa.sa.s.text;
+        wa.pattern = fa.sa.s.pattern;
+        wa.pairs = d_pairs;
+        wa.scores = d_scores;
+        wa.dirs = r.d_dirs;
+        wa.dir_off = d_dir_off;
+        wa.slot_off = d_slot_off;
+        wa.out_text = r.d_ot;
+        wa.out_pattern = r.d_op;
+        wa.alphabet = r.d_alpha;
+        wa.results = r.d_results;
+        wa.A = r.A;
+        // an extension walks as SA_ENDS_FREE with no flag: from the fill's result cell to the origin
+        wa.mode = spec.extend ? SA_ENDS_FREE : pl.score.mode;
+        wa.band = spec.banded ? spec.band : -1;
+        wa.bands = d_bands;
+        // the chunks differ in their part of the work order
+        r.fill = [&](int64_t c) -> int {
+            ScoreArgs &s = fa.sa.s;
+            s.order = d_order + pl.chunk_begin[c];
+            s.np = (int32_t)(pl.chunk_begin[c + 1] - pl.chunk_begin[c]);
+            wa.order = s.order;
+            if (!launch_wave<true>(choice, kTraceRows, r.A <= 4, (int)std::min<int64_t>(s.np, pl.score.grid), r.st, fa))
+                return fail(SA_ERR_UNSUPPORTED, "affine aligner: the call's variant has no kernel instance");
+            HIP_TRY(hipGetLastError());
+            return SA_OK;
+        };
+        r.walk = [&](int64_t) -> int {
+            const dim3 grid((unsigned)fa.sa.s.np);
+            if (wa.bands) hipLaunchKernelGGL(walk_affine_kernel<2>, grid, dim3(64), 0, r.st, wa);
+            else if (wa.band >= 0) hipLaunchKernelGGL(walk_affine_kernel<1>, grid, dim3(64), 0, r.st, wa);
+            else hipLaunchKernelGGL(walk_affine_kernel<0>, grid, dim3(64), 0, r.st, wa);
+            HIP_TRY(hipGetLastError());
+            return SA_OK;
+        };
+        return SA_OK;
+    };
+    return traced_run({"affine aligner", "affine walk", "text_len + pattern_len moves", P, pairs, np, device, d_text, d_pattern, results,
+                       aligned_text, aligned_pattern},
+                      pl, plan, setup);
+}
+
+// every sa_align_pairs_*: the host pairs packed into two arenas, then the device path
 static int align_host_pairs(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
                             char *const *aligned_text, char *const *aligned_pattern)
 {
+    const char *const fn = spec.seeded ? "sa_align_pairs_seeds" : "sa_align_pairs_affine";
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
-        return fail(SA_ERR_INVALID, "sa_align_pairs_affine: null argument");
+        return fail(SA_ERR_INVALID, std::string(fn) + ": null argument");
     HostArenas in;
-    if (int rc = upload_host_pairs("sa_align_pairs_affine", pairs, np, device, &in)) return rc;
+    if (int rc = upload_host_pairs(fn, pairs, np, device, &in)) return rc;
     return align_affine_device(P, spec, in.pairs.data(), np, device, in.text.p, in.pattern.p, results, aligned_text, aligned_pattern);
 }
 
@@ -576,211 +651,30 @@ int sa_align_pairs_affine(const sa_params *P, int32_t gap_open, int32_t gap_exte
 int sa_align_pairs_banded(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t band, const sa_host_pair *pairs,
                           int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).in_band(band), pairs, np, device, results, aligned_text, aligned_pattern);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).in_band(band), pairs, np, device, results, aligned_text,
+                            aligned_pattern);
 }
 
 int sa_align_pairs_band_at(const sa_params *P, int32_t gap_open, int32_t gap_extend, const sa_band *bands, const sa_host_pair *pairs,
                            int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).in_bands(bands), pairs, np, device, results, aligned_text, aligned_pattern);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).in_bands(bands), pairs, np, device, results,
+                            aligned_text, aligned_pattern);
 }
 
 int sa_align_pairs_extend(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_host_pair *pairs,
                           int64_t np, int device, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
-    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), pairs, np, device, results, aligned_text, aligned_pattern);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), pairs, np, device, results,
+                            aligned_text, aligned_pattern);
 }
-
-}  // extern "C"
-
-int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device,
-                           const void *d_text, const void *d_pattern, sa_result *results, char *const *aligned_text,
-                           char *const *aligned_pattern)
-{
-    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
-        return fail(SA_ERR_INVALID, "seeds aligner: null argument");
-    DeviceGuard dg(device);
-    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
-    SeedTracePlan pl;
-    std::string err;
-    if (int rc = make_seeds_trace_plan(P, spec, pairs, seeds, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, &err))
-        return fail(rc, err);
-    if (!P->alphabet) return fail(SA_ERR_INVALID, "seeds aligner: params->alphabet is null");
-    g_stats = AffineStats();
-    g_stats.arena_bytes = pl.arena_bytes;
-    g_stats.chunks = (int32_t)pl.num_chunks();
-    if (np == 0) return SA_OK;
-    if ((!d_text || !d_pattern) && pl.score.input_bytes) return fail(SA_ERR_INVALID, "seeds aligner: null arena");
-    const int A = pl.score.A;
-    const size_t ni = pl.seeds.items.size();
-
-    std::vector<uint64_t> dir_words(ni), slots((size_t)np + 1);
-    for (size_t k = 0; k < ni; ++k) dir_words[k] = pl.dir_off[k] / 4;
-    for (int64_t p = 0; p < np; ++p) slots[p] = pl.slot_off[p];
-    slots[(size_t)np] = pl.string_bytes;
-    Workspace ws;
-    SeedItem *d_items;
-    SeedPair *d_seed_pairs;
-    int32_t *d_order, *d_pair_order, *d_table, *d_rows;
-    sa_score_result *d_scores;
-    sa_seed_result *d_seed_out;
-    uint32_t *d_ctrl, *d_dirs;
-    uint64_t *d_dir_off, *d_slot_off, *d_tail;
-    char *d_ot = nullptr, *d_op = nullptr, *d_alpha;
-    sa_result *d_results;
-    int rc;
-    if ((rc = ws.alloc(&d_items, ni * sizeof(SeedItem))) || (rc = ws.alloc(&d_seed_pairs, (size_t)np * sizeof(SeedPair))) ||
-        (rc = ws.alloc(&d_order, ni * 4)) || (rc = ws.alloc(&d_pair_order, (size_t)np * 4)) || (rc = ws.alloc(&d_table, 32 * 32 * 4)) ||
-        (rc = ws.alloc(&d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) || (rc = ws.alloc(&d_scores, ni * sizeof(sa_score_result))) ||
-        (rc = ws.alloc(&d_seed_out, (size_t)np * sizeof(sa_seed_result))) || (rc = ws.alloc(&d_ctrl, 256)) ||
-        (rc = ws.alloc(&d_dirs, pl.arena_bytes)) || (rc = ws.alloc(&d_dir_off, ni * 8)) || (rc = ws.alloc(&d_slot_off, ((size_t)np + 1) * 8)) ||
-        (rc = ws.alloc(&d_tail, (size_t)np * 8)) || (rc = ws.alloc(&d_alpha, 64)) || (rc = ws.alloc(&d_results, (size_t)np * sizeof(sa_result))))
-        return rc;
-    const bool strings = aligned_text != nullptr;
-    if (strings && ((rc = ws.alloc(&d_ot, pl.string_bytes)) || (rc = ws.alloc(&d_op, pl.string_bytes)))) return rc;
-    if (ni)
-    {
-        HIP_TRY(hipMemcpy(d_items, pl.seeds.items.data(), ni * sizeof(SeedItem), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_order, pl.score.order.data(), ni * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_dir_off, dir_words.data(), ni * 8, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(d_seed_pairs, pl.seeds.pairs.data(), (size_t)np * sizeof(SeedPair), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pair_order, pl.pair_order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_slot_off, slots.data(), slots.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_alpha, P->alphabet, (size_t)A + 1, hipMemcpyHostToDevice));
-
-    hipStream_t st = nullptr;
-    const int64_t nchunks = pl.num_chunks();
-    ws.events.reserve((size_t)nchunks * 3);
-    for (int64_t e = 0; e < nchunks * 3; ++e)
-    {
-        hipEvent_t ev;
-        HIP_TRY(hipEventCreate(&ev));
-        ws.events.push_back(ev);
-    }
-    HIP_TRY(hipMemsetAsync(d_ctrl, 0, 256, st));
-    TracedWaveArgs fa = {};
-    fa.sa = score_args(pl.score, d_text, d_pattern, nullptr, d_order, 0, d_table, d_rows, d_scores, d_ctrl);
-    fa.tr.dirs = d_dirs;
-    fa.tr.dir_off = d_dir_off;
-    fa.items = d_items;
-    ScoreArgs &s = fa.sa.s;
-    const WaveChoice choice = wave_choice(pl.score.spec, pl.score.mode, true);
-    SeedsCombineArgs ca;
-    ca.text = s.text;
-    ca.pattern = s.pattern;
-    ca.pairs = d_seed_pairs;
-    ca.table = d_table;
-    ca.item_out = d_scores;
-    ca.out = d_seed_out;
-    ca.ctrl = d_ctrl;
-    ca.A = A;
-    SeedWalkArgs wa;
-    wa.text = s.text;
-    wa.pattern = s.pattern;
-    wa.items = d_items;
-    wa.pairs = d_seed_pairs;
-    wa.scores = d_scores;
-    wa.seed_out = d_seed_out;
-    wa.dirs = d_dirs;
-    wa.dir_off = d_dir_off;
-    wa.slot_off = d_slot_off;
-    wa.out_text = d_ot;
-    wa.out_pattern = d_op;
-    wa.alphabet = d_alpha;
-    wa.results = d_results;
-    wa.tail_len = d_tail;
-    wa.A = A;
-    uint32_t ctrl[2] = {0, 0};
-    std::vector<uint64_t> tail((size_t)np);
-    auto enqueue = [&]() -> int {
-        for (int64_t c = 0; c < nchunks; ++c)
-        {
-            // the chunk's items in one traced fill, then the combine and the walk of the chunk's pairs
-            const int64_t begin = pl.chunk_begin[c], count = pl.chunk_begin[c + 1] - begin;
-            const int64_t pbegin = pl.pair_chunk_begin[c], pcount = pl.pair_chunk_begin[c + 1] - pbegin;
-            if (c) HIP_TRY(hipMemsetAsync(d_ctrl, 0, 4, st));  // the work counter; the bad-input flag stays
-            s.order = d_order + begin;
-            s.np = (int32_t)count;
-            wa.order = d_pair_order + pbegin;
-            HIP_TRY(hipEventRecord(ws.events[3 * c], st));
-            if (count)
-            {
-                const int grid = (int)std::min<int64_t>(count, pl.score.grid);
-                if (!launch_wave<true>(choice, kTraceRows, A <= 4, grid, st, fa))
-                    return fail(SA_ERR_UNSUPPORTED, "seeds aligner: the call's variant has no kernel instance");
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(ws.events[3 * c + 1], st));
-            ca.order = wa.order;
-            launch_seeds_combine(ca, pcount, st);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(walk_seeds_kernel, dim3((unsigned)pcount), dim3(64), 0, st, wa);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ws.events[3 * c + 2], st));
-        }
-        HIP_TRY(hipMemcpyAsync(ctrl, d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(results, d_results, (size_t)np * sizeof(sa_result), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(tail.data(), d_tail, (size_t)np * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return SA_OK;
-    };
-    if ((rc = enqueue()))
-    {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    for (int64_t c = 0; c < nchunks; ++c)
-    {
-        float f = 0, w = 0;
-        HIP_TRY(hipEventElapsedTime(&f, ws.events[3 * c], ws.events[3 * c + 1]));
-        HIP_TRY(hipEventElapsedTime(&w, ws.events[3 * c + 1], ws.events[3 * c + 2]));
-        g_stats.fill_ms += f;
-        g_stats.walk_ms += w;
-    }
-    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
-    for (int64_t p = 0; p < np; ++p)
-        if (results[p].status != SA_OK)
-            return fail(SA_ERR_HIP, "seeded walk of pair " + std::to_string(p) + " did not end within its halves' moves");
-    if (strings && pl.string_bytes)
-    {
-        std::vector<char> ht(pl.string_bytes), hp(pl.string_bytes);
-        HIP_TRY(hipMemcpy(ht.data(), d_ot, pl.string_bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hp.data(), d_op, pl.string_bytes, hipMemcpyDeviceToHost));
-        for (int64_t p = 0; p < np; ++p)
-        {
-            // the head piece (the left half and the seed) at the start of the slot, the tail piece (the right
-            // half) at its end
-            const uint64_t cap = pairs[p].text_len + pairs[p].pattern_len;
-            const uint64_t L = std::min<uint64_t>(results[p].num_alignment_bytes, cap), tl = std::min<uint64_t>(tail[p], L), hl = L - tl;
-            if (hl)
-            {
-                std::memcpy(aligned_text[p], ht.data() + pl.slot_off[p], hl);
-                std::memcpy(aligned_pattern[p], hp.data() + pl.slot_off[p], hl);
-            }
-            if (tl)
-            {
-                std::memcpy(aligned_text[p] + hl, ht.data() + pl.slot_off[p] + cap - tl, tl);
-                std::memcpy(aligned_pattern[p] + hl, hp.data() + pl.slot_off[p] + cap - tl, tl);
-            }
-        }
-    }
-    return SA_OK;
-}
-
-extern "C" {
 
 int sa_align_pairs_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
                          const sa_host_pair *pairs, int64_t np, int device, sa_result *results, char *const *aligned_text,
                          char *const *aligned_pattern)
 {
-    if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
-        return fail(SA_ERR_INVALID, "sa_align_pairs_seeds: null argument");
-    HostArenas in;
-    if (int rc = upload_host_pairs("sa_align_pairs_seeds", pairs, np, device, &in)) return rc;
-    return align_seeds_device(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), seeds, in.pairs.data(), np, device, in.text.p,
-                              in.pattern.p, results, aligned_text, aligned_pattern);
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_seeds(seeds), pairs, np, device,
+                            results, aligned_text, aligned_pattern);
 }
 
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks)
@@ -793,3 +687,87 @@ int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes
 }
 
 }  // extern "C"
+
+int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                           const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    SeedTracePlan pl;
+    TracedWaveArgs fa = {};
+    SeedsCombineArgs ca;
+    SeedWalkArgs wa;
+    WaveChoice choice = {};
+    int32_t *d_order, *d_pair_order;
+    auto plan = [&](std::string *err) {
+        return make_seeds_trace_plan(P, spec, pairs, spec.seeds, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, err);
+    };
+    auto setup = [&](TracedRun &r) -> int {
+        const size_t ni = pl.seeds.items.size();
+        std::vector<uint64_t> dir_words(ni), slots(pl.slot_off);
+        for (size_t k = 0; k < ni; ++k) dir_words[k] = pl.dir_off[k] / 4;
+        slots.push_back(pl.string_bytes);
+        SeedItem *d_items;
+        SeedPair *d_seed_pairs;
+        sa_score_result *d_scores;
+        sa_seed_result *d_seed_out;
+        uint64_t *d_dir_off, *d_slot_off, *d_tail;
+        int rc;
+        if ((rc = r.ws.upload(&d_items, pl.seeds.items)) || (rc = r.ws.upload(&d_seed_pairs, pl.seeds.pairs)) ||
+            (rc = r.ws.upload(&d_order, pl.score.order)) || (rc = r.ws.upload(&d_pair_order, pl.pair_order)) ||
+            (rc = r.ws.alloc(&d_scores, ni * sizeof(sa_score_result))) || (rc = r.ws.alloc(&d_seed_out, (size_t)np * sizeof(sa_seed_result))) ||
+            (rc = r.ws.upload(&d_dir_off, dir_words)) || (rc = r.ws.upload(&d_slot_off, slots)) || (rc = r.ws.alloc(&d_tail, (size_t)np * 8)))
+            return rc;
+        r.d_tail = d_tail;
+        fa.sa = score_args(pl.score, d_text, d_pattern, nullptr, d_order, 0, r.d_table, r.d_rows, d_scores, r.d_ctrl);
+        fa.tr.dirs = r.d_dirs;
+        fa.tr.dir_off = d_dir_off;
+        fa.items = d_items;
+        choice = wave_choice(pl.score.spec, pl.score.mode);
+        ca.text = fa.sa.s.text;
+        ca.pattern = fa.sa.s.pattern;
+        ca.pairs = d_seed_pairs;
+        ca.table = r.d_table;
+        ca.item_out = d_scores;
+        ca.out = d_seed_out;
+        ca.ctrl = r.d_ctrl;
+        ca.A = r.A;
+        wa.text = fa.sa.s.text;
+        wa.pattern = fa.sa.s.pattern;
+        wa.items = d_items;
+        wa.pairs = d_seed_pairs;
+        wa.scores = d_scores;
+        wa.seed_out = d_seed_out;
+        wa.dirs = r.d_dirs;
+        wa.dir_off = d_dir_off;
+        wa.slot_off = d_slot_off;
+        wa.out_text = r.d_ot;
+        wa.out_pattern = r.d_op;
+        wa.alphabet = r.d_alpha;
+        wa.results = r.d_results;
+        wa.tail_len = d_tail;
+        wa.A = r.A;
+        // the chunk's items in one traced fill (none: no launch), then the combine and the walk of the chunk's pairs
+        r.fill = [&](int64_t c) -> int {
+            ScoreArgs &s = fa.sa.s;
+            s.order = d_order + pl.chunk_begin[c];
+            s.np = (int32_t)(pl.chunk_begin[c + 1] - pl.chunk_begin[c]);
+            wa.order = ca.order = d_pair_order + pl.pair_chunk_begin[c];
+            if (s.np == 0) return SA_OK;
+            if (!launch_wave<true>(choice, kTraceRows, r.A <= 4, (int)std::min<int64_t>(s.np, pl.score.grid), r.st, fa))
+                return fail(SA_ERR_UNSUPPORTED, "seeds aligner: the call's variant has no kernel instance");
+            HIP_TRY(hipGetLastError());
+            return SA_OK;
+        };
+        r.walk = [&](int64_t c) -> int {
+            const int64_t pcount = pl.pair_chunk_begin[c + 1] - pl.pair_chunk_begin[c];
+            launch_seeds_combine(ca, pcount, r.st);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(walk_seeds_kernel, dim3((unsigned)pcount), dim3(64), 0, r.st, wa);
+            HIP_TRY(hipGetLastError());
+            return SA_OK;
+        };
+        return SA_OK;
+    };
+    return traced_run({"seeds aligner", "seeded walk", "its halves' moves", P, pairs, np, device, d_text, d_pattern, results, aligned_text,
+                       aligned_pattern},
+                      pl, plan, setup);
+}

@@ -78,8 +78,7 @@ struct sa_scorer : ScorePlan {
     sa_score_result *d_out = nullptr;
     uint32_t *d_ctrl = nullptr;
     bool ran = false;
-    // seeds scorer: the plan (num_pairs, order, d_out) is the work items'; seed_pairs counts the caller's pairs
-    bool seeds = false;
+    // seeds scorer (spec.seeded): the plan (num_pairs, order, d_out) is the work items'; seed_pairs counts the caller's pairs
     int64_t seed_pairs = 0;
     SeedItem *d_items = nullptr;
     SeedPair *d_seed_pairs = nullptr;
@@ -100,10 +99,11 @@ void free_scorer(sa_scorer *s)
 
 }  // namespace
 
-// every sa_scorer_create* but the seeds one: `spec` is the variant the function stands for
+// every sa_scorer_create*: `spec` is the variant the function stands for. A seeded spec plans the work items
+// (num_pairs, order and d_out are then theirs) and keeps the pairs' seeds and results beside them
 static int create_scorer(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
-    if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create: null argument");
+    if (!out) return fail(SA_ERR_INVALID, spec.seeded ? "sa_scorer_create_seeds: null argument" : "sa_scorer_create: null argument");
     *out = nullptr;
     if (spec.band_at && !spec.bands && np > 0) return fail(SA_ERR_INVALID, "sa_scorer_create_band_at: bands is null");
     DeviceGuard dg(device);
@@ -111,79 +111,57 @@ static int create_scorer(const sa_params *P, const WaveSpec &spec, const sa_pair
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
     s->device = device;
     std::string err;
-    if (int rc = make_score_plan(P, spec, pairs, np, device_cus(device), score_knobs(), s.get(), &err)) return fail(rc, err);
-    std::vector<ScorePair> h((size_t)np);
-    for (int64_t p = 0; p < np; ++p)
-        h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
-    const int A = s->A;
+    SeedItems si;
+    if (int rc = spec.seeded ? make_seeds_score_plan(P, spec, pairs, spec.seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err)
+                             : make_score_plan(P, spec, pairs, np, device_cus(device), score_knobs(), s.get(), &err))
+        return fail(rc, err);
+    if (spec.seeded) s->seed_pairs = np;
+    const size_t nw = (size_t)s->num_pairs;  // what the waves draw: pairs, or items
     int rc;
-    if ((rc = dmalloc(&s->d_pairs, h.size() * sizeof(ScorePair)))) return rc;
-    if ((rc = dmalloc(&s->d_order, (size_t)np * 4))) return rc;
+    if ((rc = dmalloc(&s->d_order, nw * 4))) return rc;
     if ((rc = dmalloc(&s->d_table, 32 * 32 * 4))) return rc;
     if ((rc = dmalloc(&s->d_rows, (size_t)s->grid * s->row_stride * (s->spec.affine ? 8 : 4)))) return rc;
-    if ((rc = dmalloc(&s->d_out, (size_t)np * sizeof(sa_score_result)))) return rc;
+    if ((rc = dmalloc(&s->d_out, nw * sizeof(sa_score_result)))) return rc;
     if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
-    if (spec.band_at && (rc = dmalloc(&s->d_bands, std::max<size_t>((size_t)np, 1) * sizeof(Band)))) return rc;
-    if (spec.band_at && np) HIP_TRY(hipMemcpy(s->d_bands, s->bands.data(), (size_t)np * sizeof(Band), hipMemcpyHostToDevice));
-    if (np)
+    if (nw) HIP_TRY(hipMemcpy(s->d_order, s->order.data(), nw * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_table, P->score_matrix, (size_t)s->A * s->A * 4, hipMemcpyHostToDevice));
+    // the descriptors: the items with the pairs' seeds and results, or the pairs with their bands
+    auto upload = [](auto **d, const auto &h) -> int {
+        if (int rc = dmalloc(d, h.size() * sizeof(h[0]))) return rc;
+        if (h.size()) HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
+        return SA_OK;
+    };
+    if (spec.seeded)
     {
-        HIP_TRY(hipMemcpy(s->d_pairs, h.data(), h.size() * sizeof(ScorePair), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->d_order, s->order.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+        if ((rc = upload(&s->d_items, si.items)) || (rc = upload(&s->d_seed_pairs, si.pairs))) return rc;
+        if ((rc = dmalloc(&s->d_seed_out, (size_t)np * sizeof(sa_seed_result)))) return rc;
     }
-    HIP_TRY(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
+    else
+    {
+        std::vector<ScorePair> h((size_t)np);
+        for (int64_t p = 0; p < np; ++p)
+            h[p] = ScorePair{pairs[p].text_offset, pairs[p].pattern_offset, (uint32_t)pairs[p].text_len, (uint32_t)pairs[p].pattern_len};
+        if ((rc = upload(&s->d_pairs, h))) return rc;
+        if (spec.band_at && (rc = upload(&s->d_bands, s->bands))) return rc;
+    }
     *out = s.release();
     return SA_OK;
 }
 
-// sa_scorer_create_seeds: the extension scorer of the work items, with the items, the pairs' seeds and the
-// pairs' results beside it
-static int create_seeds_scorer(const sa_params *P, const WaveSpec &spec, const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device,
-                               sa_scorer **out)
+// every sa_score_batch*: upload, create, run, and the fetch of its result type; a seeded spec is sa_score_batch_seeds
+template <typename RESULT>
+static int score_batch(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, RESULT *out,
+                       int (*fetch)(sa_scorer *, RESULT *, void *) = sa_scorer_fetch)
 {
-    if (!out) return fail(SA_ERR_INVALID, "sa_scorer_create_seeds: null argument");
-    *out = nullptr;
-    DeviceGuard dg(device);
-    if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
-    std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(new sa_scorer(), free_scorer);
-    s->device = device;
-    std::string err;
-    SeedItems si;
-    if (int rc = make_seeds_score_plan(P, spec, pairs, seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err)) return fail(rc, err);
-    s->seeds = true;
-    s->seed_pairs = np;
-    const size_t ni = si.items.size();
-    const int A = s->A;
-    int rc;
-    if ((rc = dmalloc(&s->d_items, std::max<size_t>(ni, 1) * sizeof(SeedItem)))) return rc;
-    if ((rc = dmalloc(&s->d_order, std::max<size_t>(ni, 1) * 4))) return rc;
-    if ((rc = dmalloc(&s->d_table, 32 * 32 * 4))) return rc;
-    if ((rc = dmalloc(&s->d_rows, std::max<size_t>((size_t)s->grid * s->row_stride * (s->spec.affine ? 8 : 4), 8)))) return rc;
-    if ((rc = dmalloc(&s->d_out, std::max<size_t>(ni, 1) * sizeof(sa_score_result)))) return rc;
-    if ((rc = dmalloc(&s->d_ctrl, 256))) return rc;
-    if ((rc = dmalloc(&s->d_seed_pairs, std::max<size_t>((size_t)np, 1) * sizeof(SeedPair)))) return rc;
-    if ((rc = dmalloc(&s->d_seed_out, std::max<size_t>((size_t)np, 1) * sizeof(sa_seed_result)))) return rc;
-    if (ni)
-    {
-        HIP_TRY(hipMemcpy(s->d_items, si.items.data(), ni * sizeof(SeedItem), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->d_order, s->order.data(), ni * 4, hipMemcpyHostToDevice));
-    }
-    if (np) HIP_TRY(hipMemcpy(s->d_seed_pairs, si.pairs.data(), (size_t)np * sizeof(SeedPair), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_table, P->score_matrix, (size_t)A * A * 4, hipMemcpyHostToDevice));
-    *out = s.release();
-    return SA_OK;
-}
-
-// every sa_score_batch* but the seeds one
-static int score_batch(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
-{
-    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch: null argument");
+    const char *const fn = spec.seeded ? "sa_score_batch_seeds" : "sa_score_batch";
+    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, std::string(fn) + ": null argument");
     HostArenas in;
-    if (int rc = upload_host_pairs("sa_score_batch", pairs, np, device, &in)) return rc;
+    if (int rc = upload_host_pairs(fn, pairs, np, device, &in)) return rc;
     sa_scorer *raw = nullptr;
     if (int rc = create_scorer(P, spec, in.pairs.data(), np, device, &raw)) return rc;
     std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
     if (int rc = sa_scorer_run(s.get(), in.text.p, in.pattern.p, nullptr)) return rc;
-    return sa_scorer_fetch(s.get(), out, nullptr);
+    return fetch(s.get(), out, nullptr);
 }
 
 extern "C" {
@@ -220,20 +198,13 @@ int sa_scorer_create_extend(const sa_params *P, int32_t gap_open, int32_t gap_ex
 int sa_scorer_create_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
                            const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
-    return create_seeds_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), seeds, pairs, np, device, out);
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_seeds(seeds), pairs, np, device, out);
 }
 
 int sa_score_batch_seeds(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
                          const sa_host_pair *pairs, int64_t np, int device, sa_seed_result *out)
 {
-    if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, "sa_score_batch_seeds: null argument");
-    HostArenas in;
-    if (int rc = upload_host_pairs("sa_score_batch_seeds", pairs, np, device, &in)) return rc;
-    sa_scorer *raw = nullptr;
-    if (int rc = create_seeds_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), seeds, in.pairs.data(), np, device, &raw)) return rc;
-    std::unique_ptr<sa_scorer, void (*)(sa_scorer *)> s(raw, free_scorer);
-    if (int rc = sa_scorer_run(s.get(), in.text.p, in.pattern.p, nullptr)) return rc;
-    return sa_scorer_fetch_seeds(s.get(), out, nullptr);
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_seeds(seeds), pairs, np, device, out, sa_scorer_fetch_seeds);
 }
 
 int sa_scorer_destroy(sa_scorer *s)
@@ -253,18 +224,18 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
     s->ran = true;
     // a seeds scorer: the plan is the work items', filled in one launch (both halves of every pair balance
     // over the waves), then the combine of the pairs
-    if ((s->seeds ? s->seed_pairs : s->num_pairs) == 0) return SA_OK;
+    if ((s->spec.seeded ? s->seed_pairs : s->num_pairs) == 0) return SA_OK;
     if (s->num_pairs)
     {
         WaveArgs a = {};
         a.sa = score_args(*s, d_text, d_pattern, s->d_pairs, s->d_order, s->num_pairs, s->d_table, s->d_rows, s->d_out, s->d_ctrl);
-        if (s->seeds) a.items = s->d_items;
+        if (s->spec.seeded) a.items = s->d_items;
         else a.bands = s->d_bands;
-        if (!launch_wave<false>(wave_choice(s->spec, s->mode, s->seeds), s->R, s->A <= 4, s->grid, st, a))
+        if (!launch_wave<false>(wave_choice(s->spec, s->mode), s->R, s->A <= 4, s->grid, st, a))
             return fail(SA_ERR_UNSUPPORTED, "sa_scorer_run: the scorer's variant has no kernel instance");
         HIP_TRY(hipGetLastError());
     }
-    if (s->seeds)
+    if (s->spec.seeded)
     {
         SeedsCombineArgs c;
         c.text = (const int8_t *)d_text;
@@ -284,7 +255,7 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
 
 int sa_scorer_fetch_seeds(sa_scorer *s, sa_seed_result *out, void *stream)
 {
-    if (!s || !s->seeds) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: not a seeds scorer");
+    if (!s || !s->spec.seeded) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: not a seeds scorer");
     if (!out && s->seed_pairs) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: null argument");
     if (!s->ran) return fail(SA_ERR_INVALID, "sa_scorer_fetch_seeds: the scorer has not been run");
     DeviceGuard dg(s->device);
@@ -301,7 +272,7 @@ int sa_scorer_fetch_seeds(sa_scorer *s, sa_seed_result *out, void *stream)
 
 int sa_scorer_fetch(sa_scorer *s, sa_score_result *out, void *stream)
 {
-    if (s && s->seeds)
+    if (s && s->spec.seeded)
     {
         // a seeds scorer: the score with the absolute end cell
         if (!out && s->seed_pairs) return fail(SA_ERR_INVALID, "sa_scorer_fetch: null argument");

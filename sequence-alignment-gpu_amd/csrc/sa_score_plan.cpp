@@ -99,6 +99,7 @@ int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
     }
     if (spec.band_at && (!affine || spec.banded)) return fail(SA_ERR_INVALID, "per-pair bands take gap_open and gap_extend and no half-width");
     if (spec.band_at && !bands && np > 0) return fail(SA_ERR_INVALID, "scorer: null argument");
+    if (spec.seeded) return fail(SA_ERR_INVALID, "a seeded call is planned by its work items (make_seeds_score_plan)");
     if (spec.extend)
     {
         if (!affine) return fail(SA_ERR_INVALID, "extension alignment takes gap_open and gap_extend");
@@ -188,6 +189,7 @@ int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
     pl.spec.affine = affine;
     pl.spec.gap_extend = affine ? spec.gap_extend : 0;
     pl.spec.bands = nullptr;  // the caller's; the plan keeps the clipped copy
+    pl.spec.seeds = nullptr;
     pl.num_pairs = np;
     pl.num_cu = kn.max_cus > 0 ? std::min(num_cu, kn.max_cus) : num_cu;
 
@@ -278,10 +280,13 @@ int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
         *err = "seeds scorer: null argument";
         return SA_ERR_INVALID;
     }
+    WaveSpec ext = spec;  // the extension each item runs; make_score_plan takes no seeded spec
+    ext.seeded = false;
+    ext.seeds = nullptr;
     // the mode, the xdrop and the limits, on the whole pairs: the sum of the three scores of a pair stays
     // under the bound of its (n, m), and so does every key
     ScorePlan whole;
-    if (int rc = make_score_plan(P, spec, pairs, np, num_cu, kn, &whole, err)) return rc;
+    if (int rc = make_score_plan(P, ext, pairs, np, num_cu, kn, &whole, err)) return rc;
     if (np > 0 && !seeds)
     {
         *err = "seeds is null";
@@ -317,7 +322,8 @@ int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
     // the items as extension pairs: cost, R, order by cells, grid and boundary rows
     std::vector<sa_pair> ip(items->items.size());
     for (size_t k = 0; k < ip.size(); ++k) ip[k] = sa_pair{0, items->items[k].n, 0, items->items[k].m};
-    if (int rc = make_score_plan(P, spec, ip.data(), (int64_t)ip.size(), num_cu, kn, out, err)) return rc;
+    if (int rc = make_score_plan(P, ext, ip.data(), (int64_t)ip.size(), num_cu, kn, out, err)) return rc;
+    out->spec.seeded = true;
     out->device_bytes += whole.input_bytes - out->input_bytes + (uint64_t)ip.size() * (sizeof(SeedItem) - 24) +
                          (uint64_t)np * (sizeof(SeedPair) + sizeof(sa_seed_result));
     out->input_bytes = whole.input_bytes;

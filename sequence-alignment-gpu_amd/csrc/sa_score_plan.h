@@ -56,6 +56,8 @@ struct WaveSpec {
     const sa_band *bands = nullptr;
     bool extend = false;           // extension alignment (sa_hip.h sa_score_batch_extend) under
     int32_t xdrop = SA_NO_XDROP;   // this X-drop, SA_NO_XDROP for none
+    bool seeded = false;           // seed extension (sa_hip.h sa_seed, one per pair): an extension to both
+    const sa_seed *seeds = nullptr;  // sides of the caller's seeds, planned by the make_seeds_* planners
     bool traced = false;           // the aligners' instances: direction words, affine whatever the penalties
 
     static WaveSpec gaps(int32_t open, int32_t extend)
@@ -85,6 +87,13 @@ struct WaveSpec {
         WaveSpec s = *this;
         s.extend = true;
         s.xdrop = x;
+        return s;
+    }
+    WaveSpec from_seeds(const sa_seed *per_pair) const
+    {
+        WaveSpec s = *this;
+        s.seeded = true;
+        s.seeds = per_pair;
         return s;
     }
 };
@@ -169,7 +178,7 @@ constexpr uint64_t kBandScoreLimit = 1ull << 29;
 struct ScorePlan {
     int mode = 0, A = 0, gap = 0, R = 1, key_rowbits = 1;  // gap: the linear penalty, or gap open
     WaveSpec spec;                 // the variant the scorer runs: the call's, but affine false where the linear
-                                   // instances serve (an extension with gap open == gap extend) and bands null
+                                   // instances serve (an extension with gap open == gap extend), bands and seeds null
     std::vector<Band> bands;       // band-at scorer: every pair's band, clipped (band_clip)
     int num_cu = 0, waves_per_simd = 0, grid = 0;
     int64_t num_pairs = 0;
@@ -199,6 +208,7 @@ struct ScorePlan {
 //    (SA_ERR_UNSUPPORTED). Cost, R, grid and bytes are the local program's, the linear one when gap open
 //    equals gap extend (unless `traced`); xdrop changes nothing, the stop rows are not known beforehand. The
 //    limits are the int32 one and the local best-cell key's.
+//  - seeded: SA_ERR_INVALID. Seeds are planned as work items, by make_seeds_score_plan.
 int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
                     ScorePlan *out, std::string *err);
 
@@ -224,7 +234,7 @@ struct SeedItems {
     std::vector<SeedPair> pairs;
 };
 
-// Plans the seeds scorer (`spec` an extension's): `seeds` null with pairs, ts + L > n and ps + L > m are SA_ERR_INVALID, the
+// Plans the seeds scorer (`spec` an extension's, seeded or not; the plan's is): `seeds` null with pairs, ts + L > n and ps + L > m are SA_ERR_INVALID, the
 // message naming the first such pair; the mode, the xdrop and the limits are make_score_plan's for the
 // extension scorer on the whole pairs' (n, m). The plan is then make_score_plan's for the items as
 // extension pairs: costed by the local step model, ordered by cells (plan->order holds item indices and

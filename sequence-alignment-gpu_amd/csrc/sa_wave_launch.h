@@ -54,10 +54,10 @@ struct WaveChoice {
 //  - Anything else is the program of its mode; the half-width band adds its flag.
 // The planner has refused what has no instance (a linear band, SA_FIT or free ends under a half-width, a band
 // under an extension), so a spec that got past it names a row of the table below.
-constexpr WaveChoice wave_choice(const WaveSpec &sp, int mode, bool seed = false)
+constexpr WaveChoice wave_choice(const WaveSpec &sp, int mode)
 {
     const unsigned aff = sp.affine ? kWaveAffine : 0u;
-    if (sp.extend) return WaveChoice{aff | kWaveExtend | (seed ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop};
+    if (sp.extend) return WaveChoice{aff | kWaveExtend | (sp.seeded ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop};
     if (sp.band_at && mode == SA_LOCAL) return WaveChoice{kVarBandAtLocal, SA_LOCAL, 0};
     const int ends = sp.band_at && mode == SA_GLOBAL ? 0
                      : sp.band_at && mode == SA_FIT  ? SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END
@@ -69,7 +69,7 @@ constexpr WaveChoice wave_choice(const WaveSpec &sp, int mode, bool seed = false
 }
 
 namespace wave_choice_check {
-constexpr WaveSpec spec(bool affine, bool banded = false, bool band_at = false, bool extend = false)
+constexpr WaveSpec spec(bool affine, bool banded = false, bool band_at = false, bool extend = false, bool seeded = false)
 {
     WaveSpec s;
     s.affine = affine;
@@ -78,6 +78,7 @@ constexpr WaveSpec spec(bool affine, bool banded = false, bool band_at = false, 
     s.band_at = band_at;
     s.extend = extend;
     s.xdrop = extend ? 9 : SA_NO_XDROP;
+    s.seeded = seeded;
     return s;
 }
 constexpr bool is(WaveChoice c, unsigned flags, int program, int value) { return c.flags == flags && c.program == program && c.value == value; }
@@ -94,7 +95,7 @@ static_assert(is(wave_choice(spec(true, false, true), SA_ENDS_FREE | SA_FREE_PAT
               "band-at ends-free: its own flags");
 static_assert(is(wave_choice(spec(true, false, true), SA_LOCAL), kVarBandAtLocal, SA_LOCAL, 0), "band-at local: no free ends");
 static_assert(is(wave_choice(spec(false, false, false, true), SA_GLOBAL), kVarExtend, SA_GLOBAL, 9), "extension: the global program");
-static_assert(is(wave_choice(spec(true, false, false, true), SA_GLOBAL, true), kVarAffineSeeds, SA_GLOBAL, 9), "seeds: extension of a work item");
+static_assert(is(wave_choice(spec(true, false, false, true, true), SA_GLOBAL), kVarAffineSeeds, SA_GLOBAL, 9), "seeds: extension of a work item");
 }  // namespace wave_choice_check
 
 // One row of the table: a variant and the programs it has instances of.

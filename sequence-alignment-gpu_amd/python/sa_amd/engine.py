@@ -234,6 +234,35 @@ def _seeds(seeds, num_pairs: int, xdrop, band, bands) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
+def _variant(gap: int, gap_extend, band, bands, xdrop, seeds, num_pairs: int):
+    """The variant that the keywords of score_batch, Scorer and align_pairs_affine name, resolved once: the
+    suffix of the C function (sa_score_batch<suffix>, sa_scorer_create<suffix>, sa_align_pairs<suffix>), the
+    arguments that go between params and the pairs, and the array those point into, to keep alive over the
+    call. Without `gap_extend` the gap is linear, gap_open = gap_extend = gap; with nothing else either, there
+    is no gap model: the suffix is empty."""
+    if band is not None and bands is not None:
+        raise ValueError("band= and bands= exclude each other")
+    if xdrop is not None and (band is not None or bands is not None):
+        raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
+    ge = gap if gap_extend is None else gap_extend
+    if seeds is not None:
+        sd = _seeds(seeds, num_pairs, xdrop, band, bands)
+        return "_seeds", (gap, ge, xdrop, sd.ctypes.data), sd
+    if xdrop is not None:
+        return "_extend", (gap, ge, xdrop), None
+    if bands is not None:
+        b = _bands(bands, num_pairs)
+        return "_band_at", (gap, ge, b.ctypes.data), b
+    if band is not None:
+        return "_banded", (gap, ge, band), None
+    if gap_extend is not None:
+        return "_affine", (gap, ge), None
+    return _NO_GAP_MODEL
+
+
+_NO_GAP_MODEL = ("", (), None)
+
+
 def band_reachable(mode: int, n: int, m: int, lo: int, hi: int) -> bool:
     """sa_band_reachable (host only, no device call): whether a pair of n text and m pattern letters has
     an alignment of `mode` inside the band lo <= j - i <= hi. The band-at functions (bands=) refuse a
@@ -278,6 +307,26 @@ class SaHostPair(ctypes.Structure):
                 ("pattern_len", ctypes.c_uint64)]
 
 
+def _host_pairs(texts, patterns):
+    """The pairs of a call from host memory: the sa_host_pair array, and the contiguous int8 arrays it points
+    into, to keep alive over the call."""
+    ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
+    ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
+    hp = (SaHostPair * max(1, len(ts)))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
+    return hp, ts, ps
+
+
+def _result_dict(r, text=None, pattern=None) -> dict:
+    """An sa_result as the dict the aligners return; with the bytes that begin with the pair's aligned strings,
+    those too."""
+    L = r.num_alignment_bytes
+    d = {"score": r.score, "num_bytes": L, "start_text": r.start_text, "start_pattern": r.start_pattern}
+    if text is not None:
+        d["aligned_text"] = bytes(text[:L]).decode()
+        d["aligned_pattern"] = bytes(pattern[:L]).decode()
+    return d
+
+
 def batch_deal(cells: list[int], num_shards: int) -> list[int]:
     """sa_batch_deal: the pair -> shard assignment sa_align_batch uses (host only)."""
     c = np.ascontiguousarray(cells, dtype=np.uint64)
@@ -300,7 +349,7 @@ def batch_last_stats() -> dict:
 def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
                 num_gpus: int = 1, alphabet: bytes | None = None, strings: bool = True) -> list[dict]:
     """sa_align_batch: independent pairs from host memory over devices 0..num_gpus-1 (synchronous)."""
-    return _align_host_pairs(mode, texts, patterns, S, gap, None, num_gpus, 0, alphabet, strings)
+    return _align_host_pairs(mode, texts, patterns, S, gap, num_gpus, alphabet, strings, _NO_GAP_MODEL)
 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
@@ -319,13 +368,10 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
     (one (text_pos, pattern_pos, length) per pair; requires `xdrop`, mode SA_GLOBAL, no band),
     sa_align_pairs_seeds: the extension to both sides of each pair's seed joined with the seed's letters;
     start_text and start_pattern are the 0-based indices of the first aligned letters."""
-    if band is not None and bands is not None:
-        raise ValueError("band= and bands= exclude each other")
-    if xdrop is not None and (band is not None or bands is not None):
-        raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
-    if seeds is not None:
-        seeds = _seeds(seeds, len(texts), xdrop, band, bands)
-    return _align_host_pairs(mode, texts, patterns, S, gap_open, gap_extend, 1, device, None, strings, band, bands, xdrop, seeds)
+    variant = _variant(gap_open, gap_extend, band, bands, xdrop, seeds, len(texts))
+    if gap_extend is None and xdrop is None:  # as ever: without a gap model, align_batch on one device, band or no band
+        return align_batch(mode, texts, patterns, S, gap_open, 1, None, strings)
+    return _align_host_pairs(mode, texts, patterns, S, gap_open, device, None, strings, variant)
 
 
 def affine_last_stats() -> dict:
@@ -336,45 +382,23 @@ def affine_last_stats() -> dict:
     return {"fill_ms": f.value, "walk_ms": w.value, "arena_bytes": b.value, "num_chunks": c.value}
 
 
-def _align_host_pairs(mode, texts, patterns, S, gap, gap_extend, num_gpus, device, alphabet, strings, band=None,
-                      bands=None, xdrop=None, seeds=None) -> list[dict]:
-    """align_batch (gap_extend None) and align_pairs_affine (with `band`, sa_align_pairs_banded): one
-    packing of the host pairs and buffers."""
+def _align_host_pairs(mode, texts, patterns, S, gap, where, alphabet, strings, variant) -> list[dict]:
+    """align_batch (no gap model: `where` is num_gpus) and align_pairs_affine (`variant` of _variant, `where` the
+    device): one packing of the host pairs and buffers."""
     p, S_keep, alpha_keep = _params(mode, S, gap, alphabet, 0)
-    ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
-    ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
+    hp, ts, ps = _host_pairs(texts, patterns)
     n = len(ts)
-    hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
     bufs_t = [ctypes.create_string_buffer(max(1, len(t) + len(x))) for t, x in zip(ts, ps)] if strings else []
     bufs_p = [ctypes.create_string_buffer(max(1, len(t) + len(x))) for t, x in zip(ts, ps)] if strings else []
     at = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_t]) if strings else None
     ap = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in bufs_p]) if strings else None
     res = (SaResult * max(1, n))()
-    if seeds is not None:
-        _check(lib.sa_align_pairs_seeds(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, seeds.ctypes.data,
-                                        hp, n, device, res, at, ap))
-    elif xdrop is not None:
-        _check(lib.sa_align_pairs_extend(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, hp, n, device,
-                                         res, at, ap))
-    elif gap_extend is None:
-        _check(lib.sa_align_batch(ctypes.byref(p), hp, n, num_gpus, res, at, ap))
-    elif bands is not None:
-        b = _bands(bands, n)
-        _check(lib.sa_align_pairs_band_at(ctypes.byref(p), gap, gap_extend, b.ctypes.data, hp, n, device, res, at, ap))
-    elif band is None:
-        _check(lib.sa_align_pairs_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, res, at, ap))
-    else:
-        _check(lib.sa_align_pairs_banded(ctypes.byref(p), gap, gap_extend, band, hp, n, device, res, at, ap))
-    out = []
-    for i, r in enumerate(res[:n]):
-        d = {"score": r.score, "num_bytes": r.num_alignment_bytes, "start_text": r.start_text,
-             "start_pattern": r.start_pattern}
-        if strings:
-            L = r.num_alignment_bytes
-            d["aligned_text"] = bufs_t[i].raw[:L].decode()
-            d["aligned_pattern"] = bufs_p[i].raw[:L].decode()
-        out.append(d)
-    return out
+    suffix, args, keep = variant
+    fn = getattr(lib, "sa_align_pairs" + suffix) if suffix else lib.sa_align_batch
+    _check(fn(ctypes.byref(p), *args, hp, n, where, res, at, ap))
+    if not strings:
+        return [_result_dict(r) for r in res[:n]]
+    return [_result_dict(r, bufs_t[i].raw, bufs_p[i].raw) for i, r in enumerate(res[:n])]
 
 
 class Plan:
@@ -414,8 +438,7 @@ class Plan:
     def results(self, stream: int | None = None) -> list[dict]:
         out = (SaResult * max(1, self.num_pairs))()
         _check(lib.sa_plan_fetch_results(self.handle, out, stream))
-        return [{"score": r.score, "num_bytes": r.num_alignment_bytes, "start_text": r.start_text,
-                 "start_pattern": r.start_pattern} for r in out[: self.num_pairs]]
+        return [_result_dict(r) for r in out[: self.num_pairs]]
 
     def results_array(self, stream: int | None = None) -> np.ndarray:
         """Every pair's sa_result as one numpy structured array (RESULT_DTYPE): no per-pair objects."""
@@ -451,12 +474,7 @@ class Plan:
         offs = np.zeros(max(1, self.num_pairs), np.uint64)
         _check(lib.sa_plan_fetch_all(self.handle, out, tb.ctypes.data, pb.ctypes.data, max(1, nb),
                                      offs.ctypes.data, stream))
-        res = []
-        for r, o in zip(out[: self.num_pairs], offs.tolist()):
-            L = r.num_alignment_bytes
-            res.append({"score": r.score, "num_bytes": L, "start_text": r.start_text, "start_pattern": r.start_pattern,
-                        "aligned_text": tb[o:o + L].tobytes().decode(), "aligned_pattern": pb[o:o + L].tobytes().decode()})
-        return res
+        return [_result_dict(r, tb[o:], pb[o:]) for r, o in zip(out[: self.num_pairs], offs.tolist())]
 
 
 # numpy view of sa_score_result (include/sa_hip.h): int32 score, int32 status, uint64 x 2
@@ -481,36 +499,12 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     With `seeds` (one (text_pos, pattern_pos, length) per pair; requires `xdrop`, mode SA_GLOBAL, no band),
     sa_score_batch_seeds: the extension to both sides of each pair's seed plus the seed's score, as a
     SEED_DTYPE array (score, status, begin_text, begin_pattern, end_text, end_pattern)."""
-    if band is not None and bands is not None:
-        raise ValueError("band= and bands= exclude each other")
-    if xdrop is not None and (band is not None or bands is not None):
-        raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
+    suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(texts))
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
-    ts = [np.ascontiguousarray(t, dtype=np.int8) for t in texts]
-    ps = [np.ascontiguousarray(x, dtype=np.int8) for x in patterns]
+    hp, ts, ps = _host_pairs(texts, patterns)
     n = len(ts)
-    hp = (SaHostPair * max(1, n))(*[SaHostPair(t.ctypes.data, len(t), x.ctypes.data, len(x)) for t, x in zip(ts, ps)])
-    if seeds is not None:
-        sd = _seeds(seeds, n, xdrop, band, bands)
-        res = np.zeros(max(1, n), SEED_DTYPE)
-        _check(lib.sa_score_batch_seeds(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, sd.ctypes.data, hp,
-                                        n, device, res.ctypes.data))
-        return res[:n]
-    out = np.zeros(max(1, n), SCORE_DTYPE)
-    if xdrop is not None:
-        _check(lib.sa_score_batch_extend(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, xdrop, hp, n, device,
-                                         out.ctypes.data))
-    elif bands is not None:
-        b = _bands(bands, n)
-        _check(lib.sa_score_batch_band_at(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, b.ctypes.data, hp, n,
-                                          device, out.ctypes.data))
-    elif band is not None:
-        _check(lib.sa_score_batch_banded(ctypes.byref(p), gap, gap if gap_extend is None else gap_extend, band, hp, n,
-                                         device, out.ctypes.data))
-    elif gap_extend is None:
-        _check(lib.sa_score_batch(ctypes.byref(p), hp, n, device, out.ctypes.data))
-    else:
-        _check(lib.sa_score_batch_affine(ctypes.byref(p), gap, gap_extend, hp, n, device, out.ctypes.data))
+    out = np.zeros(max(1, n), SEED_DTYPE if seeds is not None else SCORE_DTYPE)
+    _check(getattr(lib, "sa_score_batch" + suffix)(ctypes.byref(p), *args, hp, n, device, out.ctypes.data))
     return out[:n]
 
 
@@ -526,10 +520,7 @@ class Scorer:
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
                  device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
                  bands=None, xdrop: int | None = None, seeds=None):
-        if band is not None and bands is not None:
-            raise ValueError("band= and bands= exclude each other")
-        if xdrop is not None and (band is not None or bands is not None):
-            raise ValueError("xdrop= takes no band: extension alignment inside a band is not built")
+        suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(pairs))
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)
@@ -537,25 +528,7 @@ class Scorer:
         self.device = device
         h = ctypes.c_void_p()
         self.seeded = seeds is not None
-        if seeds is not None:
-            sd = _seeds(seeds, len(pairs), xdrop, band, bands)
-            _check(lib.sa_scorer_create_seeds(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, xdrop,
-                                              sd.ctypes.data, arr, len(pairs), device, ctypes.byref(h)))
-        elif xdrop is not None:
-            _check(lib.sa_scorer_create_extend(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, xdrop,
-                                               arr, len(pairs), device, ctypes.byref(h)))
-        elif bands is not None:
-            b = _bands(bands, len(pairs))
-            _check(lib.sa_scorer_create_band_at(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend,
-                                                b.ctypes.data, arr, len(pairs), device, ctypes.byref(h)))
-        elif band is not None:
-            _check(lib.sa_scorer_create_banded(ctypes.byref(self._p), gap, gap if gap_extend is None else gap_extend, band,
-                                               arr, len(pairs), device, ctypes.byref(h)))
-        elif gap_extend is None:
-            _check(lib.sa_scorer_create(ctypes.byref(self._p), arr, len(pairs), device, ctypes.byref(h)))
-        else:
-            _check(lib.sa_scorer_create_affine(ctypes.byref(self._p), gap, gap_extend, arr, len(pairs), device,
-                                               ctypes.byref(h)))
+        _check(getattr(lib, "sa_scorer_create" + suffix)(ctypes.byref(self._p), *args, arr, len(pairs), device, ctypes.byref(h)))
         self.handle = h
 
     def close(self) -> None:
@@ -621,14 +594,6 @@ def search(mode: int, query: np.ndarray, texts: list[np.ndarray], S: np.ndarray,
     else:
         _check(lib.sa_search_affine(ctypes.byref(p), gap, gap_extend, q.ctypes.data, len(q), tp, tl.ctypes.data, n, k,
                                     device, scores.ctypes.data, idx.ctypes.data, res, at, ap, ctypes.byref(nh)))
-    hits = []
-    for h in range(nh.value):
-        r = res[h]
-        d = {"index": int(idx[h]), "score": r.score, "num_bytes": r.num_alignment_bytes, "start_text": r.start_text,
-             "start_pattern": r.start_pattern}
-        if strings:
-            L = r.num_alignment_bytes
-            d["aligned_text"] = bufs_t[h].raw[:L].decode()
-            d["aligned_pattern"] = bufs_p[h].raw[:L].decode()
-        hits.append(d)
+    hits = [{"index": int(idx[h]), **(_result_dict(res[h], bufs_t[h].raw, bufs_p[h].raw) if strings else _result_dict(res[h]))}
+            for h in range(nh.value)]
     return scores[:n], hits
