@@ -225,6 +225,23 @@ uint64_t alignSequencesGPUSeeds(const Request *requests, Response *responses, ui
                                 int gapOpen, int gapExtend, int xdrop, const uint64_t *seedTextPos,
                                 const uint64_t *seedPatternPos, const uint64_t *seedLength);
 
+/// Extension: the four functions above inside a width of the anchor's diagonal (sa_score_batch_extend_band,
+/// sa_align_pairs_extend_band, sa_score_batch_seeds_band, sa_align_pairs_seeds_band; sa_hip.h has the
+/// definition): cell (i, j) of an extension matrix counts iff |j - i| <= width, for a seeded request in each
+/// half's own coordinates, one width >= 0 for all requests. With width >= max(n, m) every value equals the
+/// function's without a width. The aligners keep direction bytes for the band only. Everything else as the
+/// functions above. Returns 0, or 1 with the message on stdout.
+uint64_t scoreSequencesGPUExtendBand(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                     int xdrop, int width, int *scores);
+uint64_t alignSequencesGPUExtendBand(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                     int gapOpen, int gapExtend, int xdrop, int width);
+uint64_t scoreSequencesGPUSeedsBand(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                    int xdrop, int width, const uint64_t *seedTextPos, const uint64_t *seedPatternPos,
+                                    const uint64_t *seedLength, int *scores);
+uint64_t alignSequencesGPUSeedsBand(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                    int gapOpen, int gapExtend, int xdrop, int width, const uint64_t *seedTextPos,
+                                    const uint64_t *seedPatternPos, const uint64_t *seedLength);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

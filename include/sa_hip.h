@@ -514,8 +514,58 @@ int sa_align_pairs_seeds(const sa_params *params, int32_t gap_open, int32_t gap_
                          const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
                          char *const *aligned_text, char *const *aligned_pattern);
 
+/* ---- banded extension: extension and seeds within a width of the anchor's diagonal ------------ */
+
+/* width = w >= 0, one per call. Cell (i, j) of an extension matrix is in band iff |j - i| <= w: the band
+ * lies about the diagonal of the extension's anchor, the origin. For a seeded pair this holds for each half
+ * in its own coordinates, the left half being the reversed-prefix matrix, so the same w serves both halves
+ * and nothing is mirrored. Everything is the extension definition above, on the banded matrix:
+ *   cells:      Gotoh's recurrence with global borders and no clamp; H, E and F of every out-of-band cell
+ *               are minus infinity, border cells included: H[0][j] = -gap(j) for j <= w, H[i][0] = -gap(i)
+ *               for i <= w. The origin is always in band
+ *   row maxima: r(i) is the maximum of H[i][j] over the in-band j in 1..n, minus infinity when the row has
+ *               none, which is the case for i > n + w
+ *   stop row:   B and i* as defined; a minus-infinity row drops under every X >= 0, and under SA_NO_XDROP
+ *               nothing drops
+ *   result:     the first maximum in row-major order over the in-band interior cells of rows < i*, if it
+ *               is > 0; otherwise 0 at (0, 0)
+ *   walk:       from that cell to the origin; it never leaves the band
+ *   empty:      as extension has it
+ * r, B and i* are defined on the banded matrix: no output depends on rows_per_lane, the grid or how much
+ * work is skipped.
+ * Identities: (W1) w >= max(n, m) gives every output of the unbanded _extend / _seeds function at every
+ * xdrop. (W2) The score and both strings equal sa_align_pairs_band_at in SA_GLOBAL mode with band {-w, w}
+ * on text[:end_text], pattern[:end_pattern]; the end cell is in band, so that pair is reachable. (W3) Under
+ * SA_NO_XDROP the score is non-decreasing in w and never above the unbanded score. (W4)
+ * gap_open == gap_extend == g gives the outputs of the linear recurrence of g; the instance that runs is
+ * affine, as for the band-at scorer. (W5) Seeds S1, S2 and S3 hold with the same width on both sides, S3
+ * exactly, ties included, because the band is symmetric.
+ * Refusals: width < 0 is SA_ERR_INVALID; any width above max(n, m) acts as if clipped to it. The mode and
+ * xdrop rules are extension's (the seeds functions': theirs). The limits are extension's best-cell key range
+ * plus the banded score limit (SA_ERR_UNSUPPORTED, "scores may reach the band's sentinel"). band / bands
+ * (the functions above) stay separate: there is no _banded or _band_at extension.
+ * The aligners keep direction bytes for the band's windows only, as sa_align_pairs_band_at does for a band
+ * of the caller's: a pair (a seeded pair: its two halves) whose full rectangle exceeds
+ * SA_TRACE_ARENA_BYTES aligns when its band fits. sa_scorer_fetch_seeds serves a banded seeds scorer
+ * unchanged, and sa_affine_last_stats reports the aligner calls. */
+int sa_score_batch_extend_band(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                               const sa_host_pair *pairs, int64_t num_pairs, int device, sa_score_result *out);
+int sa_scorer_create_extend_band(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                                 const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_align_pairs_extend_band(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                               const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                               char *const *aligned_text, char *const *aligned_pattern);
+int sa_score_batch_seeds_band(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                              const sa_seed *seeds, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_seed_result *out);
+int sa_scorer_create_seeds_band(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                                const sa_seed *seeds, const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_align_pairs_seeds_band(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                              const sa_seed *seeds, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                              char *const *aligned_text, char *const *aligned_pattern);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
- * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend, sa_align_pairs_seeds or sa_search_affine (k > 0): device
+ * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend, sa_align_pairs_seeds,
+ * sa_align_pairs_extend_band, sa_align_pairs_seeds_band or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

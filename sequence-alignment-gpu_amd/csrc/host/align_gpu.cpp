@@ -195,6 +195,7 @@ struct Variant {
     const int *lo = nullptr, *hi = nullptr;       // the per-request bands of the ...BandAt functions
     const int *xdrop = nullptr;       // extension: the mode is SA_GLOBAL, whose borders an extension has, whatever alignmentType says
     const std::vector<sa_seed> *seeds = nullptr;  // with xdrop: the ...Seeds functions
+    const int *width = nullptr;       // with xdrop: the ...ExtendBand and ...SeedsBand functions
     explicit Variant(const char *n) : name(n), affine(false), gapOpen(0), gapExtend(0) {}
     Variant(const char *n, int open, int extend) : name(n), affine(true), gapOpen(open), gapExtend(extend) {}
 };
@@ -248,7 +249,9 @@ uint64_t scoreRequests(const Variant &v, const Request *requests, uint64_t numRe
     const int64_t n = (int64_t)numRequests;
     std::vector<sa_score_result> res(numRequests);
     std::vector<sa_seed_result> sres(v.seeds ? numRequests : 0);
-    const int rc = v.seeds    ? sa_score_batch_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, sres.data())
+    const int rc = v.seeds && v.width ? sa_score_batch_seeds_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, v.seeds->data(), pairs, n, device, sres.data())
+                   : v.width  ? sa_score_batch_extend_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, pairs, n, device, res.data())
+                   : v.seeds  ? sa_score_batch_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, sres.data())
                    : v.xdrop  ? sa_score_batch_extend(P, v.gapOpen, v.gapExtend, *v.xdrop, pairs, n, device, res.data())
                    : v.lo     ? sa_score_batch_band_at(P, v.gapOpen, v.gapExtend, k.bands.data(), pairs, n, device, res.data())
                    : v.band   ? sa_score_batch_banded(P, v.gapOpen, v.gapExtend, *v.band, pairs, n, device, res.data())
@@ -270,7 +273,9 @@ uint64_t alignRequests(const Variant &v, const Request *requests, Response *resp
     const int64_t n = (int64_t)numRequests;
     std::vector<sa_result> res(numRequests);
     char **at = k.at.data(), **ap = k.ap.data();
-    const int rc = v.seeds   ? sa_align_pairs_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, res.data(), at, ap)
+    const int rc = v.seeds && v.width ? sa_align_pairs_seeds_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, v.seeds->data(), pairs, n, device, res.data(), at, ap)
+                   : v.width ? sa_align_pairs_extend_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, pairs, n, device, res.data(), at, ap)
+                   : v.seeds ? sa_align_pairs_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, res.data(), at, ap)
                    : v.xdrop ? sa_align_pairs_extend(P, v.gapOpen, v.gapExtend, *v.xdrop, pairs, n, device, res.data(), at, ap)
                    : v.lo    ? sa_align_pairs_band_at(P, v.gapOpen, v.gapExtend, k.bands.data(), pairs, n, device, res.data(), at, ap)
                    : v.band  ? sa_align_pairs_banded(P, v.gapOpen, v.gapExtend, *v.band, pairs, n, device, res.data(), at, ap)
@@ -414,6 +419,50 @@ uint64_t SequenceAlignment::alignSequencesGPUSeeds(const Request *requests, Resp
     if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "alignSequencesGPUSeeds", &seeds)) return 1;
     Variant v("alignSequencesGPUSeeds", gapOpen, gapExtend);
     v.xdrop = &xdrop;
+    v.seeds = &seeds;
+    return alignRequests(v, requests, responses, numRequests, device);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUExtendBand(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                        int gapExtend, int xdrop, int width, int *scores)
+{
+    Variant v("scoreSequencesGPUExtendBand", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.width = &width;
+    return scoreRequests(v, requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUExtendBand(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                                        int gapOpen, int gapExtend, int xdrop, int width)
+{
+    Variant v("alignSequencesGPUExtendBand", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.width = &width;
+    return alignRequests(v, requests, responses, numRequests, device);
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUSeedsBand(const Request *requests, uint64_t numRequests, int device, int gapOpen,
+                                                       int gapExtend, int xdrop, int width, const uint64_t *seedTextPos,
+                                                       const uint64_t *seedPatternPos, const uint64_t *seedLength, int *scores)
+{
+    std::vector<sa_seed> seeds;
+    if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "scoreSequencesGPUSeedsBand", &seeds)) return 1;
+    Variant v("scoreSequencesGPUSeedsBand", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.width = &width;
+    v.seeds = &seeds;
+    return scoreRequests(v, requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUSeedsBand(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                                       int gapOpen, int gapExtend, int xdrop, int width, const uint64_t *seedTextPos,
+                                                       const uint64_t *seedPatternPos, const uint64_t *seedLength)
+{
+    std::vector<sa_seed> seeds;
+    if (!seedsOk(seedTextPos, seedPatternPos, seedLength, numRequests, "alignSequencesGPUSeedsBand", &seeds)) return 1;
+    Variant v("alignSequencesGPUSeedsBand", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.width = &width;
     v.seeds = &seeds;
     return alignRequests(v, requests, responses, numRequests, device);
 }

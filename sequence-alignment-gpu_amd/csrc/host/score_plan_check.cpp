@@ -2,7 +2,7 @@
 // GPU, no ROCm: it plans the pair shapes on its command line for a device of a given CU count, under
 // the knobs of its environment, and prints the plan as one JSON object (tests/test_score_plan.py).
 //   sa_score_plan_check --mode global|local|fit|<int> --alphabet A --gap G --cus N [--rows-per-lane R]
-//                       [--gap-extend E] [--band W | --band-at LO:HI] [--extend X|none] [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--gap-extend E] [--band W | --band-at LO:HI] [--extend X|none [--width W]] [--match M --mismatch X] NxM[xCOUNT] ...
 // With --gap-extend the plan is the affine scorer's and --gap is the gap-open penalty. With --band W
 // it is the banded scorer's (sa_hip.h), and the plan also prints band_cells and, for the first 8
 // pairs, "bands": lo, hi, the pair's band cells and the [jmin, jmax, b0, b1] window of every strip at
@@ -15,6 +15,10 @@
 // scorer's (sa_score_batch_seeds) under the xdrop of --extend (none without it): "items" lists the work
 // items, "halves" every pair's [left, right] item (-1: empty), and "order", "num_pairs", "grid", "R" and the
 // bytes are those of the items. With a band of either kind the call is refused as --extend with a band is.
+// With --width W (beside --extend, with or without --seeds) it is the banded extension scorer's or the banded
+// seeds scorer's (sa_score_batch_extend_band, sa_score_batch_seeds_band): the plan prints "width", "band_cells"
+// and "bands" as --band-at does, for the first 8 pairs or, with --seeds, work items, each on the band of the
+// width for its own shape. --band or --band-at beside --extend stays refused, with or without --width.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -40,6 +44,8 @@ int main(int argc, char **argv)
     sa_band at = {0, 0};
     bool extend = false;
     int32_t xdrop = SA_NO_XDROP;
+    bool has_width = false;
+    int32_t width = 0;
     int32_t gap_extend = 0;
     std::vector<sa_pair> pairs;
     std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
@@ -83,6 +89,11 @@ int main(int argc, char **argv)
             extend = true;
             const std::string v = value();
             xdrop = v == "none" ? SA_NO_XDROP : std::atoi(v.c_str());
+        }
+        else if (a == "--width")
+        {
+            has_width = true;
+            width = std::atoi(value());
         }
         else if (a == "--seeds")
         {
@@ -141,6 +152,7 @@ int main(int argc, char **argv)
     if (banded) spec = spec.in_band(band);
     if (band_at) spec = spec.in_bands(bands.data());
     if (extend || !shape_seeds.empty()) spec = spec.extending(xdrop);
+    if (has_width) spec = spec.within(width);
     const int rc = seeded ? make_seeds_score_plan(&P, spec, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &si, &err)
                           : make_score_plan(&P, spec, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err);
     if (rc != SA_OK)
@@ -172,6 +184,26 @@ int main(int argc, char **argv)
         }
         std::printf("], \"halves\": [");
         for (size_t p = 0; p < si.pairs.size() && p < 64; ++p) std::printf("%s[%d, %d]", p ? ", " : "", si.pairs[p].left, si.pairs[p].right);
+        std::printf("]");
+    }
+    if (has_width && !banded && !band_at)
+    {
+        std::printf(", \"width\": %d, \"band_cells\": %llu, \"bands\": [", pl.spec.width, (unsigned long long)pl.band_cells);
+        const size_t count = seeded ? si.items.size() : pairs.size();
+        for (size_t i = 0; i < count && i < 8; ++i)
+        {
+            const int64_t n = seeded ? (int64_t)si.items[i].n : (int64_t)pairs[i].text_len;
+            const int64_t m = seeded ? (int64_t)si.items[i].m : (int64_t)pairs[i].pattern_len, rows = 64 * pl.R;
+            const Band bd = band_ext(n, m, width);
+            std::printf("%s{\"lo\": %d, \"hi\": %d, \"cells\": %llu, \"windows\": [", i ? ", " : "", bd.lo, bd.hi,
+                        (unsigned long long)band_cells((uint64_t)n, (uint64_t)m, bd));
+            for (int64_t s = 0; n && m && s < (m + rows - 1) / rows; ++s)
+            {
+                const BandWindow bw = band_window_at(n, m, rows, s, bd);
+                std::printf("%s[%d, %d, %d, %d]", s ? ", " : "", bw.jmin, bw.jmax, bw.b0, bw.b1);
+            }
+            std::printf("]}");
+        }
         std::printf("]");
     }
     if (banded || band_at)

@@ -2,7 +2,7 @@
 // stand-alone program. No GPU, no ROCm: it plans the pair shapes on its command line and prints the
 // plan as one JSON object (tests/test_trace_plan.py).
 //   sa_trace_plan_check --mode global|local|fit|<int> --alphabet A --gap G --gap-extend E --cus N
-//                       [--budget BYTES] [--band W | --band-at LO:HI] [--extend X|none] [--match M --mismatch X] NxM[xCOUNT] ...
+//                       [--budget BYTES] [--band W | --band-at LO:HI] [--extend X|none [--width W]] [--match M --mismatch X] NxM[xCOUNT] ...
 // --gap is the gap-open penalty. With --band W the plan is the banded aligner's (sa_hip.h): dir_bytes
 // are the band's, "steps" is the sum of the strips' window steps, and each pair also lists the
 // [b0, b1] bodies of its strips' windows (the first 64 strips). With --band-at LO:HI it is the band-at
@@ -13,6 +13,10 @@
 // direction bytes and offsets, "order" the items chunk by chunk ("chunk_begin"), "pair_order" and
 // "pair_chunk_begin" the pairs of each chunk's walk. With a band of either kind the call is refused as
 // --extend with a band is.
+// With --width W (beside --extend, with or without --seeds) it is the banded extension aligner's or the banded
+// seeds aligner's (sa_align_pairs_extend_band, sa_align_pairs_seeds_band): "width" is printed, every pair's or
+// item's dir_bytes are those of the width's band for its shape, and a pair also lists its strips' windows as
+// --band-at does. --band or --band-at beside --extend stays refused, with or without --width.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -38,6 +42,8 @@ int main(int argc, char **argv)
     sa_band at = {0, 0};
     bool extend = false;
     int32_t xdrop = SA_NO_XDROP;
+    bool has_width = false;
+    int32_t width = 0;
     std::vector<sa_pair> pairs;
     std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
     std::vector<size_t> shape_of;      // the shape argument of each pair
@@ -59,6 +65,11 @@ int main(int argc, char **argv)
             extend = true;
             const std::string v = value();
             xdrop = v == "none" ? SA_NO_XDROP : std::atoi(v.c_str());
+        }
+        else if (a == "--width")
+        {
+            has_width = true;
+            width = std::atoi(value());
         }
         else if (a == "--seeds")
         {
@@ -129,7 +140,9 @@ int main(int argc, char **argv)
         std::vector<sa_seed> seeds;
         for (size_t i = 0; i < pairs.size(); ++i) seeds.push_back(shape_seeds[shape_seeds.size() == 1 ? 0 : shape_of[i]]);
         SeedTracePlan sp;
-        const int rc = make_seeds_trace_plan(&P, WaveSpec::gaps(go, ge).extending(xdrop), pairs.data(), seeds.data(), (int64_t)pairs.size(), cus,
+        WaveSpec sspec = WaveSpec::gaps(go, ge).extending(xdrop);
+        if (has_width) sspec = sspec.within(width);
+        const int rc = make_seeds_trace_plan(&P, sspec, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus,
                                              score_knobs(), budget, &sp, &err);
         if (rc != SA_OK)
         {
@@ -138,10 +151,11 @@ int main(int argc, char **argv)
         }
         std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"gap_extend\": %d, \"R\": %d, \"grid\": %d, \"num_pairs\": %lld, \"num_items\": %zu, "
                     "\"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, \"num_chunks\": %lld, "
-                    "\"seeds\": true, \"xdrop\": %d, \"chunk_begin\": [",
+                    "\"seeds\": true, \"xdrop\": %d, \"width\": %d, \"chunk_begin\": [",
                     sp.score.mode, sp.score.A, sp.score.gap, sp.score.spec.gap_extend, sp.score.R, sp.score.grid, (long long)sp.num_pairs,
                     sp.seeds.items.size(), (unsigned long long)sp.budget, (unsigned long long)sp.arena_bytes,
-                    (unsigned long long)sp.total_dir_bytes, (unsigned long long)sp.string_bytes, (long long)sp.num_chunks(), sp.score.spec.xdrop);
+                    (unsigned long long)sp.total_dir_bytes, (unsigned long long)sp.string_bytes, (long long)sp.num_chunks(), sp.score.spec.xdrop,
+                    has_width ? sp.score.spec.width : -1);
         for (size_t i = 0; i < sp.chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)sp.chunk_begin[i]);
         std::printf("], \"pair_chunk_begin\": [");
         for (size_t i = 0; i < sp.pair_chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)sp.pair_chunk_begin[i]);
@@ -172,6 +186,8 @@ int main(int argc, char **argv)
     if (banded) spec = spec.in_band(band);
     if (band_at) spec = spec.in_bands(bands.data());
     if (extend) spec = spec.extending(xdrop);
+    if (has_width) spec = spec.within(width);
+    const bool windows = banded || band_at || has_width;
     const int rc = make_trace_plan(&P, spec, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), budget, &pl, &err);
     if (rc != SA_OK)
     {
@@ -180,10 +196,11 @@ int main(int argc, char **argv)
     }
     std::printf("{\"mode\": %d, \"A\": %d, \"gap\": %d, \"gap_extend\": %d, \"R\": %d, \"grid\": %d, \"num_pairs\": %lld, "
                 "\"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, "
-                "\"num_chunks\": %lld, \"chunk_begin\": [",
+                "\"num_chunks\": %lld, \"width\": %d, \"chunk_begin\": [",
                 pl.score.mode, pl.score.A, pl.score.gap, pl.score.spec.gap_extend, pl.score.R, pl.score.grid,
                 (long long)pl.score.num_pairs, (unsigned long long)pl.budget, (unsigned long long)pl.arena_bytes,
-                (unsigned long long)pl.total_dir_bytes, (unsigned long long)pl.string_bytes, (long long)pl.num_chunks());
+                (unsigned long long)pl.total_dir_bytes, (unsigned long long)pl.string_bytes, (long long)pl.num_chunks(),
+                has_width ? pl.score.spec.width : -1);
     for (size_t i = 0; i < pl.chunk_begin.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)pl.chunk_begin[i]);
     // the lists of a large batch are long: the first 64 entries
     std::printf("], \"order\": [");
@@ -194,12 +211,12 @@ int main(int argc, char **argv)
         const uint64_t strips = pl.dir_bytes[i] ? trace_strips(pairs[i].pattern_len) : 0;
         std::printf("%s{\"strips\": %llu, \"steps\": %llu, \"dir_bytes\": %llu, \"dir_off\": %llu, \"slot_off\": %llu", i ? ", " : "",
                     (unsigned long long)strips,
-                    (unsigned long long)(banded || band_at ? pl.dir_bytes[i] / kTraceStepBytes : pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
+                    (unsigned long long)(windows ? pl.dir_bytes[i] / kTraceStepBytes : pl.dir_bytes[i] ? trace_steps(pairs[i].text_len) : 0),
                     (unsigned long long)pl.dir_bytes[i], (unsigned long long)pl.dir_off[i], (unsigned long long)pl.slot_off[i]);
-        if (banded || band_at)
+        if (windows)
         {
             const int64_t n = (int64_t)pairs[i].text_len, m = (int64_t)pairs[i].pattern_len;
-            const Band bd = band_at ? pl.score.bands[i] : band_of(n, m, band);
+            const Band bd = has_width ? band_ext(n, m, width) : band_at ? pl.score.bands[i] : band_of(n, m, band);
             std::printf(", \"windows\": [");
             for (uint64_t s = 0; s < strips && s < 64; ++s)
             {

@@ -33,7 +33,7 @@ struct WalkArgs {
     const char *alphabet;             // A letters and the gap letter
     sa_result *results;
     int32_t A, mode;                  // mode: one of sa_mode, or SA_ENDS_FREE with its flags
-    int32_t band;                     // the half-width of a banded fill, or -1
+    int32_t band;                     // the half-width of a banded fill, or -1; after a banded extension's fill, its width
     const Band *bands;                // after a band-at fill: every pair's band, clipped; else null
 };
 
@@ -69,7 +69,9 @@ struct WalkArgs {
 // and stepping back pass over it; the walk reads words of in-band interior cells only, whose strips
 // have a window. The argument above holds for any band: on a border the walk only moves where the stop
 // rule has not ended it, that is, along a border that costs, and the planner admits a pair whose
-// in-band cells of such a border reach back to an in-band origin.
+// in-band cells of such a border reach back to an in-band origin. 3 is 2 after a banded extension's fill
+// (sa_align_pairs_extend_band): the band is band_ext(n, m, width), computed as the fill computed it, and holds
+// the origin, where the walk ends.
 template <int BANDED>
 __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
 {
@@ -88,9 +90,10 @@ __global__ __launch_bounds__(64) void walk_affine_kernel(WalkArgs a)
     const bool local = a.mode == SA_LOCAL, fit = a.mode == SA_FIT, ends = BANDED != 1 && (a.mode & SA_ENDS_FREE) != 0;
     const bool tbegin = fit || (ends && (a.mode & SA_FREE_TEXT_BEGIN)), pbegin = ends && (a.mode & SA_FREE_PATTERN_BEGIN);
     const int A = a.A;
-    constexpr bool banded = BANDED != 0, bat = BANDED == 2;
+    constexpr bool banded = BANDED != 0, bat = BANDED >= 2;
     Band bd;
-    if constexpr (bat)
+    if constexpr (BANDED == 3) bd = band_ext(n, m, a.band);
+    else if constexpr (bat)
     {
         bd = a.bands[pi];
         bd = Band{uniform(bd.lo), uniform(bd.hi)};
@@ -227,6 +230,7 @@ struct SeedWalkArgs {
     sa_result *results;
     uint64_t *tail_len;               // per pair: the bytes of the right half's piece, at the end of the slot
     int32_t A;
+    int32_t width;                    // after a banded fill (walk_seeds_kernel<true>): the width of every half's band
 };
 
 // The walk of one work item, walk_affine_kernel<0>'s for an extension: from the fill's result cell to the
@@ -235,8 +239,10 @@ struct SeedWalkArgs {
 // out[-1 - k], backwards from the end of the pair's slot, as every other walk does. LEFT true writes it to
 // out[k]: the left half's matrix is that of the reversed prefixes, so its walk from the end cell to the
 // origin meets the columns of the final alignment in forward order. Returns the number of emissions;
-// *ended is false for a walk that did not reach the origin within n + m moves.
-template <bool LEFT>
+// *ended is false for a walk that did not reach the origin within n + m moves. BANDED (after a seeds fill inside
+// a width) adds walk_affine_kernel<3>'s bookkeeping for the item's band, band_ext of its own shape: the strip
+// whose words are held, its first word and its window's first step, and the end of a walk that leaves the band.
+template <bool LEFT, bool BANDED>
 __device__ __forceinline__ int seed_walk_item(const SeedWalkArgs &a, int item, char *out_t, char *out_p, bool *ended)
 {
     const int lane = threadIdx.x;
@@ -253,6 +259,9 @@ __device__ __forceinline__ int seed_walk_item(const SeedWalkArgs &a, int item, c
     int cur = -1, t0 = 0;
     uint32_t win = 0;
     int ri = 0, rj = 0, rd = 0;
+    const Band bd = band_ext(n, m, BANDED ? a.width : 0);
+    int bstrip = -1, bstep0 = 0, bsteps = INT32_MAX;
+    uint64_t bbase = 0;
     const bool strings = out_t != nullptr;
     auto flush = [&](int base, int count) {
         if (strings && lane < count)
@@ -284,8 +293,19 @@ __device__ __forceinline__ int seed_walk_item(const SeedWalkArgs &a, int item, c
             const int t = j - 1 + l;
             if (col != cur || t0 - t >= 64)
             {
-                const int step = t - lane;
-                win = step >= 0 ? dirs[(uint64_t)(col >> 6) * strip_words + ((uint32_t)step * 64u + (uint32_t)l)] : 0u;
+                const int strip = col >> 6;
+                if (BANDED && strip != bstrip)
+                {
+                    if (bstrip < 0)
+                        for (bstrip = 0; bstrip < strip; ++bstrip) bbase += trace_band_at_strip_words(n, m, bstrip, bd);
+                    for (; bstrip > strip; --bstrip) bbase -= trace_band_at_strip_words(n, m, bstrip - 1, bd);
+                    const BandWindow bw = band_window_at(n, m, (int64_t)kTraceStripRows, strip, bd);
+                    bstep0 = 64 * bw.b0;
+                    bsteps = 64 * (bw.b1 - bw.b0);
+                }
+                const int step = t - lane - bstep0;
+                const uint64_t sbase = BANDED ? bbase : (uint64_t)strip * strip_words;
+                win = step >= 0 && (!BANDED || step < bsteps) ? dirs[sbase + ((uint32_t)step * 64u + (uint32_t)l)] : 0u;
                 cur = col;
                 t0 = t;
             }
@@ -307,6 +327,7 @@ __device__ __forceinline__ int seed_walk_item(const SeedWalkArgs &a, int item, c
         i -= d == kDirDiag || d == kDirTop;
         state = next;
         if ((len & 63) == 0) flush(len - 64, 64);
+        if (BANDED && (uint32_t)(j - i - bd.lo) > (uint32_t)(bd.hi - bd.lo)) break;  // out of band: not ended
     }
     flush(len & ~63, len & 63);
     return len;
@@ -316,6 +337,7 @@ __device__ __forceinline__ int seed_walk_item(const SeedWalkArgs &a, int item, c
 // letters after it, and the right item's walk written backwards from the slot's end. The three lengths
 // sum to at most n + m - L, so the slot of n + m bytes holds the head piece and the tail piece apart; the
 // host joins them (tail_len). The result's score and starts are the combine's.
+template <bool BANDED>
 __global__ __launch_bounds__(64) void walk_seeds_kernel(SeedWalkArgs a)
 {
     const int lane = threadIdx.x;
@@ -330,7 +352,7 @@ __global__ __launch_bounds__(64) void walk_seeds_kernel(SeedWalkArgs a)
     if (left >= 0)
     {
         bool ended;
-        len_l = seed_walk_item<true>(a, left, strings ? a.out_text + slot : nullptr, strings ? a.out_pattern + slot : nullptr, &ended);
+        len_l = seed_walk_item<true, BANDED>(a, left, strings ? a.out_text + slot : nullptr, strings ? a.out_pattern + slot : nullptr, &ended);
         ok = ok && ended;
     }
     if (strings)
@@ -347,7 +369,7 @@ __global__ __launch_bounds__(64) void walk_seeds_kernel(SeedWalkArgs a)
     if (right >= 0)
     {
         bool ended;
-        len_r = seed_walk_item<false>(a, right, strings ? a.out_text + slot_end : nullptr, strings ? a.out_pattern + slot_end : nullptr, &ended);
+        len_r = seed_walk_item<false, BANDED>(a, right, strings ? a.out_text + slot_end : nullptr, strings ? a.out_pattern + slot_end : nullptr, &ended);
         ok = ok && ended;
     }
     if (lane == 0)
@@ -600,7 +622,7 @@ int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_p
         wa.A = r.A;
         // an extension walks as SA_ENDS_FREE with no flag: from the fill's result cell to the origin
         wa.mode = spec.extend ? SA_ENDS_FREE : pl.score.mode;
-        wa.band = spec.banded ? spec.band : -1;
+        wa.band = spec.banded ? spec.band : spec.ext_band ? spec.width : -1;
         wa.bands = d_bands;
         // the chunks differ in their part of the work order
         r.fill = [&](int64_t c) -> int {
@@ -615,7 +637,8 @@ int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_p
         };
         r.walk = [&](int64_t) -> int {
             const dim3 grid((unsigned)fa.sa.s.np);
-            if (wa.bands) hipLaunchKernelGGL(walk_affine_kernel<2>, grid, dim3(64), 0, r.st, wa);
+            if (spec.ext_band) hipLaunchKernelGGL(walk_affine_kernel<3>, grid, dim3(64), 0, r.st, wa);
+            else if (wa.bands) hipLaunchKernelGGL(walk_affine_kernel<2>, grid, dim3(64), 0, r.st, wa);
             else if (wa.band >= 0) hipLaunchKernelGGL(walk_affine_kernel<1>, grid, dim3(64), 0, r.st, wa);
             else hipLaunchKernelGGL(walk_affine_kernel<0>, grid, dim3(64), 0, r.st, wa);
             HIP_TRY(hipGetLastError());
@@ -674,6 +697,22 @@ int sa_align_pairs_seeds(const sa_params *P, int32_t gap_open, int32_t gap_exten
                          char *const *aligned_pattern)
 {
     return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_seeds(seeds), pairs, np, device,
+                            results, aligned_text, aligned_pattern);
+}
+
+int sa_align_pairs_extend_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                               const sa_host_pair *pairs, int64_t np, int device, sa_result *results, char *const *aligned_text,
+                               char *const *aligned_pattern)
+{
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width), pairs, np, device, results,
+                            aligned_text, aligned_pattern);
+}
+
+int sa_align_pairs_seeds_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width, const sa_seed *seeds,
+                              const sa_host_pair *pairs, int64_t np, int device, sa_result *results, char *const *aligned_text,
+                              char *const *aligned_pattern)
+{
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width).from_seeds(seeds), pairs, np, device,
                             results, aligned_text, aligned_pattern);
 }
 
@@ -745,6 +784,7 @@ int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pa
         wa.results = r.d_results;
         wa.tail_len = d_tail;
         wa.A = r.A;
+        wa.width = spec.ext_band ? spec.width : -1;
         // the chunk's items in one traced fill (none: no launch), then the combine and the walk of the chunk's pairs
         r.fill = [&](int64_t c) -> int {
             ScoreArgs &s = fa.sa.s;
@@ -761,7 +801,8 @@ int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pa
             const int64_t pcount = pl.pair_chunk_begin[c + 1] - pl.pair_chunk_begin[c];
             launch_seeds_combine(ca, pcount, r.st);
             HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(walk_seeds_kernel, dim3((unsigned)pcount), dim3(64), 0, r.st, wa);
+            if (spec.ext_band) hipLaunchKernelGGL(walk_seeds_kernel<true>, dim3((unsigned)pcount), dim3(64), 0, r.st, wa);
+            else hipLaunchKernelGGL(walk_seeds_kernel<false>, dim3((unsigned)pcount), dim3(64), 0, r.st, wa);
             HIP_TRY(hipGetLastError());
             return SA_OK;
         };

@@ -207,6 +207,25 @@ int sa_score_batch_seeds(const sa_params *P, int32_t gap_open, int32_t gap_exten
     return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_seeds(seeds), pairs, np, device, out, sa_scorer_fetch_seeds);
 }
 
+int sa_scorer_create_extend_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                                 const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+{
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width), pairs, np, device, out);
+}
+
+int sa_scorer_create_seeds_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                                const sa_seed *seeds, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+{
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width).from_seeds(seeds), pairs, np, device, out);
+}
+
+int sa_score_batch_seeds_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                              const sa_seed *seeds, const sa_host_pair *pairs, int64_t np, int device, sa_seed_result *out)
+{
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width).from_seeds(seeds), pairs, np, device, out,
+                       sa_scorer_fetch_seeds);
+}
+
 int sa_scorer_destroy(sa_scorer *s)
 {
     free_scorer(s);
@@ -331,6 +350,12 @@ int sa_score_batch_extend(const sa_params *P, int32_t gap_open, int32_t gap_exte
                           int64_t np, int device, sa_score_result *out)
 {
     return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop), pairs, np, device, out);
+}
+
+int sa_score_batch_extend_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
+                               const sa_host_pair *pairs, int64_t np, int device, sa_score_result *out)
+{
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width), pairs, np, device, out);
 }
 
 }  // extern "C"

@@ -28,6 +28,10 @@ int score_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 7 : 
 // the affine instances: 61, 84, 118 and 158 VGPRs (local, alphabets up to 4); extension: 59, 79, 114, 154
 int score_affine_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 5 : 8; }
 
+// the banded extension instances (kVarExtendBand, kVarSeedsBand): 69, 91, 125 and 166 VGPRs (alphabets up to 4;
+// 63, 79, 110 and 160 above): one wave per SIMD fewer than the affine class at R = 1
+int score_ext_band_waves_per_simd(int R) { return R >= 8 ? 3 : R >= 4 ? 4 : R >= 2 ? 5 : 7; }
+
 namespace {
 
 int bitlen(uint64_t v)
@@ -106,16 +110,18 @@ int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
         if (P->mode != SA_GLOBAL) return fail(SA_ERR_INVALID, "extension alignment takes mode SA_GLOBAL: its borders are global's");
         if (spec.xdrop < SA_NO_XDROP || spec.xdrop >= (1 << 30)) return fail(SA_ERR_INVALID, "xdrop must be SA_NO_XDROP or 0 .. 2^30 - 1");
         if (spec.banded || spec.band_at) return fail(SA_ERR_UNSUPPORTED, "extension alignment inside a band (band or bands with xdrop) is not built");
+        if (spec.ext_band && spec.width < 0) return fail(SA_ERR_INVALID, "width must be >= 0");
     }
+    else if (spec.ext_band) return fail(SA_ERR_INVALID, "a width takes an extension (xdrop)");
     // gap open == gap extend is the linear recurrence of that penalty: the linear instances, step costs and
     // boundary row, with the penalty in the place of P->gap_penalty
     int64_t g = P->gap_penalty;
-    if (spec.extend && !spec.traced && spec.gap_open == spec.gap_extend)
+    if (spec.extend && !spec.ext_band && !spec.traced && spec.gap_open == spec.gap_extend)  // a banded instance is affine
     {
         g = spec.gap_open;
         affine = false;
     }
-    const bool banded = spec.banded || spec.band_at;
+    const bool banded = spec.banded || spec.band_at || spec.ext_band;
     int R = P->rows_per_lane;
     if (kn.rows_per_lane) R = kn.rows_per_lane;
     if (R == 16 || R == 32) R = 8;  // a params struct shared with a plan: the scorer's tallest strip
@@ -176,6 +182,7 @@ int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
     }
     // a pair's band and the window of one of its strips: band_window_at is band_window on the bands of band_of
     auto pair_band = [&](int64_t p) {
+        if (spec.ext_band) return band_ext((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, spec.width);
         return spec.band_at ? pl.bands[p] : band_of((int64_t)pairs[p].text_len, (int64_t)pairs[p].pattern_len, spec.band);
     };
     pl.key_rowbits = std::max(1, bitlen(lmax + 1));
@@ -263,7 +270,9 @@ int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
 
     // ---- launch and workspace ----
     pl.waves_per_simd = kn.waves_per_simd > 0 ? std::min(kn.waves_per_simd, 8)
-                        : affine ? score_affine_waves_per_simd(pl.R) : score_waves_per_simd(pl.R);
+                        : spec.ext_band ? score_ext_band_waves_per_simd(pl.R)
+                        : affine        ? score_affine_waves_per_simd(pl.R)
+                                        : score_waves_per_simd(pl.R);
     pl.grid = (int)std::min<int64_t>(np, (int64_t)pl.num_cu * 4 * pl.waves_per_simd);
     pl.row_stride = (pl.max_text + 63) / 64 * 64 + 64;
     const uint64_t per_pair = 24 /* descriptor */ + (spec.band_at ? 8 : 0) /* band */ + 4 /* order */ + sizeof(sa_score_result);

@@ -56,6 +56,8 @@ struct WaveSpec {
     const sa_band *bands = nullptr;
     bool extend = false;           // extension alignment (sa_hip.h sa_score_batch_extend) under
     int32_t xdrop = SA_NO_XDROP;   // this X-drop, SA_NO_XDROP for none
+    bool ext_band = false;         // an extension inside |j - i| <= width of its anchor's diagonal (sa_hip.h
+    int32_t width = 0;             // sa_score_batch_extend_band): one half-width per call, both halves of a seed
     bool seeded = false;           // seed extension (sa_hip.h sa_seed, one per pair): an extension to both
     const sa_seed *seeds = nullptr;  // sides of the caller's seeds, planned by the make_seeds_* planners
     bool traced = false;           // the aligners' instances: direction words, affine whatever the penalties
@@ -87,6 +89,13 @@ struct WaveSpec {
         WaveSpec s = *this;
         s.extend = true;
         s.xdrop = x;
+        return s;
+    }
+    WaveSpec within(int32_t w) const
+    {
+        WaveSpec s = *this;
+        s.ext_band = true;
+        s.width = w;
         return s;
     }
     WaveSpec from_seeds(const sa_seed *per_pair) const
@@ -154,6 +163,14 @@ SA_BAND_FN Band band_clip(int64_t n, int64_t m, int64_t lo, int64_t hi)
     const int64_t l = lo < -m ? -m : lo > n ? n : lo, h = hi < -m ? -m : hi > n ? n : hi;
     return Band{(int32_t)l, (int32_t)h};
 }
+// The band of a banded extension (sa_hip.h sa_score_batch_extend_band) of half-width w >= 0 about the
+// diagonal of its anchor, the origin of the extension matrix, clipped as band_clip clips: a wider w
+// admits no further cell. The planner, the kernels and the walks all derive it from (n, m, w); for a
+// seed's half, from the half's own shape.
+SA_BAND_FN Band band_ext(int64_t n, int64_t m, int64_t w)
+{
+    return Band{(int32_t)(w < m ? -w : -m), (int32_t)(w < n ? w : n)};
+}
 // band_window for any lo <= hi. Rows of the strip with an in-band column in 1..n are those from 1 - hi
 // to n - lo; their windows shift right row by row, so the strip's in-band columns run from the first
 // such row's to the last such row's. A strip without one is empty: b0 == b1, jmax < jmin, no body runs
@@ -208,6 +225,11 @@ struct ScorePlan {
 //    (SA_ERR_UNSUPPORTED). Cost, R, grid and bytes are the local program's, the linear one when gap open
 //    equals gap extend (unless `traced`); xdrop changes nothing, the stop rows are not known beforehand. The
 //    limits are the int32 one and the local best-cell key's.
+//  - ext_band (with extend): the banded extension scorer (sa_hip.h sa_score_batch_extend_band). width < 0 is
+//    SA_ERR_INVALID. A pair is planned on band_ext(n, m, width) as a band-at pair is on its band: a strip is
+//    charged its band_window_at steps at the local step cost, the order and padded_cells count band cells, and
+//    kBandScoreLimit applies. The instance is affine whatever the penalties; no bands are kept, the kernel
+//    computes each from the width.
 //  - seeded: SA_ERR_INVALID. Seeds are planned as work items, by make_seeds_score_plan.
 int make_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
                     ScorePlan *out, std::string *err);
@@ -247,5 +269,6 @@ int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
 // instances).
 int score_waves_per_simd(int R);
 int score_affine_waves_per_simd(int R);
+int score_ext_band_waves_per_simd(int R);  // the banded extension and banded seeds instances
 
 }  // namespace sa

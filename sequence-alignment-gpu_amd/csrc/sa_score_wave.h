@@ -17,6 +17,8 @@
 //   kVarAffineExtend   Affine Extend                   global               gap_extend, xdrop
 //   kVarSeeds          Extend Seed                     global               xdrop, items
 //   kVarAffineSeeds    Affine Extend Seed              global               gap_extend, xdrop, items
+//   kVarExtendBand     Affine Band BandAt Extend       global               gap_extend, xdrop, width
+//   kVarSeedsBand      Affine Band BandAt Extend Seed  global               gap_extend, xdrop, width, items
 //
 // Untraced, every row exists at R = 1, 2, 4, 8; with Trace added, the affine rows exist at R = 8. The
 // static_asserts of score_wave are the rule for a legal combination, the table of sa_wave_launch.h is the
@@ -160,7 +162,34 @@
 //    every word: it never reads a word of a strip that did not run.
 //  - xdrop SA_NO_XDROP skips the test: every row counts, as with a drop that no score can reach.
 //
-// SEED (EXT: kVarSeeds, kVarAffineSeeds) is seed extension, sa_hip.h
+// BAND + EXT (AFFINE, BAT: kVarExtendBand, with SEED kVarSeedsBand) is extension alignment inside a width of the
+// anchor's diagonal, sa_hip.h sa_score_batch_extend_band: the band-at program's cells with EXT's result. The
+// band is computed, not loaded: band_ext(n, m, width) of the pair or item the wave drew, from the wave-uniform
+// kernel argument `width`, so lo <= 0 <= hi, the origin is in band, every in-band cell lies on a diagonal that
+// starts in an in-band border cell of the global borders, and BAT's "every in-band cell is a real score" holds
+// with no reachability test. Everything of it is under `if constexpr (BAND && EXT)` or inside BAT's and EXT's
+// own sections; the other instances compile to what they were.
+//  - Cells. BAT's borders ((row, 0) real iff row <= -lo, (0, j) iff j <= hi), band_window_at windows and the
+//    MASK step, on global's recurrence: no clamp.
+//  - Per-row best. best[r] starts at the sentinel, not at INT32_MIN: a masked cell registers the sentinel (it is
+//    `valid`, and never above the start value), a real cell is above -2^29 and always registers, and a row the
+//    window never meets, or a row of a strip without a window, keeps the start value. So after a strip best[r]
+//    is r(row) on the banded matrix, with the sentinel standing for minus infinity.
+//  - Drop test. 0 <= B < 2^29 (kBandScoreLimit) and best[r] >= -2^30, so B - best[r] < 2^31 stays inside int32,
+//    and for a row without an in-band cell it is >= 2^30 > xdrop: the row drops under every xdrop >= 0 by the
+//    test as it stands. lm and pm[] take maxima only. Under SA_NO_XDROP nothing is tested and such a row
+//    holds no candidate, as best[r] > 0 fails.
+//  - Empty strips end the pair. Rows with an in-band column are 1 .. n - lo, a prefix: once a strip's window is
+//    empty every later one is, none holds a candidate, and a finite drop fired at the latest in the first row
+//    past n - lo. The strip loop ends there, before any of the strip's work.
+//  - The row buffer. Strip s + 1 reads only the in-band columns of row 64R (s + 1), which strip s wrote after
+//    reading them (BAT, "Windows" and BAND, "Bottom row"); after a drop or an empty strip the boundary row is
+//    stale and harmless by EXT's "Exit": the wave's next pair starts from the border formulas.
+//  - TRACE. The strips that run store their windows' words one after another (trace_band_at_dir_bytes of the
+//    band sizes the pair); a strip past the stop row or without a window stores none, and the walk, which
+//    starts in a row < i*, steps over strips that ran only.
+//
+// SEED (EXT: kVarSeeds, kVarAffineSeeds, kVarSeedsBand) is seed extension, sa_hip.h
 // sa_score_batch_seeds: the wave draws work items (SeedItem, sa_score_plan.h), a pair's left half or its
 // right half, where the other instances draw pairs, and `order`, `np`, `out` and TRACE's dir_off speak of
 // items. An item is an extension pair whose letter k lies at base[dir * k], base the address of the half's
@@ -249,9 +278,12 @@ constexpr unsigned kVarBandAtLocal = kWaveAffine | kWaveBand | kWaveBandAt;  // 
 constexpr unsigned kVarBandAt = kVarBandAtLocal | kWaveEnds;                 // the global and the fit program
 constexpr unsigned kVarExtend = kWaveExtend, kVarAffineExtend = kWaveAffine | kWaveExtend;
 constexpr unsigned kVarSeeds = kVarExtend | kWaveSeed, kVarAffineSeeds = kVarAffineExtend | kWaveSeed;
+constexpr unsigned kVarExtendBand = kVarAffineExtend | kWaveBand | kWaveBandAt;  // extension inside a width
+constexpr unsigned kVarSeedsBand = kVarExtendBand | kWaveSeed;
 
 // The kernel argument of every instance: the base arguments, then (traced instances) the direction arena,
-// then one int and one pointer whose meaning is the variant's. The static_asserts of score_wave make the
+// then one int and one pointer whose meaning is the variant's, then the width of a banded extension, which has
+// both of those taken (xdrop, and with kWaveSeed items). The static_asserts of score_wave make the
 // union members mutually exclusive; an instance loads only the fields of its flags.
 struct WaveArgs {
     ScoreAffineArgs sa;
@@ -264,6 +296,7 @@ struct WaveArgs {
         const Band *bands;      // kWaveBandAt: per pair, clipped (ScorePlan::bands)
         const SeedItem *items;  // kWaveSeed: a.order, a.np and a.out speak of items, a.pairs is unused
     };
+    int32_t width;  // kWaveExtend with kWaveBandAt: the half-width about the anchor's diagonal
 };
 struct TracedWaveArgs {
     ScoreAffineArgs sa;
@@ -275,13 +308,15 @@ struct TracedWaveArgs {
         const Band *bands;
         const SeedItem *items;
     };
+    int32_t width;
 };
 // the offsets the instances were compiled against before the variants shared one struct
 static_assert(offsetof(WaveArgs, sa.gap_extend) == 88 && offsetof(WaveArgs, band) == 96 && offsetof(WaveArgs, bands) == 104 &&
-                  sizeof(WaveArgs) == 112,
+                  offsetof(WaveArgs, width) == 112 && sizeof(WaveArgs) == 120,
               "untraced kernel arguments: gap_extend, the variant's int, the variant's pointer");
 static_assert(offsetof(TracedWaveArgs, tr.dirs) == 96 && offsetof(TracedWaveArgs, tr.dir_off) == 104 &&
-                  offsetof(TracedWaveArgs, band) == 112 && offsetof(TracedWaveArgs, bands) == 120 && sizeof(TracedWaveArgs) == 128,
+                  offsetof(TracedWaveArgs, band) == 112 && offsetof(TracedWaveArgs, bands) == 120 &&
+                  offsetof(TracedWaveArgs, width) == 128 && sizeof(TracedWaveArgs) == 136,
               "traced kernel arguments: the direction arena before the variant's fields");
 // (through a class template, so that a kernel's mangled name spells F and not the expression on it)
 template <unsigned F>
@@ -295,7 +330,8 @@ using ArgsOf = typename WaveArgsFor<F>::type;
 // sit in registers). The variant's values arrive as function arguments, unpacked by wave_kernel below,
 // its only caller, and not as loads from the argument struct inside the body: the optimizer ranks an
 // argument and a loaded value differently when it orders operands, and one more level of inlining moves
-// code as well; the instances are to stay what they were (profiles/r19/score_disasm_compare.md).
+// code as well; the instances are to stay what they were (profiles/r19/score_disasm_compare.md). A banded
+// extension's width arrives as `band`, which no other band-at instance reads.
 template <int R, int MODE, bool SMALL, unsigned F>
 __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, int32_t *tab, const TraceArgs &tr, int band, int ends,
                                            const Band *bands, int xdrop, const SeedItem *items)
@@ -308,8 +344,9 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
     static_assert(MODE == SA_GLOBAL || MODE == SA_LOCAL || MODE == SA_FIT, "one of the three modes");
     static_assert(!BAND || (AFFINE && (BAT || MODE != SA_FIT)), "banded instances: affine; on the half-width, global or local");
     static_assert(!ENDS || (MODE != SA_LOCAL && (BAT || !BAND)), "ends-free instances: the global or the fit program, no band but the caller's");
-    static_assert(!BAT || (BAND && (ENDS || MODE == SA_LOCAL)), "band-at instances: banded; local, or ends-free (global and fit are two of its flag sets)");
-    static_assert(!EXT || (MODE == SA_GLOBAL && !BAND && !ENDS), "extension instances: the global borders, no band, no free ends");
+    static_assert(!BAT || (BAND && (ENDS || MODE == SA_LOCAL || EXT)),
+                  "band-at instances: banded; local, ends-free (global and fit are two of its flag sets), or an extension inside its width");
+    static_assert(!EXT || (MODE == SA_GLOBAL && (!BAND || BAT) && !ENDS), "extension instances: the global borders, no band but its width's, no free ends");
     static_assert(!SEED || EXT, "seeds instances: extension alignment of a work item");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
     constexpr bool BEST = LOCAL || EXT;  // the result is the best cell: per-row running best and the key
@@ -420,7 +457,14 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
         // BAND: cell (i, j) is in band iff (unsigned)(j - i - blo) <= bspan
         int blo = 0;
         uint32_t bspan = 0;
-        if constexpr (BAT)
+        if constexpr (BAT && EXT)
+        {
+            // the band of the width about the anchor's diagonal, for this pair's or item's shape: wave-uniform
+            const Band bd = band_ext(n, m, band);
+            blo = bd.lo;
+            bspan = (uint32_t)(bd.hi - bd.lo);
+        }
+        else if constexpr (BAT)
         {
             // the caller's band of this pair, clipped by the planner (band_clip): wave-uniform
             const Band bd = bands[pi];
@@ -442,6 +486,10 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
             if constexpr (BAT) bw = band_window_at(n, m, 64 * R, s, Band{blo, blo + (int)bspan});  // may be empty: no body
             else if constexpr (BAND) bw = band_window(n, m, 64 * R, s, Band{blo, blo + (int)bspan});
             const int bfirst = BAND ? bw.b0 : 0, bend = BAND ? bw.b1 : nbodies;
+            if constexpr (BAND && EXT)
+            {
+                if (bfirst == bend) break;  // uniform: no row from here on holds an in-band cell
+            }
             int s0[R], s1[R], s2[R], s3[R];  // S[pattern letter of the row][0..3] (SMALL)
             int prow[R];               // A * pattern letter of the row (LDS table row)
             int el[R];                 // AFFINE: E[row][column - 1]
@@ -485,7 +533,9 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     hl[r] = in ? hl[r] : SENT;
                     el[r] = in ? el[r] : SENT;
                 }
-                best[r] = EXT ? INT32_MIN : 0;  // EXT: below any score, so that after the strip it is r(row)
+                // EXT: below any score, so that after the strip it is r(row); in a band the sentinel, which keeps
+                // the drop test of a row without an in-band cell inside int32
+                best[r] = EXT ? (BAND ? SENT : INT32_MIN) : 0;
                 bestt[r] = 0;
             }
             if constexpr (FIT)
@@ -751,6 +801,7 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
                     for (int r = R - 1; r >= 0; --r)
                     {
                         // |H| < 2^30 and 0 <= B < 2^30 (planner): the difference stays inside int32
+                        // (BAND: B < 2^29 and best[r] >= -2^30, the sentinel of a row without an in-band cell)
                         const bool drop = row1 + r < m && max(before, pm[r]) - best[r] > xdrop;
                         fr = drop ? r : fr;
                     }
@@ -869,8 +920,9 @@ __global__ __launch_bounds__(64) void wave_kernel(ArgsOf<F> w)
     __shared__ int32_t tab[SMALL ? 1 : 32 * 32];
     constexpr bool BAT = (F & kWaveBandAt) != 0;
     const int gap_extend = F & kWaveAffine ? w.sa.gap_extend : 0;
-    const int band = (F & kWaveBand) && !BAT ? w.band : 0, ends = F & kWaveEnds ? w.ends : 0, xdrop = F & kWaveExtend ? w.xdrop : SA_NO_XDROP;
-    const Band *const bands = BAT ? w.bands : nullptr;
+    constexpr bool EXTBAND = BAT && (F & kWaveExtend) != 0;
+    const int band = (F & kWaveBand) && !BAT ? w.band : EXTBAND ? w.width : 0, ends = F & kWaveEnds ? w.ends : 0, xdrop = F & kWaveExtend ? w.xdrop : SA_NO_XDROP;
+    const Band *const bands = BAT && !EXTBAND ? w.bands : nullptr;
     const SeedItem *const items = F & kWaveSeed ? w.items : nullptr;
     if constexpr ((F & kWaveTrace) != 0) score_wave<R, MODE, SMALL, F>(w.sa.s, gap_extend, tab, w.tr, band, ends, bands, xdrop, items);
     else score_wave<R, MODE, SMALL, F>(w.sa.s, gap_extend, tab, TraceArgs(), band, ends, bands, xdrop, items);

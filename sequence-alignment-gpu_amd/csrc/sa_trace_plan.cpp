@@ -49,7 +49,8 @@ int make_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
     for (int64_t p = 0; p < np; ++p)
     {
         const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len;
-        pl.dir_bytes[p] = spec.band_at  ? trace_band_at_dir_bytes(n, m, pl.score.bands[p])
+        pl.dir_bytes[p] = spec.ext_band ? trace_band_at_dir_bytes(n, m, band_ext((int64_t)n, (int64_t)m, spec.width))
+                          : spec.band_at  ? trace_band_at_dir_bytes(n, m, pl.score.bands[p])
                           : spec.banded ? trace_band_dir_bytes(n, m, spec.band)
                                         : trace_dir_bytes(n, m);
         pl.total_dir_bytes += pl.dir_bytes[p];
@@ -100,9 +101,14 @@ int make_seeds_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
     const int64_t ni = (int64_t)items.size();
     pl.dir_bytes.resize((size_t)ni);
     pl.dir_off.resize((size_t)ni);
+    // a half's cells: under a width, those of its own band (band_ext of the half's shape)
+    std::vector<uint64_t> icells((size_t)ni);
     for (int64_t k = 0; k < ni; ++k)
     {
-        pl.dir_bytes[k] = trace_dir_bytes(items[k].n, items[k].m);
+        const uint64_t n = items[k].n, m = items[k].m;
+        const Band bd = band_ext((int64_t)n, (int64_t)m, spec.width);
+        pl.dir_bytes[k] = spec.ext_band ? trace_band_at_dir_bytes(n, m, bd) : trace_dir_bytes(n, m);
+        icells[k] = spec.ext_band ? band_cells(n, m, bd) : n * m;
         pl.total_dir_bytes += pl.dir_bytes[k];
     }
     // per pair: the directions and the cells of both halves, and the string slot
@@ -115,7 +121,7 @@ int make_seeds_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
             if (k >= 0)
             {
                 pbytes[p] += pl.dir_bytes[k];
-                pcells[p] += (uint64_t)items[k].n * items[k].m;
+                pcells[p] += icells[k];
             }
         pl.slot_off[p] = pl.string_bytes;
         pl.string_bytes += pairs[p].text_len + pairs[p].pattern_len;
@@ -133,7 +139,7 @@ int make_seeds_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
     // in the order of their cells
     std::vector<int32_t> &order = pl.score.order;
     order.clear();
-    auto by_cells = [&](int32_t a, int32_t b) { return (uint64_t)items[a].n * items[a].m > (uint64_t)items[b].n * items[b].m; };
+    auto by_cells = [&](int32_t a, int32_t b) { return icells[a] > icells[b]; };
     auto close_chunk = [&]() { std::stable_sort(order.begin() + pl.chunk_begin.back(), order.end(), by_cells); };
     pl.chunk_begin.push_back(0);
     pl.pair_chunk_begin.push_back(0);

@@ -93,6 +93,8 @@ struct TracePlan {
 //    trace_band_at_dir_bytes of the clipped band).
 //  - extend: the extension aligner (sa_hip.h sa_align_pairs_extend; make_score_plan's checks). A pair is
 //    planned with the directions of a global pair: where its fill stops is not known beforehand.
+//  - ext_band (with extend): the banded extension aligner (sa_align_pairs_extend_band): a pair's directions are
+//    trace_band_at_dir_bytes of band_ext(n, m, width), whatever its fill's stop row.
 int make_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
                     uint64_t budget, TracePlan *out, std::string *err);
 
@@ -102,7 +104,8 @@ int make_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pai
 // bytes. The chunks are cut over the pairs, ordered by the cells of both halves together, so that a
 // pair's halves share a chunk: chunk c walks positions pair_chunk_begin[c] .. of pair_order and fills
 // positions chunk_begin[c] .. of score.order, that chunk's items, most cells first. A pair is
-// SA_ERR_UNSUPPORTED only when its two halves together exceed `budget`.
+// SA_ERR_UNSUPPORTED only when its two halves together exceed `budget`. Under a width (spec.ext_band) each half
+// is traced inside band_ext of its own shape: two banded rectangles, and the orders count their band cells.
 struct SeedTracePlan : TracePlan {
     SeedItems seeds;
     std::vector<int32_t> pair_order;

@@ -39,15 +39,17 @@ inline ScoreAffineArgs score_args(const ScorePlan &pl, const void *d_text, const
 }
 
 // What a call launches: the variant's flags (without kWaveTrace), the program, and the int the variant
-// reads from its arguments (the half-width, the SA_FREE_* flags or the xdrop).
+// reads from its arguments (the half-width, the SA_FREE_* flags or the xdrop), and the width of a banded
+// extension, whose int is its xdrop.
 struct WaveChoice {
     unsigned flags;
     int program;
     int32_t value;
+    int32_t width;
 };
 
 // The single mode -> program mapping.
-//  - Extension (and seeds) is the global program.
+//  - Extension (and seeds) is the global program; inside a width it is the affine band-at instance of it.
 //  - Per-pair bands: SA_LOCAL is the local program; every other mode runs as the ends-free mode it equals,
 //    SA_GLOBAL with no flag and SA_FIT with the text's two.
 //  - Ends-free is the fit program when the text's end is free and the global program otherwise.
@@ -57,19 +59,20 @@ struct WaveChoice {
 constexpr WaveChoice wave_choice(const WaveSpec &sp, int mode)
 {
     const unsigned aff = sp.affine ? kWaveAffine : 0u;
-    if (sp.extend) return WaveChoice{aff | kWaveExtend | (sp.seeded ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop};
-    if (sp.band_at && mode == SA_LOCAL) return WaveChoice{kVarBandAtLocal, SA_LOCAL, 0};
+    if (sp.extend && sp.ext_band) return WaveChoice{kVarExtendBand | (sp.seeded ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop, sp.width};
+    if (sp.extend) return WaveChoice{aff | kWaveExtend | (sp.seeded ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop, 0};
+    if (sp.band_at && mode == SA_LOCAL) return WaveChoice{kVarBandAtLocal, SA_LOCAL, 0, 0};
     const int ends = sp.band_at && mode == SA_GLOBAL ? 0
                      : sp.band_at && mode == SA_FIT  ? SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END
                                                      : mode & 15;
-    if (sp.band_at) return WaveChoice{kVarBandAt, ends & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL, ends};
-    if (mode & SA_ENDS_FREE) return WaveChoice{aff | kWaveEnds, ends & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL, ends};
-    if (sp.banded) return WaveChoice{kVarBand, mode, sp.band};
-    return WaveChoice{aff, mode, 0};
+    if (sp.band_at) return WaveChoice{kVarBandAt, ends & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL, ends, 0};
+    if (mode & SA_ENDS_FREE) return WaveChoice{aff | kWaveEnds, ends & SA_FREE_TEXT_END ? SA_FIT : SA_GLOBAL, ends, 0};
+    if (sp.banded) return WaveChoice{kVarBand, mode, sp.band, 0};
+    return WaveChoice{aff, mode, 0, 0};
 }
 
 namespace wave_choice_check {
-constexpr WaveSpec spec(bool affine, bool banded = false, bool band_at = false, bool extend = false, bool seeded = false)
+constexpr WaveSpec spec(bool affine, bool banded = false, bool band_at = false, bool extend = false, bool seeded = false, bool ext_band = false)
 {
     WaveSpec s;
     s.affine = affine;
@@ -79,9 +82,14 @@ constexpr WaveSpec spec(bool affine, bool banded = false, bool band_at = false, 
     s.extend = extend;
     s.xdrop = extend ? 9 : SA_NO_XDROP;
     s.seeded = seeded;
+    s.ext_band = ext_band;
+    s.width = ext_band ? 5 : 0;
     return s;
 }
-constexpr bool is(WaveChoice c, unsigned flags, int program, int value) { return c.flags == flags && c.program == program && c.value == value; }
+constexpr bool is(WaveChoice c, unsigned flags, int program, int value, int width = 0)
+{
+    return c.flags == flags && c.program == program && c.value == value && c.width == width;
+}
 static_assert(is(wave_choice(spec(false), SA_FIT), kVarLinear, SA_FIT, 0), "a plain mode is its own program");
 static_assert(is(wave_choice(spec(true), SA_LOCAL), kVarAffine, SA_LOCAL, 0), "a plain mode is its own program");
 static_assert(is(wave_choice(spec(true, true), SA_LOCAL), kVarBand, SA_LOCAL, 7), "the half-width band keeps the mode");
@@ -96,6 +104,10 @@ static_assert(is(wave_choice(spec(true, false, true), SA_ENDS_FREE | SA_FREE_PAT
 static_assert(is(wave_choice(spec(true, false, true), SA_LOCAL), kVarBandAtLocal, SA_LOCAL, 0), "band-at local: no free ends");
 static_assert(is(wave_choice(spec(false, false, false, true), SA_GLOBAL), kVarExtend, SA_GLOBAL, 9), "extension: the global program");
 static_assert(is(wave_choice(spec(true, false, false, true, true), SA_GLOBAL), kVarAffineSeeds, SA_GLOBAL, 9), "seeds: extension of a work item");
+static_assert(is(wave_choice(spec(true, false, false, true, false, true), SA_GLOBAL), kVarExtendBand, SA_GLOBAL, 9, 5),
+              "extension inside a width: the affine band-at instance of the global program");
+static_assert(is(wave_choice(spec(true, false, false, true, true, true), SA_GLOBAL), kVarSeedsBand, SA_GLOBAL, 9, 5),
+              "seeds inside a width: the same of a work item");
 }  // namespace wave_choice_check
 
 // One row of the table: a variant and the programs it has instances of.
@@ -117,7 +129,9 @@ using WaveTable = std::tuple<
     WaveRow<kVarExtend,       SA_GLOBAL>,                    // xdrop
     WaveRow<kVarAffineExtend, SA_GLOBAL>,                    // xdrop
     WaveRow<kVarSeeds,        SA_GLOBAL>,                    // xdrop, items
-    WaveRow<kVarAffineSeeds,  SA_GLOBAL>>;                   // xdrop, items
+    WaveRow<kVarAffineSeeds,  SA_GLOBAL>,                    // xdrop, items
+    WaveRow<kVarExtendBand,   SA_GLOBAL>,                    // xdrop, width
+    WaveRow<kVarSeedsBand,    SA_GLOBAL>>;                   // xdrop, width, items
 
 template <bool TRACE>
 using WaveArgsT = ArgsOf<TRACE ? kWaveTrace : 0u>;
@@ -162,12 +176,13 @@ bool launch_wave_table(std::tuple<ROWS...> *, const WaveChoice &c, int R, bool s
 }  // namespace detail
 
 // Launches the instance of `c` on `grid` one-wave workgroups; `a` holds everything but the variant's int,
-// which is c.value. R is 1, 2, 4 or 8 (traced: 8 whatever it says), small is A <= 4. False: the table has
+// which is c.value, and the width, which is c.width. R is 1, 2, 4 or 8 (traced: 8 whatever it says), small is A <= 4. False: the table has
 // no such instance and nothing was launched, which is an error of the caller's planner.
 template <bool TRACE>
 bool launch_wave(const WaveChoice &c, int R, bool small, int grid, hipStream_t st, WaveArgsT<TRACE> a)
 {
     a.band = c.value;
+    a.width = c.width;
     return detail::launch_wave_table<TRACE>((WaveTable *)nullptr, c, R, small, grid, st, a);
 }
 

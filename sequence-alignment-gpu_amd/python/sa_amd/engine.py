@@ -43,7 +43,9 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_score_batch_banded", "sa_scorer_create_banded", "sa_align_pairs_banded",
            "sa_score_batch_band_at", "sa_scorer_create_band_at", "sa_align_pairs_band_at", "sa_band_reachable",
            "sa_score_batch_extend", "sa_scorer_create_extend", "sa_align_pairs_extend",
-           "sa_score_batch_seeds", "sa_scorer_create_seeds", "sa_scorer_fetch_seeds", "sa_align_pairs_seeds")
+           "sa_score_batch_seeds", "sa_scorer_create_seeds", "sa_scorer_fetch_seeds", "sa_align_pairs_seeds",
+           "sa_score_batch_extend_band", "sa_scorer_create_extend_band", "sa_align_pairs_extend_band",
+           "sa_score_batch_seeds_band", "sa_scorer_create_seeds_band", "sa_align_pairs_seeds_band")
 
 
 class SaParams(ctypes.Structure):
@@ -156,6 +158,16 @@ def _load():
     L.sa_scorer_fetch_seeds.argtypes = [P, P, P]
     L.sa_align_pairs_seeds.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, ctypes.c_int64, I,
                                        ctypes.POINTER(SaResult), P, P]
+    L.sa_score_batch_extend_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_extend_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                               ctypes.POINTER(P)]
+    L.sa_align_pairs_extend_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, P, ctypes.c_int64, I,
+                                             ctypes.POINTER(SaResult), P, P]
+    L.sa_score_batch_seeds_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, P, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_seeds_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, P, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                              ctypes.POINTER(P)]
+    L.sa_align_pairs_seeds_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, P, P, ctypes.c_int64, I,
+                                            ctypes.POINTER(SaResult), P, P]
     L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
     L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -234,12 +246,13 @@ def _seeds(seeds, num_pairs: int, xdrop, band, bands) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
-def _variant(gap: int, gap_extend, band, bands, xdrop, seeds, num_pairs: int):
+def _variant(gap: int, gap_extend, band, bands, xdrop, seeds, num_pairs: int, width=None):
     """The variant that the keywords of score_batch, Scorer and align_pairs_affine name, resolved once: the
     suffix of the C function (sa_score_batch<suffix>, sa_scorer_create<suffix>, sa_align_pairs<suffix>), the
     arguments that go between params and the pairs, and the array those point into, to keep alive over the
     call. Without `gap_extend` the gap is linear, gap_open = gap_extend = gap; with nothing else either, there
-    is no gap model: the suffix is empty."""
+    is no gap model: the suffix is empty. `width` (an extension's or a seeds call's half-width about the anchor's
+    diagonal) is checked after everything else, so a call that was refused before is refused by the same words."""
     if band is not None and bands is not None:
         raise ValueError("band= and bands= exclude each other")
     if xdrop is not None and (band is not None or bands is not None):
@@ -247,7 +260,15 @@ def _variant(gap: int, gap_extend, band, bands, xdrop, seeds, num_pairs: int):
     ge = gap if gap_extend is None else gap_extend
     if seeds is not None:
         sd = _seeds(seeds, num_pairs, xdrop, band, bands)
+        if width is not None:
+            return "_seeds_band", (gap, ge, xdrop, width, sd.ctypes.data), sd
         return "_seeds", (gap, ge, xdrop, sd.ctypes.data), sd
+    if width is not None:
+        if band is not None or bands is not None:
+            raise ValueError("width= takes neither band= nor bands=: it is the band of an extension (xdrop=), about its anchor's diagonal")
+        if xdrop is None:
+            raise ValueError("width= requires xdrop= (NO_XDROP for none)")
+        return "_extend_band", (gap, ge, xdrop, width), None
     if xdrop is not None:
         return "_extend", (gap, ge, xdrop), None
     if bands is not None:
@@ -354,7 +375,7 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
                        gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None,
-                       bands=None, xdrop: int | None = None, seeds=None) -> list[dict]:
+                       bands=None, xdrop: int | None = None, seeds=None, width: int | None = None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
     ones. With gap_open == gap_extend == g every value is align_pair's for gap g. `mode` may also be FIT
@@ -367,8 +388,11 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
     the origin to the best cell of the rows before the X-drop's stop row; both starts are 0. With `seeds`
     (one (text_pos, pattern_pos, length) per pair; requires `xdrop`, mode SA_GLOBAL, no band),
     sa_align_pairs_seeds: the extension to both sides of each pair's seed joined with the seed's letters;
-    start_text and start_pattern are the 0-based indices of the first aligned letters."""
-    variant = _variant(gap_open, gap_extend, band, bands, xdrop, seeds, len(texts))
+    start_text and start_pattern are the 0-based indices of the first aligned letters. With `width` (>= 0;
+    requires `xdrop`, takes neither `band` nor `bands`), sa_align_pairs_extend_band or, with `seeds`,
+    sa_align_pairs_seeds_band: the same inside |j - i| <= width of each extension's own matrix, with direction
+    bytes for the band only."""
+    variant = _variant(gap_open, gap_extend, band, bands, xdrop, seeds, len(texts), width)
     if gap_extend is None and xdrop is None:  # as ever: without a gap model, align_batch on one device, band or no band
         return align_batch(mode, texts, patterns, S, gap_open, 1, None, strings)
     return _align_host_pairs(mode, texts, patterns, S, gap_open, device, None, strings, variant)
@@ -484,7 +508,7 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                bands=None, xdrop: int | None = None, seeds=None) -> np.ndarray:
+                bands=None, xdrop: int | None = None, seeds=None, width: int | None = None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
     the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
@@ -498,8 +522,11 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     the rows before the X-drop's stop row, anchored at the origin; without `gap_extend` the gap is linear.
     With `seeds` (one (text_pos, pattern_pos, length) per pair; requires `xdrop`, mode SA_GLOBAL, no band),
     sa_score_batch_seeds: the extension to both sides of each pair's seed plus the seed's score, as a
-    SEED_DTYPE array (score, status, begin_text, begin_pattern, end_text, end_pattern)."""
-    suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(texts))
+    SEED_DTYPE array (score, status, begin_text, begin_pattern, end_text, end_pattern). With `width` (>= 0;
+    requires `xdrop`, takes neither `band` nor `bands`), sa_score_batch_extend_band or, with `seeds`,
+    sa_score_batch_seeds_band: the extension inside |j - i| <= width of its own matrix, the same width on both
+    sides of a seed; a width of max(n, m) or more is the unbanded call."""
+    suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(texts), width)
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     hp, ts, ps = _host_pairs(texts, patterns)
     n = len(ts)
@@ -515,12 +542,13 @@ class Scorer:
     `bands`, one (lo, hi) per pair, a band-at scorer (sa_scorer_create_band_at; not with `band`). With
     `xdrop`, an extension scorer (sa_scorer_create_extend; mode SA_GLOBAL, no band). With `seeds` (one
     (text_pos, pattern_pos, length) per pair; requires `xdrop`), a seeds scorer (sa_scorer_create_seeds):
-    results() is then a SEED_DTYPE array. `mode` as score_batch takes it."""
+    results() is then a SEED_DTYPE array. With `width` (requires `xdrop`), the banded extension scorer or seeds
+    scorer (sa_scorer_create_extend_band, sa_scorer_create_seeds_band). `mode` as score_batch takes it."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
                  device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                 bands=None, xdrop: int | None = None, seeds=None):
-        suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(pairs))
+                 bands=None, xdrop: int | None = None, seeds=None, width: int | None = None):
+        suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(pairs), width)
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)

@@ -69,6 +69,17 @@ costs. A second table has each window clipped to the read's span +- 32 letters. 
 end to end on 4000 of the pairs beside the two-call host composition, whose strings it must equal.
 
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+With --mode extend --width W.. the banded extension (sa_hip.h: sa_scorer_create_extend_band,
+sa_align_pairs_extend_band) on the chimeric pairs under --exit-gap, without a drop and at --xdrop: per X, the
+unbanded extension scorer and, per width, the banded extension scorer and the band-at global scorer on {-w, w},
+which covers the same cells; alternated round by round after a warm-up, medians with min and max, the planner's
+step-model ratio beside each measured ratio, and the number of scores that equal the unbanded ones. Then the
+aligners on 64 of the pairs: arena bytes, fill and walk ms of sa_affine_last_stats and end-to-end wall time.
+With --mode seeds --width W.. the banded seeds scorer (sa_scorer_create_seeds_band) on the mapped reads with their
+longest-match seeds beside the unbanded seeds scorer on the whole windows and on the windows clipped to the
+read's span +- 32, the share of equal scores, and sa_align_pairs_seeds_band on 4000 of the reads.
+    python3 tools/score_bench.py --mode extend --width 64 500 --out profiles/r21/score_extend_band_bench.json
+    python3 tools/score_bench.py --mode seeds --width 16 64 --out profiles/r21/score_seeds_band_bench.json
     python3 tools/score_bench.py --mode seeds [--small] --out profiles/r18/score_seeds_bench.json
     python3 tools/score_bench.py --mode extend [--small] --out profiles/r17/score_extend_bench.json
     python3 tools/score_bench.py --mode ends [--small] --out profiles/r15/score_ends_bench.json
@@ -696,6 +707,148 @@ def seeds_aligned_row(args, engine, w, seeds, go: int, ge: int, xdrop) -> dict:
             "seeds_over_composition": round(statistics.median(ms["seeds"]) / statistics.median(ms["composition"]), 4)}
 
 
+def width_model_cost(pairs, width: int, R: int, local: bool) -> int:
+    """The planner's instruction count of a banded pair (sa_score_plan.h: band_ext, band_window_at): the affine
+    step of the local (an extension) or the global program, charged jmax - jmin + 64 times per strip that holds
+    an in-band cell."""
+    step, rows, total = 18 + R * (14 if local else 10), 64 * R, 0
+    for _, n, _, m in pairs:
+        if n == 0 or m == 0:
+            continue
+        lo, hi = max(-width, -m), min(width, n)
+        for first in range(1, m + 1, rows):
+            ia, ib = max(first, 1 - hi), min(m, first + rows - 1, n - lo)
+            if ia <= ib:
+                total += (min(n, ib + hi) - max(1, ia + lo) + 64) * step
+    return total
+
+
+def aligned_stats(engine, call, rounds: int) -> dict:
+    """One aligner call, `rounds` times after a warm-up: wall time end to end and sa_affine_last_stats."""
+    import time
+    wall, fill, walk, st = [], [], [], {}
+    for rnd in range(rounds + 1):
+        t0 = time.perf_counter()
+        got = call()
+        ms = (time.perf_counter() - t0) * 1e3
+        st = engine.affine_last_stats()
+        if rnd:
+            wall.append(ms), fill.append(st["fill_ms"]), walk.append(st["walk_ms"])
+    return {"end_to_end_wall": stats(wall), "fill": stats(fill), "walk": stats(walk), "arena_bytes": st["arena_bytes"],
+            "num_chunks": st["num_chunks"]}, got
+
+
+def extend_band_rows(args, engine, w, dt, dp, go: int, ge: int, xdrop) -> dict:
+    """The unbanded extension scorer, and per width the banded extension scorer and the band-at global scorer
+    on {-w, w}, at one X-drop (None: no drop); alternated."""
+    pairs, cells = w["pairs"], sum(p[1] * p[3] for p in w["pairs"])
+    x = engine.NO_XDROP if xdrop is None else xdrop
+    sc = {"extend": engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, xdrop=x)}
+    for wd in args.width:
+        sc[f"extend_band_{wd}"] = engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, xdrop=x, width=wd)
+        sc[f"band_at_global_{wd}"] = engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, bands=[(-wd, wd)] * len(pairs))
+    row = {"name": w["name"] + ("_xdrop" if xdrop is not None else "_no_xdrop"), "pairs": len(pairs), "cells": cells, "gap_open": go,
+           "gap_extend": ge, "xdrop": xdrop, "widths": list(args.width), "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for _ in range(2):  # warm-up, and the results
+        for k, s in sc.items():
+            s.run(dt.data_ptr(), dp.data_ptr())
+            res[k] = s.results().copy()
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k, s in sc.items():
+            ms[k].append(timed(lambda: s.run(dt.data_ptr(), dp.data_ptr()), lambda: s.results()))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    for k, s in sc.items():
+        row[k + "_run"] = stats(ms[k])
+        s.close()
+    Rf = row["scorers"]["extend"]["rows_per_lane"]
+    full_model = model_cost(pairs, Rf, True, True)
+    for wd in args.width:
+        b, a = f"extend_band_{wd}", f"band_at_global_{wd}"
+        Rb, Ra = row["scorers"][b]["rows_per_lane"], row["scorers"][a]["rows_per_lane"]
+        assert (res[b]["score"] <= res["extend"]["score"]).all() or xdrop is not None, "a banded score exceeds the unbanded one (W3)"
+        row[f"width_{wd}"] = {
+            "band_over_unbanded": round(med[b] / med["extend"], 4),
+            "model_band_over_unbanded": round(width_model_cost(pairs, wd, Rb, True) / full_model, 4),
+            "band_over_band_at_global": round(med[b] / med[a], 4),
+            "model_band_over_band_at_global": round(width_model_cost(pairs, wd, Rb, True) / width_model_cost(pairs, wd, Ra, False), 4),
+            "scores_equal_the_unbanded": int((res[b]["score"] == res["extend"]["score"]).sum()),
+            "cells_equal_the_unbanded": int(((res[b]["score"] == res["extend"]["score"]) & (res[b]["end_text"] == res["extend"]["end_text"]) &
+                                             (res[b]["end_pattern"] == res["extend"]["end_pattern"])).sum())}
+    # aligned: the first pairs end to end, unbanded and at each width
+    nal = min(len(pairs), 16 if args.small else 64)
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in pairs[:nal]]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in pairs[:nal]]
+    rounds = max(3, args.rounds // 2)
+    row["aligned"] = {"pairs": nal}
+    row["aligned"]["unbanded"], full = aligned_stats(engine, lambda: engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, xdrop=x), rounds)
+    for wd in args.width:
+        st, got = aligned_stats(engine, lambda: engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, xdrop=x, width=wd), rounds)
+        assert [g["score"] for g in got] == res[f"extend_band_{wd}"]["score"][:nal].tolist(), "the banded aligner and scorer differ"
+        same = [k for k in range(nal) if got[k]["score"] == full[k]["score"] and got[k]["num_bytes"] == full[k]["num_bytes"]]
+        assert all(got[k] == full[k] for k in same), "equal scores with different strings"
+        st["scores_equal_the_unbanded"] = len(same)
+        row["aligned"][f"width_{wd}"] = st
+    return row
+
+
+def seeds_band_rows(args, engine, w, seeds, wc, seeds_c, gap: int, gap_extend: int, xdrop) -> dict:
+    """The unbanded seeds scorer on the whole windows and on the clipped ones, and per width the banded seeds
+    scorer on the whole windows; alternated."""
+    import torch
+    x = engine.NO_XDROP if xdrop is None else xdrop
+    dev = {k: (torch.from_numpy(v["text"]).cuda(), torch.from_numpy(v["pattern"]).cuda()) for k, v in (("w", w), ("c", wc))}
+    sc = {"seeds": engine.Scorer(0, w["S"], gap, w["pairs"], gap_extend=gap_extend, xdrop=x, seeds=seeds),
+          "seeds_clipped": engine.Scorer(0, w["S"], gap, wc["pairs"], gap_extend=gap_extend, xdrop=x, seeds=seeds_c)}
+    ptr = {"seeds": dev["w"], "seeds_clipped": dev["c"]}
+    for wd in args.width:
+        sc[f"seeds_band_{wd}"] = engine.Scorer(0, w["S"], gap, w["pairs"], gap_extend=gap_extend, xdrop=x, seeds=seeds, width=wd)
+        ptr[f"seeds_band_{wd}"] = dev["w"]
+    run = {k: (lambda k=k: sc[k].run(ptr[k][0].data_ptr(), ptr[k][1].data_ptr())) for k in sc}
+    row = {"name": w["name"] + "_seeds_band" + ("_xdrop" if xdrop is not None else "_no_xdrop"), "pairs": len(w["pairs"]),
+           "cells": sum(p[1] * p[3] for p in w["pairs"]), "clipped_cells": sum(p[1] * p[3] for p in wc["pairs"]), "gap": gap,
+           "gap_extend": gap_extend, "xdrop": xdrop, "widths": list(args.width), "scorers": {k: s.info() for k, s in sc.items()}}
+    res = {}
+    for _ in range(2):
+        for k in sc:
+            run[k]()
+            res[k] = sc[k].results().copy()
+    ms = {k: [] for k in sc}
+    for _ in range(args.rounds):
+        for k in sc:
+            ms[k].append(timed(run[k], lambda: sc[k].results()))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    for k, s in sc.items():
+        row[k + "_run"] = stats(ms[k])
+        s.close()
+    left, right = halves_workloads(w, seeds)
+    items = [(0, n, 0, m) for _, n, _, m in left["pairs"] + right["pairs"]]
+    full_model = model_cost(items, row["scorers"]["seeds"]["rows_per_lane"], True, gap != gap_extend)
+    for wd in args.width:
+        b = f"seeds_band_{wd}"
+        row[f"width_{wd}"] = {
+            "band_over_whole_windows": round(med[b] / med["seeds"], 4),
+            "model_band_over_whole_windows": round(width_model_cost(items, wd, row["scorers"][b]["rows_per_lane"], True) / full_model, 4),
+            "band_over_clipped_windows": round(med[b] / med["seeds_clipped"], 4),
+            "share_of_scores_equal_the_whole_windows": round(float((res[b]["score"] == res["seeds"]["score"]).mean()), 4)}
+    row["share_of_clipped_scores_equal_the_whole_windows"] = round(float((res["seeds_clipped"]["score"] == res["seeds"]["score"]).mean()), 4)
+    # aligned: the first reads end to end
+    nal = min(len(w["pairs"]), 4000)
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in w["pairs"][:nal]]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in w["pairs"][:nal]]
+    sd = seeds[:nal]
+    rounds = max(3, args.rounds // 2)
+    row["aligned"] = {"pairs": nal}
+    row["aligned"]["unbanded"], full = aligned_stats(engine, lambda: engine.align_pairs_affine(0, texts, pats, w["S"], gap, gap_extend, xdrop=x, seeds=sd), rounds)
+    for wd in args.width:
+        st, got = aligned_stats(engine, lambda: engine.align_pairs_affine(0, texts, pats, w["S"], gap, gap_extend, xdrop=x, seeds=sd, width=wd), rounds)
+        assert [g["score"] for g in got] == res[f"seeds_band_{wd}"]["score"][:nal].tolist(), "the banded seeds aligner and scorer differ"
+        st["alignments_equal_the_unbanded"] = sum(a == b for a, b in zip(got, full))
+        row["aligned"][f"width_{wd}"] = st
+    return row
+
+
 def fit_rows(args, engine, w, dt, dp, gap: int, gap_extend) -> dict:
     """The fit, global and local scorers of one gap model on the mapping workload, alternated."""
     cells = sum(p[1] * p[3] for p in w["pairs"])
@@ -881,6 +1034,9 @@ def main() -> int:
                          "against the fit scorer (profiles/r18/score_seeds_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
+    ap.add_argument("--width", type=int, nargs="+", default=None,
+                    help="--mode extend, --mode seeds: the banded extension and the banded seeds functions at these half-widths "
+                         "(profiles/r21/score_extend_band_bench.json, profiles/r21/score_seeds_band_bench.json)")
     ap.add_argument("--tree", default=None,
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
@@ -891,6 +1047,8 @@ def main() -> int:
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
                                                     ("r15", "score_ends_bench.json") if args.mode == "ends" else
                                                     ("r16", "score_mapped_bench.json") if args.mode == "mapped" else
+                                                    ("r21", "score_extend_band_bench.json") if args.mode == "extend" and args.width else
+                                                    ("r21", "score_seeds_band_bench.json") if args.mode == "seeds" and args.width else
                                                     ("r17", "score_extend_bench.json") if args.mode == "extend" else
                                                     ("r18", "score_seeds_bench.json") if args.mode == "seeds" else ("r09", "score_bench.json")))
     if args.tree:
@@ -928,6 +1086,23 @@ def main() -> int:
             report["workloads"].append(row)
             print(json.dumps(row), flush=True)
         del dt, dp
+    elif args.mode == "extend" and args.width:
+        w = chimeric_workload(args.small)
+        dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
+        for xdrop in (None, args.xdrop):
+            row = extend_band_rows(args, engine, w, dt, dp, args.exit_gap[0], args.exit_gap[1], xdrop)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+        del dt, dp
+    elif args.mode == "seeds" and args.width:
+        w = mapped_workload(args.small)
+        ge = args.gap_extend if args.gap_extend is not None else 2
+        seeds, spans = longest_match_seeds(engine, w, args.gap_open, ge)
+        wc, seeds_c = clip_workload(w, seeds, spans)
+        for xdrop in (None, args.xdrop):
+            row = seeds_band_rows(args, engine, w, seeds, wc, seeds_c, args.gap_open, ge, xdrop)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
     elif args.mode == "extend":
         w = mapping_workload(args.small)
         dt, dp = torch.from_numpy(w["text"]).cuda(), torch.from_numpy(w["pattern"]).cuda()
