@@ -242,6 +242,23 @@ uint64_t alignSequencesGPUSeedsBand(const Request *requests, Response *responses
                                     int gapOpen, int gapExtend, int xdrop, int width, const uint64_t *seedTextPos,
                                     const uint64_t *seedPatternPos, const uint64_t *seedLength);
 
+/// Extension: chained seeds (sa_score_batch_chains, sa_align_pairs_chains; sa_hip.h has the definition). Request k
+/// carries seedCount[k] >= 1 seeds, colinear and without overlap, in the order of the sequences; the seeds of all
+/// requests lie one request after another in seedTextPos, seedPatternPos and seedLength, as the ...Seeds functions
+/// carry one each. Between two consecutive seeds the rectangle they enclose is aligned globally, before the first
+/// and after the last seed the sequences are extended under xdrop (-1, SA_NO_XDROP, never stops), and the seeds'
+/// letters are scored as they are. The score is the sum of all pieces; Response::startInAlignedText and
+/// startInAlignedPattern are the 0-based indices of the first aligned letters, and the aligned strings are the
+/// pieces in forward order. Request::alignmentType and Request::gapPenalty are ignored; one alphabet and score
+/// matrix for all requests. A chain that is empty, out of order or outside its request fails the whole call.
+/// Returns 0, or 1 with the message on stdout.
+uint64_t scoreSequencesGPUChains(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                 int xdrop, const uint64_t *seedCount, const uint64_t *seedTextPos,
+                                 const uint64_t *seedPatternPos, const uint64_t *seedLength, int *scores);
+uint64_t alignSequencesGPUChains(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                 int gapOpen, int gapExtend, int xdrop, const uint64_t *seedCount,
+                                 const uint64_t *seedTextPos, const uint64_t *seedPatternPos, const uint64_t *seedLength);
+
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);
 void traceBackSW(const char *, const uint64_t, const uint64_t, const uint64_t, const Request &, Response *);

@@ -563,9 +563,73 @@ int sa_align_pairs_seeds_band(const sa_params *params, int32_t gap_open, int32_t
                               const sa_seed *seeds, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
                               char *const *aligned_text, char *const *aligned_pattern);
 
+/* ---- chained seeds: gap fills between the seeds of a chain, extensions at its two ends ----------- */
+
+/* Pair k, text t of n letters and pattern p of m letters, owns the seeds seeds[chain_off[k] .. chain_off[k + 1])
+ * of one flat sa_seed array; chain_off has num_pairs + 1 entries, chain_off[0] == 0, and is non-decreasing. A
+ * pair's seeds {ts_i, ps_i, L_i}, i = 0 .. c - 1, c >= 1, are colinear and do not overlap:
+ * ts_i + L_i <= ts_(i+1), ps_i + L_i <= ps_(i+1), ts_(c-1) + L_(c-1) <= n and ps_(c-1) + L_(c-1) <= m. L_i = 0 is
+ * allowed, and a seed's letters need not match: they are scored as they are. The chain says where the path is,
+ * so only the rectangle two consecutive seeds enclose is filled between them, and only the two ends extend.
+ *   left end:  the seeds functions' left half for seed 0: extension of reverse(t[: ts_0]) against
+ *              reverse(p[: ps_0]) under gap_open, gap_extend and xdrop
+ *   right end: the seeds functions' right half for seed c - 1
+ *   gap i:     i = 0 .. c - 2, the SA_GLOBAL alignment, as sa_align_pairs_affine defines it (score, walk and
+ *              tie rules), of t[ts_i + L_i : ts_(i+1)] against p[ps_i + L_i : ps_(i+1)]. Both sides empty:
+ *              score 0, no columns. One side empty, k letters on the other: one gap run, score
+ *              -(gap_open + (k - 1) gap_extend), k columns. xdrop does not apply to gaps
+ *   seed i:    the sum over q < L_i of S[p[ps_i + q]][t[ts_i + q]], L_i columns
+ *   result:    an sa_seed_result. score is the sum of all pieces; begin_text = ts_0 - left.end_text,
+ *              begin_pattern = ps_0 - left.end_pattern; end_text = ts_(c-1) + L_(c-1) + right.end_text,
+ *              end_pattern = ps_(c-1) + L_(c-1) + right.end_pattern
+ *   strings:   reverse(left.aligned) + seed_0 + gap_0 + seed_1 + ... + seed_(c-1) + right.aligned, on both
+ *              sides. In sa_result start_text = begin_text, start_pattern = begin_pattern and
+ *              num_alignment_bytes is the sum of the piece lengths
+ * Identities: (C1) every output equals this composition, built from sa_align_pairs_extend on host-sliced and
+ * host-reversed ends and sa_align_pairs_affine in SA_GLOBAL mode on host-sliced gaps. (C2) A chain of one seed
+ * gives every output of the seeds function. (C3) Cutting a seed {ts, ps, L} into {ts, ps, a} and
+ * {ts + a, ps + a, L - a} changes no output: the gap between them is empty. (C4) Mirror: reversing both
+ * sequences and the chain (seed i becomes {n - ts_i - L_i, m - ps_i - L_i, L_i}, the order reversed) gives the
+ * same score, begin' = (n - end_text, m - end_pattern) and end' = (n - begin_text, m - begin_pattern), exactly,
+ * under 0 <= gap_extend <= gap_open (otherwise a gap run along a rectangle's border costs its closed form while
+ * one inside it may open anew cell by cell, and the reversed rectangle may score differently).
+ * The ends mirror exactly, ties included, as (S3) has it. A gap's string is that of the global aligner on the
+ * reversed rectangle, and the global walk's tie rules are not symmetric (between a diagonal and a gap of equal
+ * score it prefers the gap, between E and F it prefers E, and it meets them from the far corner), so among
+ * equally good gap alignments the mirrored call may pick another one: the identity holds for scores and
+ * intervals, and for the strings only in that every gap's string is the global aligner's on its reversed
+ * rectangle. (C5) gap_open == gap_extend runs the linear kernels for every piece and gives the linear
+ * recurrence's outputs.
+ * Refusals: SA_ERR_INVALID, sa_last_error() naming the pair and (where one is at fault) the seed's index in
+ * its chain, for seeds or chain_off NULL with num_pairs > 0, chain_off[0] != 0, chain_off decreasing, a pair
+ * with no seed, a seed out of range, and a seed out of order or overlapping the one before it. The mode and
+ * xdrop rules are the seeds functions'. A byte outside the alphabet that any piece reads is SA_ERR_INVALID:
+ * seed letters and gap letters always, the letters of an end only where its X-drop let the fill reach them.
+ * The score limit and the best-cell key limit are checked on the whole pair's (n, m), as for seeds. There is
+ * no band: the functions take no width, and sa_search*, the plans, sa_align_pair, sa_align_batch, the
+ * multi-GPU path and the CLI take no chains.
+ * A chains scorer runs two fills on the caller's stream, one of the gap pieces and one of the ends, each with
+ * the rows per lane and the grid that suit its own items (gaps are many and small, ends few and larger), then
+ * one combine. It works with sa_scorer_run, _info, _fetch, _fetch_seeds and _destroy as a seeds scorer does;
+ * sa_scorer_info reports the larger grid and the rows per lane of the launch with more cells. Its device
+ * memory is that of the two launches plus the work items, the seeds and a record per pair.
+ * sa_align_pairs_chains keeps direction bytes for the pieces only, each gap rectangle and each end as a global
+ * pair of its shape, never for n x m, and keeps a pair's pieces in one chunk: a read whose full directions exceed
+ * SA_TRACE_ARENA_BYTES many times over aligns, and a pair is SA_ERR_UNSUPPORTED only when its pieces together
+ * exceed it. Every piece is walked at once, a wave each, into a part of the pair's n + m string bytes of its own,
+ * and one wave per pair then joins the pieces with the seeds' letters in place. sa_affine_last_stats reports the
+ * call: the two fills as the fill, the combine, the walks and the join as the walk. */
+int sa_score_batch_chains(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                          const uint64_t *chain_off, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_seed_result *out);
+int sa_scorer_create_chains(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                            const uint64_t *chain_off, const sa_pair *pairs, int64_t num_pairs, int device, sa_scorer **out);
+int sa_align_pairs_chains(const sa_params *params, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds,
+                          const uint64_t *chain_off, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
+                          char *const *aligned_text, char *const *aligned_pattern);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
  * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend, sa_align_pairs_seeds,
- * sa_align_pairs_extend_band, sa_align_pairs_seeds_band or sa_search_affine (k > 0): device
+ * sa_align_pairs_extend_band, sa_align_pairs_seeds_band, sa_align_pairs_chains or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

@@ -196,6 +196,7 @@ struct Variant {
     const int *xdrop = nullptr;       // extension: the mode is SA_GLOBAL, whose borders an extension has, whatever alignmentType says
     const std::vector<sa_seed> *seeds = nullptr;  // with xdrop: the ...Seeds functions
     const int *width = nullptr;       // with xdrop: the ...ExtendBand and ...SeedsBand functions
+    const std::vector<uint64_t> *chainOff = nullptr;  // with xdrop and seeds: the ...Chains functions, request k's seeds are [chainOff[k], chainOff[k + 1])
     explicit Variant(const char *n) : name(n), affine(false), gapOpen(0), gapExtend(0) {}
     Variant(const char *n, int open, int extend) : name(n), affine(true), gapOpen(open), gapExtend(extend) {}
 };
@@ -249,7 +250,8 @@ uint64_t scoreRequests(const Variant &v, const Request *requests, uint64_t numRe
     const int64_t n = (int64_t)numRequests;
     std::vector<sa_score_result> res(numRequests);
     std::vector<sa_seed_result> sres(v.seeds ? numRequests : 0);
-    const int rc = v.seeds && v.width ? sa_score_batch_seeds_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, v.seeds->data(), pairs, n, device, sres.data())
+    const int rc = v.chainOff ? sa_score_batch_chains(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), v.chainOff->data(), pairs, n, device, sres.data())
+                   : v.seeds && v.width ? sa_score_batch_seeds_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, v.seeds->data(), pairs, n, device, sres.data())
                    : v.width  ? sa_score_batch_extend_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, pairs, n, device, res.data())
                    : v.seeds  ? sa_score_batch_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, sres.data())
                    : v.xdrop  ? sa_score_batch_extend(P, v.gapOpen, v.gapExtend, *v.xdrop, pairs, n, device, res.data())
@@ -273,7 +275,8 @@ uint64_t alignRequests(const Variant &v, const Request *requests, Response *resp
     const int64_t n = (int64_t)numRequests;
     std::vector<sa_result> res(numRequests);
     char **at = k.at.data(), **ap = k.ap.data();
-    const int rc = v.seeds && v.width ? sa_align_pairs_seeds_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, v.seeds->data(), pairs, n, device, res.data(), at, ap)
+    const int rc = v.chainOff ? sa_align_pairs_chains(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), v.chainOff->data(), pairs, n, device, res.data(), at, ap)
+                   : v.seeds && v.width ? sa_align_pairs_seeds_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, v.seeds->data(), pairs, n, device, res.data(), at, ap)
                    : v.width ? sa_align_pairs_extend_band(P, v.gapOpen, v.gapExtend, *v.xdrop, *v.width, pairs, n, device, res.data(), at, ap)
                    : v.seeds ? sa_align_pairs_seeds(P, v.gapOpen, v.gapExtend, *v.xdrop, v.seeds->data(), pairs, n, device, res.data(), at, ap)
                    : v.xdrop ? sa_align_pairs_extend(P, v.gapOpen, v.gapExtend, *v.xdrop, pairs, n, device, res.data(), at, ap)
@@ -396,6 +399,50 @@ uint64_t SequenceAlignment::alignSequencesGPUExtend(const Request *requests, Res
 {
     Variant v("alignSequencesGPUExtend", gapOpen, gapExtend);
     v.xdrop = &xdrop;
+    return alignRequests(v, requests, responses, numRequests, device);
+}
+
+// the chains of the ...Chains functions: a count per request and three flat arrays over all requests' seeds
+bool chainsOk(const uint64_t *count, const uint64_t *textPos, const uint64_t *patternPos, const uint64_t *length, uint64_t numRequests,
+              const char *name, std::vector<sa_seed> *seeds, std::vector<uint64_t> *off)
+{
+    off->assign(1, 0);
+    for (uint64_t i = 0; count && i < numRequests; ++i) off->push_back(off->back() + count[i]);
+    if (numRequests && (!count || (off->back() && (!textPos || !patternPos || !length))))
+    {
+        std::cout << "error: " << name << " needs seedCount, one entry per request, and seedTextPos, seedPatternPos and seedLength, one entry per seed\n";
+        return false;
+    }
+    for (uint64_t i = 0; i < off->back(); ++i) seeds->push_back(sa_seed{textPos[i], patternPos[i], length[i]});
+    seeds->push_back(sa_seed{0, 0, 0});  // a call without a seed still passes an address: the library names the request
+    return true;
+}
+
+uint64_t SequenceAlignment::scoreSequencesGPUChains(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
+                                                    int xdrop, const uint64_t *seedCount, const uint64_t *seedTextPos,
+                                                    const uint64_t *seedPatternPos, const uint64_t *seedLength, int *scores)
+{
+    std::vector<sa_seed> seeds;
+    std::vector<uint64_t> off;
+    if (!chainsOk(seedCount, seedTextPos, seedPatternPos, seedLength, numRequests, "scoreSequencesGPUChains", &seeds, &off)) return 1;
+    Variant v("scoreSequencesGPUChains", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.seeds = &seeds;
+    v.chainOff = &off;
+    return scoreRequests(v, requests, numRequests, device, scores);
+}
+
+uint64_t SequenceAlignment::alignSequencesGPUChains(const Request *requests, Response *responses, uint64_t numRequests, int device,
+                                                    int gapOpen, int gapExtend, int xdrop, const uint64_t *seedCount,
+                                                    const uint64_t *seedTextPos, const uint64_t *seedPatternPos, const uint64_t *seedLength)
+{
+    std::vector<sa_seed> seeds;
+    std::vector<uint64_t> off;
+    if (!chainsOk(seedCount, seedTextPos, seedPatternPos, seedLength, numRequests, "alignSequencesGPUChains", &seeds, &off)) return 1;
+    Variant v("alignSequencesGPUChains", gapOpen, gapExtend);
+    v.xdrop = &xdrop;
+    v.seeds = &seeds;
+    v.chainOff = &off;
     return alignRequests(v, requests, responses, numRequests, device);
 }
 

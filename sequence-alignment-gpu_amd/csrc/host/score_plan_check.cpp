@@ -19,6 +19,11 @@
 // seeds scorer's (sa_score_batch_extend_band, sa_score_batch_seeds_band): the plan prints "width", "band_cells"
 // and "bands" as --band-at does, for the first 8 pairs or, with --seeds, work items, each on the band of the
 // width for its own shape. --band or --band-at beside --extend stays refused, with or without --width.
+// With --chain TS:PS:L,TS:PS:L,... (once for all pairs, or once per shape argument; csrc/host/chain_args.h) it is the
+// chains scorer's (sa_score_batch_chains) under the xdrop of --extend: the program prints the two launches' plans as
+// "ends_plan" and "gaps_plan" (R, grid, num_items, the gap model, row_stride, cost, order), the work items as "ends"
+// and "gaps" as --seeds prints its items, every pair's record under "chains", and the bytes. A band of either kind
+// or a width beside it is refused. --chain-off is for the refusals.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -28,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "chain_args.h"
 #include "sa_score_plan.h"
 
 using namespace sa;
@@ -50,6 +56,7 @@ int main(int argc, char **argv)
     std::vector<sa_pair> pairs;
     std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
     std::vector<size_t> shape_of;      // the shape argument of each pair
+    ChainArgs chain;                   // --chain, --chain-off
     size_t num_shapes = 0;
     for (int i = 1; i < argc; ++i)
     {
@@ -105,6 +112,15 @@ int main(int argc, char **argv)
             }
             shape_seeds.push_back(sa_seed{ts, ps, len});
         }
+        else if (a == "--chain")
+        {
+            if (!chain.parse_chain(value()))
+            {
+                std::fprintf(stderr, "sa_score_plan_check: --chain takes TS:PS:L,TS:PS:L,...\n");
+                return 2;
+            }
+        }
+        else if (a == "--chain-off") chain.parse_off(value());
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--rows-per-lane") P.rows_per_lane = std::atoi(value());
         else if (a == "--match") match = std::atoi(value());
@@ -153,6 +169,37 @@ int main(int argc, char **argv)
     if (band_at) spec = spec.in_bands(bands.data());
     if (extend || !shape_seeds.empty()) spec = spec.extending(xdrop);
     if (has_width) spec = spec.within(width);
+    if (chain.given())
+    {
+        if (!chain.resolve(shape_of, num_shapes))
+        {
+            std::fprintf(stderr, "sa_score_plan_check: --chain once, or once per shape\n");
+            return 2;
+        }
+        ChainsScorePlan cp;
+        const int rc = make_chains_score_plan(&P, spec.extending(xdrop).from_chains(chain.seeds_ptr(), chain.off_ptr()), pairs.data(),
+                                              (int64_t)pairs.size(), cus, score_knobs(), &cp, &err);
+        if (rc != SA_OK)
+        {
+            std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+            return 0;
+        }
+        std::printf("{\"chains_call\": true, \"xdrop\": %d, \"input_bytes\": %llu, \"device_bytes\": %llu", cp.ends.spec.xdrop,
+                    (unsigned long long)cp.ends.input_bytes, (unsigned long long)cp.device_bytes);
+        for (const ScorePlan *l : {&cp.ends, &cp.gaps})
+        {
+            std::printf(", \"%s_plan\": {\"R\": %d, \"grid\": %d, \"num_items\": %lld, \"affine\": %s, \"gap\": %d, \"gap_extend\": %d, \"extend\": %s, "
+                        "\"max_text\": %llu, \"row_stride\": %llu, \"cost\": [%llu, %llu, %llu, %llu]",
+                        l == &cp.ends ? "ends" : "gaps", l->R, l->grid, (long long)l->num_pairs, l->spec.affine ? "true" : "false", l->gap,
+                        l->spec.gap_extend, l->spec.extend ? "true" : "false", (unsigned long long)l->max_text, (unsigned long long)l->row_stride,
+                        (unsigned long long)l->cost[0], (unsigned long long)l->cost[1], (unsigned long long)l->cost[2], (unsigned long long)l->cost[3]);
+            print_order("order", l->order);
+            std::printf("}");
+        }
+        print_chain_items(cp.items);
+        std::printf("}\n");
+        return 0;
+    }
     const int rc = seeded ? make_seeds_score_plan(&P, spec, pairs.data(), seeds.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &si, &err)
                           : make_score_plan(&P, spec, pairs.data(), (int64_t)pairs.size(), cus, score_knobs(), &pl, &err);
     if (rc != SA_OK)

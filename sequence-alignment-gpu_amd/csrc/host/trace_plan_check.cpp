@@ -17,6 +17,10 @@
 // seeds aligner's (sa_align_pairs_extend_band, sa_align_pairs_seeds_band): "width" is printed, every pair's or
 // item's dir_bytes are those of the width's band for its shape, and a pair also lists its strips' windows as
 // --band-at does. --band or --band-at beside --extend stays refused, with or without --width.
+// With --chain TS:PS:L,TS:PS:L,... (once for all pairs, or once per shape argument; csrc/host/chain_args.h) it is the
+// chains aligner's (sa_align_pairs_chains): "ends" and "gaps" list the work items of the two traced fills with their
+// direction bytes and offsets, "order" and "gap_order" the items chunk by chunk ("chunk_begin", "gap_chunk_begin"),
+// "pair_order" and "pair_chunk_begin" the pairs of each chunk, "chains" every pair's record and "slots" its slot.
 // NxM is text length x pattern length; the matrix is M on the diagonal and X elsewhere (5 / -4).
 // A planning error prints {"error": code, "message": text}.
 #include <algorithm>
@@ -26,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "chain_args.h"
 #include "sa_trace_plan.h"
 
 using namespace sa;
@@ -47,6 +52,7 @@ int main(int argc, char **argv)
     std::vector<sa_pair> pairs;
     std::vector<sa_seed> shape_seeds;  // --seeds: one per shape argument, or one for all
     std::vector<size_t> shape_of;      // the shape argument of each pair
+    ChainArgs chain;                   // --chain, --chain-off
     size_t num_shapes = 0;
     for (int i = 1; i < argc; ++i)
     {
@@ -81,6 +87,15 @@ int main(int argc, char **argv)
             }
             shape_seeds.push_back(sa_seed{ts, ps, len});
         }
+        else if (a == "--chain")
+        {
+            if (!chain.parse_chain(value()))
+            {
+                std::fprintf(stderr, "sa_trace_plan_check: --chain takes TS:PS:L,TS:PS:L,...\n");
+                return 2;
+            }
+        }
+        else if (a == "--chain-off") chain.parse_off(value());
         else if (a == "--cus") cus = std::atoi(value());
         else if (a == "--budget") budget = std::strtoull(value(), nullptr, 10);
         else if (a == "--band")
@@ -129,6 +144,49 @@ int main(int argc, char **argv)
     P.score_matrix = S.data();
 
     std::string err;
+    if (chain.given())
+    {
+        if (!chain.resolve(shape_of, num_shapes))
+        {
+            std::fprintf(stderr, "sa_trace_plan_check: --chain once, or once per shape\n");
+            return 2;
+        }
+        ChainTracePlan cp;
+        WaveSpec cspec = WaveSpec::gaps(go, ge);
+        const std::vector<sa_band> cbands(std::max<size_t>(pairs.size(), 1), at);
+        if (banded) cspec = cspec.in_band(band);
+        if (band_at) cspec = cspec.in_bands(cbands.data());
+        cspec = cspec.extending(xdrop);
+        if (has_width) cspec = cspec.within(width);
+        const int rc = make_chains_trace_plan(&P, cspec.from_chains(chain.seeds_ptr(), chain.off_ptr()), pairs.data(), (int64_t)pairs.size(), cus,
+                                              score_knobs(), budget, &cp, &err);
+        if (rc != SA_OK)
+        {
+            std::printf("{\"error\": %d, \"message\": \"%s\"}\n", rc, err.c_str());
+            return 0;
+        }
+        std::printf("{\"chains_call\": true, \"xdrop\": %d, \"R\": %d, \"gap_R\": %d, \"grid\": %d, \"gap_grid\": %d, \"affine\": %s, \"gap_affine\": %s, "
+                    "\"num_pairs\": %lld, \"budget\": %llu, \"arena_bytes\": %llu, \"total_dir_bytes\": %llu, \"string_bytes\": %llu, \"num_chunks\": %lld",
+                    cp.score.spec.xdrop, cp.score.R, cp.gaps.R, cp.score.grid, cp.gaps.grid, cp.score.spec.affine ? "true" : "false",
+                    cp.gaps.spec.affine ? "true" : "false", (long long)cp.num_pairs, (unsigned long long)cp.budget, (unsigned long long)cp.arena_bytes,
+                    (unsigned long long)cp.total_dir_bytes, (unsigned long long)cp.string_bytes, (long long)cp.num_chunks());
+        auto list = [](const char *name, const std::vector<int64_t> &v) {
+            std::printf(", \"%s\": [", name);
+            for (size_t i = 0; i < v.size(); ++i) std::printf("%s%lld", i ? ", " : "", (long long)v[i]);
+            std::printf("]");
+        };
+        list("chunk_begin", cp.chunk_begin);
+        list("gap_chunk_begin", cp.gap_chunk_begin);
+        list("pair_chunk_begin", cp.pair_chunk_begin);
+        print_order("order", cp.score.order);
+        print_order("gap_order", cp.gaps.order);
+        print_order("pair_order", cp.pair_order);
+        print_chain_items(cp.items, &cp.dir_bytes, &cp.dir_off, &cp.gap_dir_bytes, &cp.gap_dir_off);
+        std::printf(", \"slots\": [");
+        for (size_t p = 0; p < cp.slot_off.size() && p < 64; ++p) std::printf("%s%llu", p ? ", " : "", (unsigned long long)cp.slot_off[p]);
+        std::printf("]}\n");
+        return 0;
+    }
     // --seeds: the seeds aligner; with a band of either kind the call is the extension aligner's, refused as it is
     if (!shape_seeds.empty() && !banded && !band_at)
     {

@@ -34,9 +34,33 @@ struct SeedsCombineArgs {
 };
 void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream);
 
+// Chained seeds (sa_hip.h sa_score_batch_chains): chains_combine_kernel (sa_score.hip), one wave per pair after
+// the two fills, shared by the chains scorer and the chains aligner. It sums the substitution scores of all the
+// pair's seed columns and the scores of its gap items, adds the closed-form gaps, flags a seed letter outside the
+// alphabet in ctrl[1] and writes the pair's sa_seed_result from these and its two end items.
+struct ChainsCombineArgs {
+    const int8_t *text, *pattern;
+    const ChainPair *pairs;
+    const ChainSeed *seeds;
+    const int32_t *order;              // workgroup w combines pair order[w]; null: pair w
+    const int32_t *table;              // A x A scores, [pattern][text]
+    const sa_score_result *end_out;    // the extension fill's result of every end item
+    const sa_score_result *gap_out;    // the global fill's result of every gap item
+    sa_seed_result *out;
+    uint32_t *ctrl;
+    int32_t A;
+};
+void launch_chains_combine(const ChainsCombineArgs &a, int64_t np, void *stream);
+
 // sa_align_pairs_seeds on device arenas: the traced fill of the work items, the combine and the seeded walk,
 // chunk by chunk (sa_trace_plan.h SeedTracePlan); arguments as align_affine_device, the seeds are spec.seeds.
 int align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
+
+// sa_align_pairs_chains on device arenas: per chunk (sa_trace_plan.h ChainTracePlan) the traced fills of the gap
+// items and of the end items, the combine, the walk of every item at once and the join of the pairs; arguments as
+// align_affine_device, the chains are spec.seeds and spec.chain_off.
+int align_chains_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
 
 }  // namespace sa

@@ -386,6 +386,195 @@ __global__ __launch_bounds__(64) void walk_seeds_kernel(SeedWalkArgs a)
     }
 }
 
+// Chained seeds (sa_hip.h sa_align_pairs_chains). Every item of a chunk is walked at once, one wave per item:
+// workgroups 0 .. num_ends - 1 walk the end items, the rest the gap items, all through seed_walk_item. A gap
+// item's walk is the global walk: its fill wrote the end cell (m, n), and from there row 0 forces LEFT and column 0
+// TOP down to the origin. A pair's slot of n + m bytes is cut into sub-slots: the piece that covers the text from
+// ta to tb and the pattern from pa to pb has bytes slot + ta + pa .. slot + tb + pb - 1, at least as many as it can
+// have columns, apart from and in the order of every other piece's. The left end writes forwards from the start
+// of its sub-slot (the slot's), every other walk backwards from the end of its own; *_len takes the piece's
+// length, -1 for a walk that did not end.
+struct ChainWalkArgs {
+    SeedWalkArgs w;                   // what seed_walk_item takes, with the end items, their scores and their dir_off
+    const SeedItem *gap_items;        // the same three of the gap items
+    const sa_score_result *gap_scores;
+    const uint64_t *gap_dir_off;
+    const ChainPair *pairs;
+    const int32_t *end_order, *gap_order;  // the chunk's parts of the two work orders
+    const uint64_t *slot_off;         // num_pairs + 1 entries
+    int32_t *end_len, *gap_len;       // per end item, per gap item
+    int32_t num_ends;                 // of the chunk
+};
+
+__global__ __launch_bounds__(64) void walk_chain_items_kernel(ChainWalkArgs a)
+{
+    const int lane = threadIdx.x;
+    const int b = (int)blockIdx.x;
+    const bool is_end = b < a.num_ends;  // wave-uniform
+    SeedWalkArgs wa = a.w;
+    wa.items = is_end ? a.w.items : a.gap_items;
+    wa.scores = is_end ? a.w.scores : a.gap_scores;
+    wa.dir_off = is_end ? a.w.dir_off : a.gap_dir_off;
+    const int item = uniform(is_end ? a.end_order[b] : a.gap_order[b - a.num_ends]);
+    const SeedItem sd = wa.items[item];
+    const int pi = uniform(sd.pair);
+    const ChainPair cp = a.pairs[pi];
+    const bool strings = wa.out_text != nullptr;
+    const bool left = uniform(sd.dir) < 0;
+    // the first byte of a left end's sub-slot, one past the last byte of any other piece's
+    uint64_t at = uniform64(a.slot_off[pi]);
+    if (!left) at += (uniform64(sd.text_off) - uniform64(cp.text_base)) + (uniform64(sd.pattern_off) - uniform64(cp.pattern_base)) + sd.n + sd.m;
+    char *const ot = strings ? wa.out_text + at : nullptr, *const op = strings ? wa.out_pattern + at : nullptr;
+    bool ended;
+    const int len = left ? seed_walk_item<true, false>(wa, item, ot, op, &ended) : seed_walk_item<false, false>(wa, item, ot, op, &ended);
+    if (lane == 0) (is_end ? a.end_len : a.gap_len)[item] = ended ? len : -1;
+}
+
+struct ChainJoinArgs {
+    const int8_t *text, *pattern;
+    const ChainPair *pairs;
+    const ChainSeed *seeds;
+    const int32_t *order;             // the chunk's part of the pair order
+    const sa_seed_result *seed_out;   // the combine's result of every pair
+    const int32_t *end_len, *gap_len; // the walks' piece lengths
+    const uint64_t *slot_off;         // num_pairs + 1 entries
+    char *out_text, *out_pattern;     // both null: results only
+    const char *alphabet;
+    sa_result *results;
+    uint64_t *tail_len;               // per pair: 0, the joined string starts at the start of the slot
+    int32_t A;
+};
+
+// One wave per pair, after the walks. The pair's pieces in the order of the strings are the left end, then seed
+// and gap in turn, then the right end: 2 c + 1 of them for c seeds. 64 pieces at a time, lane l takes piece
+// base + l: its length (an end's or a gap item's from its walk, a seed's L, an empty-side gap's k), where its
+// bytes lie (a walked piece: in its sub-slot; a seed or an empty-side gap run: nowhere yet, they are made from the
+// input letters here) and, by a prefix sum over the wave, where they go. The pieces are then placed one after
+// another, each by all lanes in 64-byte steps, ascending. A piece's destination is at or left of its source and
+// ends at or left of the next piece's source (the sub-slots are in order and as long as their pieces), so a step
+// reads only bytes that no step before it wrote, and a step's 64 loads are complete before its stores.
+__global__ __launch_bounds__(64) void chain_join_kernel(ChainJoinArgs a)
+{
+    const int lane = threadIdx.x;
+    const int pi = uniform(a.order[blockIdx.x]);
+    const ChainPair cp = a.pairs[pi];
+    const uint64_t slot = uniform64(a.slot_off[pi]), slot_end = uniform64(a.slot_off[pi + 1]);
+    const uint64_t tbase = uniform64(cp.text_base), pbase = uniform64(cp.pattern_base);
+    const int sbegin = uniform(cp.seed_begin), c = uniform(cp.seed_end) - sbegin;
+    const int left = uniform(cp.left), right = uniform(cp.right);
+    const int npieces = 2 * c + 1;
+    const bool strings = a.out_text != nullptr;
+    const int A = a.A;
+    enum { kMove = 0, kSeed = 1, kTextRun = 2, kPatternRun = 3 };
+    auto bcast64 = [](uint64_t v, int l) {
+        return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32);
+    };
+    uint64_t total = 0;
+    bool ok = true;
+    for (int base = 0; base < npieces; base += kWave)
+    {
+        const int j = base + lane;
+        int len = 0, kind = kMove;
+        uint64_t src = 0, toff = 0, poff = 0;  // kMove: the piece's first byte; else the arena offsets of its letters
+        if (j == 0)
+        {
+            len = left >= 0 ? a.end_len[left] : 0;
+            src = slot;
+        }
+        else if (j == npieces - 1)
+        {
+            len = right >= 0 ? a.end_len[right] : 0;
+            src = slot_end - (uint64_t)max(len, 0);
+        }
+        else if (j < npieces)
+        {
+            const int i = (j - 1) >> 1;
+            const ChainSeed sd = a.seeds[sbegin + i];
+            if (j & 1)
+            {
+                kind = kSeed;
+                len = (int)sd.len;
+                toff = sd.text_off;
+                poff = sd.pattern_off;
+            }
+            else
+            {
+                const ChainSeed nx = a.seeds[sbegin + i + 1];
+                if (sd.gap >= 0)
+                {
+                    len = a.gap_len[sd.gap];
+                    src = slot + (nx.text_off - tbase) + (nx.pattern_off - pbase) - (uint64_t)max(len, 0);
+                }
+                else
+                {
+                    // an empty side: one run of the other side's letters against gap letters
+                    toff = sd.text_off + sd.len;
+                    poff = sd.pattern_off + sd.len;
+                    const uint64_t gn = nx.text_off - toff, gm = nx.pattern_off - poff;
+                    kind = gn ? kTextRun : kPatternRun;
+                    len = (int)(gn + gm);
+                }
+            }
+        }
+        ok = ok && len >= 0;
+        len = max(len, 0);
+        const int incl = wave_prefix_sum(len);
+        const uint64_t dst = slot + total + (uint64_t)(incl - len);
+        const int count = min(kWave, npieces - base);
+        for (int q = 0; strings && q < count; ++q)
+        {
+            const int qlen = __builtin_amdgcn_readlane(len, q), qkind = __builtin_amdgcn_readlane(kind, q);
+            if (qlen == 0) continue;
+            const uint64_t qdst = bcast64(dst, q);
+            if (qkind == kMove)
+            {
+                const uint64_t qsrc = bcast64(src, q);
+                if (qsrc == qdst) continue;
+                for (int off = lane; off - lane < qlen; off += kWave)
+                {
+                    char ct = 0, cq = 0;
+                    if (off < qlen)
+                    {
+                        ct = a.out_text[qsrc + off];
+                        cq = a.out_pattern[qsrc + off];
+                    }
+                    if (off < qlen)
+                    {
+                        a.out_text[qdst + off] = ct;
+                        a.out_pattern[qdst + off] = cq;
+                    }
+                }
+            }
+            else
+            {
+                const int8_t *const ts = a.text + bcast64(toff, q);
+                const int8_t *const ps = a.pattern + bcast64(poff, q);
+                for (int off = lane; off < qlen; off += kWave)
+                {
+                    const int ct = qkind == kPatternRun ? A : min(max((int)ts[off], 0), A - 1);
+                    const int cq = qkind == kTextRun ? A : min(max((int)ps[off], 0), A - 1);
+                    a.out_text[qdst + off] = a.alphabet[ct];
+                    a.out_pattern[qdst + off] = a.alphabet[cq];
+                }
+            }
+        }
+        total += (uint64_t)__builtin_amdgcn_readlane(incl, kWave - 1);
+    }
+    const bool all_ok = ballot(!ok) == 0;
+    if (lane == 0)
+    {
+        const sa_seed_result so = a.seed_out[pi];
+        sa_result r;
+        r.score = so.score;
+        r.status = all_ok ? SA_OK : SA_ERR_HIP;
+        r.num_alignment_bytes = total;
+        r.start_text = so.begin_text;
+        r.start_pattern = so.begin_pattern;
+        a.results[pi] = r;
+        a.tail_len[pi] = 0;
+    }
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -503,7 +692,7 @@ int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
         ev.push_back(one);
     }
     HIP_TRY(hipMemsetAsync(r.d_ctrl, 0, 256, st));
-    uint32_t ctrl[2] = {0, 0};
+    uint32_t ctrl[4] = {0, 0, 0, 0};  // [2] and [3]: the work counter and the bad-input flag of a chains call's gap fill
     std::vector<uint64_t> tail((size_t)np, UINT64_MAX);
     // everything enqueued on the stream, up to its synchronise; a failure on the way must not leave
     // copies into `results`, `ctrl` and `tail` pending when this function returns
@@ -536,7 +725,7 @@ int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
         g_stats.fill_ms += f;
         g_stats.walk_ms += w;
     }
-    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+    if (ctrl[1] || ctrl[3]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
     for (int64_t p = 0; p < np; ++p)
         if (c.results[p].status != SA_OK)
             return fail(SA_ERR_HIP, std::string(c.walk) + " of pair " + std::to_string(p) + " did not end within " + c.moves);
@@ -571,6 +760,7 @@ int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
 int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
                             const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
 {
+    if (spec.chained) return align_chains_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern);
     if (spec.seeded) return align_seeds_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern);
     TracePlan pl;
     TracedWaveArgs fa = {};
@@ -655,7 +845,7 @@ int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_p
 static int align_host_pairs(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
                             char *const *aligned_text, char *const *aligned_pattern)
 {
-    const char *const fn = spec.seeded ? "sa_align_pairs_seeds" : "sa_align_pairs_affine";
+    const char *const fn = spec.chained ? "sa_align_pairs_chains" : spec.seeded ? "sa_align_pairs_seeds" : "sa_align_pairs_affine";
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, std::string(fn) + ": null argument");
     HostArenas in;
@@ -713,6 +903,14 @@ int sa_align_pairs_seeds_band(const sa_params *P, int32_t gap_open, int32_t gap_
                               char *const *aligned_pattern)
 {
     return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).within(width).from_seeds(seeds), pairs, np, device,
+                            results, aligned_text, aligned_pattern);
+}
+
+int sa_align_pairs_chains(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds, const uint64_t *chain_off,
+                          const sa_host_pair *pairs, int64_t np, int device, sa_result *results, char *const *aligned_text,
+                          char *const *aligned_pattern)
+{
+    return align_host_pairs(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_chains(seeds, chain_off), pairs, np, device,
                             results, aligned_text, aligned_pattern);
 }
 
@@ -809,6 +1007,139 @@ int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pa
         return SA_OK;
     };
     return traced_run({"seeds aligner", "seeded walk", "its halves' moves", P, pairs, np, device, d_text, d_pattern, results, aligned_text,
+                       aligned_pattern},
+                      pl, plan, setup);
+}
+
+int sa::align_chains_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
+                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+{
+    ChainTracePlan pl;
+    TracedWaveArgs fe = {}, fg = {};  // the fill of the end items and of the gap items
+    ChainsCombineArgs ca;
+    ChainWalkArgs wa = {};
+    ChainJoinArgs ja;
+    WaveChoice echoice = {}, gchoice = {};
+    int32_t *d_eorder, *d_gorder, *d_pair_order;
+    auto plan = [&](std::string *err) {
+        return make_chains_trace_plan(P, spec, pairs, np, device_cus(device), score_knobs(), trace_arena_budget(), &pl, err);
+    };
+    auto setup = [&](TracedRun &r) -> int {
+        const size_t ne = pl.items.ends.size(), ng = pl.items.gaps.size();
+        std::vector<uint64_t> edir(ne), gdir(ng), slots(pl.slot_off);
+        for (size_t k = 0; k < ne; ++k) edir[k] = pl.dir_off[k] / 4;
+        for (size_t k = 0; k < ng; ++k) gdir[k] = pl.gap_dir_off[k] / 4;
+        slots.push_back(pl.string_bytes);
+        SeedItem *d_ends, *d_gaps;
+        ChainPair *d_pairs;
+        ChainSeed *d_seeds;
+        sa_score_result *d_escores, *d_gscores;
+        sa_seed_result *d_seed_out;
+        uint64_t *d_edir, *d_gdir, *d_slot_off, *d_tail;
+        int32_t *d_grows, *d_elen, *d_glen;
+        int rc;
+        if ((rc = r.ws.upload(&d_ends, pl.items.ends)) || (rc = r.ws.upload(&d_gaps, pl.items.gaps)) || (rc = r.ws.upload(&d_pairs, pl.items.pairs)) ||
+            (rc = r.ws.upload(&d_seeds, pl.items.seeds)) || (rc = r.ws.upload(&d_eorder, pl.score.order)) || (rc = r.ws.upload(&d_gorder, pl.gaps.order)) ||
+            (rc = r.ws.upload(&d_pair_order, pl.pair_order)) || (rc = r.ws.alloc(&d_escores, ne * sizeof(sa_score_result))) ||
+            (rc = r.ws.alloc(&d_gscores, ng * sizeof(sa_score_result))) || (rc = r.ws.alloc(&d_seed_out, (size_t)np * sizeof(sa_seed_result))) ||
+            (rc = r.ws.upload(&d_edir, edir)) || (rc = r.ws.upload(&d_gdir, gdir)) || (rc = r.ws.upload(&d_slot_off, slots)) ||
+            (rc = r.ws.alloc(&d_tail, (size_t)np * 8)) || (rc = r.ws.alloc(&d_grows, (size_t)pl.gaps.grid * pl.gaps.row_stride * 8)) ||
+            (rc = r.ws.alloc(&d_elen, ne * 4)) || (rc = r.ws.alloc(&d_glen, ng * 4)))
+            return rc;
+        r.d_tail = d_tail;
+        fe.sa = score_args(pl.score, d_text, d_pattern, nullptr, d_eorder, 0, r.d_table, r.d_rows, d_escores, r.d_ctrl);
+        fe.tr.dirs = r.d_dirs;
+        fe.tr.dir_off = d_edir;
+        fe.items = d_ends;
+        echoice = wave_choice(pl.score.spec, pl.score.mode);
+        fg.sa = score_args(pl.gaps, d_text, d_pattern, nullptr, d_gorder, 0, r.d_table, d_grows, d_gscores, r.d_ctrl + 2);
+        fg.tr.dirs = r.d_dirs;
+        fg.tr.dir_off = d_gdir;
+        fg.items = d_gaps;
+        gchoice = wave_choice(pl.gaps.spec, pl.gaps.mode);
+        ca.text = fe.sa.s.text;
+        ca.pattern = fe.sa.s.pattern;
+        ca.pairs = d_pairs;
+        ca.seeds = d_seeds;
+        ca.table = r.d_table;
+        ca.end_out = d_escores;
+        ca.gap_out = d_gscores;
+        ca.out = d_seed_out;
+        ca.ctrl = r.d_ctrl;
+        ca.A = r.A;
+        wa.w.text = fe.sa.s.text;
+        wa.w.pattern = fe.sa.s.pattern;
+        wa.w.dirs = r.d_dirs;
+        wa.w.out_text = r.d_ot;
+        wa.w.out_pattern = r.d_op;
+        wa.w.alphabet = r.d_alpha;
+        wa.w.A = r.A;
+        wa.w.width = -1;
+        wa.w.items = d_ends;
+        wa.w.scores = d_escores;
+        wa.w.dir_off = d_edir;
+        wa.gap_items = d_gaps;
+        wa.gap_scores = d_gscores;
+        wa.gap_dir_off = d_gdir;
+        wa.pairs = d_pairs;
+        wa.slot_off = d_slot_off;
+        wa.end_len = d_elen;
+        wa.gap_len = d_glen;
+        ja.text = fe.sa.s.text;
+        ja.pattern = fe.sa.s.pattern;
+        ja.pairs = d_pairs;
+        ja.seeds = d_seeds;
+        ja.seed_out = d_seed_out;
+        ja.end_len = d_elen;
+        ja.gap_len = d_glen;
+        ja.slot_off = d_slot_off;
+        ja.out_text = r.d_ot;
+        ja.out_pattern = r.d_op;
+        ja.alphabet = r.d_alpha;
+        ja.results = r.d_results;
+        ja.tail_len = d_tail;
+        ja.A = r.A;
+        // the chunk's gap items and end items in a traced fill each (none: no launch), then the combine of the chunk's
+        // pairs, the walk of all its items and the join of its pairs
+        r.fill = [&](int64_t c) -> int {
+            ScoreArgs &e = fe.sa.s, &g = fg.sa.s;
+            e.order = wa.end_order = d_eorder + pl.chunk_begin[c];
+            e.np = wa.num_ends = (int32_t)(pl.chunk_begin[c + 1] - pl.chunk_begin[c]);
+            g.order = wa.gap_order = d_gorder + pl.gap_chunk_begin[c];
+            g.np = (int32_t)(pl.gap_chunk_begin[c + 1] - pl.gap_chunk_begin[c]);
+            ja.order = ca.order = d_pair_order + pl.pair_chunk_begin[c];
+            if (g.np)
+            {
+                HIP_TRY(hipMemsetAsync(r.d_ctrl + 2, 0, 4, r.st));  // the gap fill's work counter; its bad-input flag stays
+                if (!launch_wave<true>(gchoice, kTraceRows, r.A <= 4, (int)std::min<int64_t>(g.np, pl.gaps.grid), r.st, fg))
+                    return fail(SA_ERR_UNSUPPORTED, "chains aligner: the gap items' variant has no kernel instance");
+                HIP_TRY(hipGetLastError());
+            }
+            if (e.np)
+            {
+                if (!launch_wave<true>(echoice, kTraceRows, r.A <= 4, (int)std::min<int64_t>(e.np, pl.score.grid), r.st, fe))
+                    return fail(SA_ERR_UNSUPPORTED, "chains aligner: the end items' variant has no kernel instance");
+                HIP_TRY(hipGetLastError());
+            }
+            return SA_OK;
+        };
+        r.walk = [&](int64_t c) -> int {
+            const int64_t pcount = pl.pair_chunk_begin[c + 1] - pl.pair_chunk_begin[c];
+            const int64_t icount = (int64_t)fe.sa.s.np + fg.sa.s.np;
+            launch_chains_combine(ca, pcount, r.st);
+            HIP_TRY(hipGetLastError());
+            if (icount)
+            {
+                hipLaunchKernelGGL(walk_chain_items_kernel, dim3((unsigned)icount), dim3(64), 0, r.st, wa);
+                HIP_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(chain_join_kernel, dim3((unsigned)pcount), dim3(64), 0, r.st, ja);
+            HIP_TRY(hipGetLastError());
+            return SA_OK;
+        };
+        return SA_OK;
+    };
+    return traced_run({"chains aligner", "chained walk", "its pieces' moves", P, pairs, np, device, d_text, d_pattern, results, aligned_text,
                        aligned_pattern},
                       pl, plan, setup);
 }

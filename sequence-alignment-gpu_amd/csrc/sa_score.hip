@@ -2,7 +2,7 @@
 // the cell it is read from, without direction planes, strip descriptors, records or a traceback.
 // The kernels are the untraced instances of wave_kernel<R, MODE, SMALL, F>, the one wave program of
 // sa_score_wave.h, launched through the table of sa_wave_launch.h; here are the combine kernel of the
-// seeds scorer and the host side. What a scorer runs is decided in sa_score_plan.cpp (host-only, no HIP).
+// seeds scorer, that of the chains scorer and the host side. What a scorer runs is decided in sa_score_plan.cpp (host-only, no HIP).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -63,6 +63,64 @@ void launch_seeds_combine(const SeedsCombineArgs &a, int64_t np, void *stream)
     hipLaunchKernelGGL(seeds_combine_kernel, dim3((unsigned)np), dim3(64), 0, (hipStream_t)stream, a);
 }
 
+// One wave per pair, after the fills of the end items and of the gap items (sa_hip.h sa_score_batch_chains). The
+// pair's seeds lie one after another in `seeds`: 64 at a time, a lane sums the columns of its own seed when that
+// is shorter than a wave, and the seeds of 64 letters or more are then summed one by one by all lanes in a
+// strided loop (a ballot names them), so neither a long chain nor a long seed is serial. The gap items' scores
+// are a strided sum as well; one prefix sum over the wave adds both, and lane 0 adds the closed-form gaps and the
+// two end items (an empty end: 0 at (0, 0)).
+__global__ __launch_bounds__(64) void chains_combine_kernel(ChainsCombineArgs a)
+{
+    const int lane = threadIdx.x;
+    const int p = a.order ? uniform(a.order[blockIdx.x]) : (int)blockIdx.x;
+    const ChainPair cp = a.pairs[p];
+    const int A = a.A;
+    const int sbegin = uniform(cp.seed_begin), send = uniform(cp.seed_end), gbegin = uniform(cp.gap_begin), gend = uniform(cp.gap_end);
+    int sum = 0;
+    bool bad = false;
+    auto column = [&](const ChainSeed &sd, uint64_t q) {
+        const int ct = a.text[sd.text_off + q], cq = a.pattern[sd.pattern_off + q];
+        bad = bad || ct < 0 || ct >= A || cq < 0 || cq >= A;
+        sum += a.table[min(max(cq, 0), A - 1) * A + min(max(ct, 0), A - 1)];
+    };
+    for (int base = sbegin; base < send; base += kWave)
+    {
+        ChainSeed mine = {0, 0, 0, -1, 0};
+        if (base + lane < send) mine = a.seeds[base + lane];
+        const bool wide = mine.len >= (uint64_t)kWave;
+        if (!wide)
+            for (uint64_t q = 0; q < mine.len; ++q) column(mine, q);
+        for (uint64_t w = ballot(wide); w; w &= w - 1)
+        {
+            const ChainSeed sd = a.seeds[base + __builtin_ctzll(w)];  // wave-uniform
+            const uint64_t len = uniform64(sd.len);
+            for (uint64_t q = (uint64_t)lane; q < len; q += kWave) column(sd, q);
+        }
+    }
+    for (int k = gbegin + lane; k < gend; k += kWave) sum += a.gap_out[k].score;
+    sum = __builtin_amdgcn_readlane(wave_prefix_sum(sum), kWave - 1);
+    if (bad) __hip_atomic_store(&a.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0)
+    {
+        sa_score_result l = {0, SA_OK, 0, 0}, r = {0, SA_OK, 0, 0};
+        if (cp.left >= 0) l = a.end_out[cp.left];
+        if (cp.right >= 0) r = a.end_out[cp.right];
+        sa_seed_result o;
+        o.score = l.score + sum + cp.closed_score + r.score;
+        o.status = SA_OK;
+        o.begin_text = cp.ts - l.end_text;
+        o.begin_pattern = cp.ps - l.end_pattern;
+        o.end_text = cp.te + r.end_text;
+        o.end_pattern = cp.pe + r.end_pattern;
+        a.out[p] = o;
+    }
+}
+
+void launch_chains_combine(const ChainsCombineArgs &a, int64_t np, void *stream)
+{
+    hipLaunchKernelGGL(chains_combine_kernel, dim3((unsigned)np), dim3(64), 0, (hipStream_t)stream, a);
+}
+
 }  // namespace sa
 
 // ==================================================================================================
@@ -83,6 +141,15 @@ struct sa_scorer : ScorePlan {
     SeedItem *d_items = nullptr;
     SeedPair *d_seed_pairs = nullptr;
     sa_seed_result *d_seed_out = nullptr;
+    // chains scorer (spec.chained, with spec.seeded): the plan and the buffers above are the end items'; the gap
+    // items have a plan, a work order, boundary rows and results of their own, and their launch counts its work
+    // and flags its bad letters in d_ctrl[2] and d_ctrl[3]
+    ScorePlan gaps;
+    int32_t *d_gap_order = nullptr, *d_gap_rows = nullptr;
+    SeedItem *d_gap_items = nullptr;
+    sa_score_result *d_gap_out = nullptr;
+    ChainPair *d_chain_pairs = nullptr;
+    ChainSeed *d_chain_seeds = nullptr;
 };
 
 namespace {
@@ -91,7 +158,8 @@ void free_scorer(sa_scorer *s)
 {
     if (!s) return;
     DeviceGuard dg(s->device);
-    void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl, s->d_bands, s->d_items, s->d_seed_pairs, s->d_seed_out};
+    void *bufs[] = {s->d_pairs, s->d_order, s->d_table, s->d_rows, s->d_out, s->d_ctrl, s->d_bands, s->d_items, s->d_seed_pairs, s->d_seed_out,
+                    s->d_gap_order, s->d_gap_rows, s->d_gap_items, s->d_gap_out, s->d_chain_pairs, s->d_chain_seeds};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -100,10 +168,14 @@ void free_scorer(sa_scorer *s)
 }  // namespace
 
 // every sa_scorer_create*: `spec` is the variant the function stands for. A seeded spec plans the work items
-// (num_pairs, order and d_out are then theirs) and keeps the pairs' seeds and results beside them
+// (num_pairs, order and d_out are then theirs) and keeps the pairs' seeds and results beside them; a chained
+// spec plans the end items so and the gap items beside them
 static int create_scorer(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
-    if (!out) return fail(SA_ERR_INVALID, spec.seeded ? "sa_scorer_create_seeds: null argument" : "sa_scorer_create: null argument");
+    if (!out)
+        return fail(SA_ERR_INVALID, spec.chained  ? "sa_scorer_create_chains: null argument"
+                                    : spec.seeded ? "sa_scorer_create_seeds: null argument"
+                                                  : "sa_scorer_create: null argument");
     *out = nullptr;
     if (spec.band_at && !spec.bands && np > 0) return fail(SA_ERR_INVALID, "sa_scorer_create_band_at: bands is null");
     DeviceGuard dg(device);
@@ -112,7 +184,15 @@ static int create_scorer(const sa_params *P, const WaveSpec &spec, const sa_pair
     s->device = device;
     std::string err;
     SeedItems si;
-    if (int rc = spec.seeded ? make_seeds_score_plan(P, spec, pairs, spec.seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err)
+    ChainsScorePlan cp;
+    if (spec.chained)
+    {
+        if (int rc = make_chains_score_plan(P, spec, pairs, np, device_cus(device), score_knobs(), &cp, &err)) return fail(rc, err);
+        static_cast<ScorePlan &>(*s) = cp.ends;
+        s->gaps = cp.gaps;
+        s->device_bytes = cp.device_bytes;
+    }
+    else if (int rc = spec.seeded ? make_seeds_score_plan(P, spec, pairs, spec.seeds, np, device_cus(device), score_knobs(), s.get(), &si, &err)
                              : make_score_plan(P, spec, pairs, np, device_cus(device), score_knobs(), s.get(), &err))
         return fail(rc, err);
     if (spec.seeded) s->seed_pairs = np;
@@ -131,7 +211,18 @@ static int create_scorer(const sa_params *P, const WaveSpec &spec, const sa_pair
         if (h.size()) HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
         return SA_OK;
     };
-    if (spec.seeded)
+    if (spec.chained)
+    {
+        if ((rc = upload(&s->d_items, cp.items.ends)) || (rc = upload(&s->d_gap_items, cp.items.gaps)) ||
+            (rc = upload(&s->d_gap_order, s->gaps.order)) || (rc = upload(&s->d_chain_pairs, cp.items.pairs)) ||
+            (rc = upload(&s->d_chain_seeds, cp.items.seeds)))
+            return rc;
+        if ((rc = dmalloc(&s->d_gap_rows, (size_t)s->gaps.grid * s->gaps.row_stride * (s->gaps.spec.affine ? 8 : 4))) ||
+            (rc = dmalloc(&s->d_gap_out, (size_t)s->gaps.num_pairs * sizeof(sa_score_result))) ||
+            (rc = dmalloc(&s->d_seed_out, (size_t)np * sizeof(sa_seed_result))))
+            return rc;
+    }
+    else if (spec.seeded)
     {
         if ((rc = upload(&s->d_items, si.items)) || (rc = upload(&s->d_seed_pairs, si.pairs))) return rc;
         if ((rc = dmalloc(&s->d_seed_out, (size_t)np * sizeof(sa_seed_result)))) return rc;
@@ -153,7 +244,7 @@ template <typename RESULT>
 static int score_batch(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, RESULT *out,
                        int (*fetch)(sa_scorer *, RESULT *, void *) = sa_scorer_fetch)
 {
-    const char *const fn = spec.seeded ? "sa_score_batch_seeds" : "sa_score_batch";
+    const char *const fn = spec.chained ? "sa_score_batch_chains" : spec.seeded ? "sa_score_batch_seeds" : "sa_score_batch";
     if (!P || np < 0 || (np > 0 && (!pairs || !out))) return fail(SA_ERR_INVALID, std::string(fn) + ": null argument");
     HostArenas in;
     if (int rc = upload_host_pairs(fn, pairs, np, device, &in)) return rc;
@@ -207,6 +298,19 @@ int sa_score_batch_seeds(const sa_params *P, int32_t gap_open, int32_t gap_exten
     return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_seeds(seeds), pairs, np, device, out, sa_scorer_fetch_seeds);
 }
 
+int sa_scorer_create_chains(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds, const uint64_t *chain_off,
+                            const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
+{
+    return create_scorer(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_chains(seeds, chain_off), pairs, np, device, out);
+}
+
+int sa_score_batch_chains(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, const sa_seed *seeds, const uint64_t *chain_off,
+                          const sa_host_pair *pairs, int64_t np, int device, sa_seed_result *out)
+{
+    return score_batch(P, WaveSpec::gaps(gap_open, gap_extend).extending(xdrop).from_chains(seeds, chain_off), pairs, np, device, out,
+                       sa_scorer_fetch_seeds);
+}
+
 int sa_scorer_create_extend_band(const sa_params *P, int32_t gap_open, int32_t gap_extend, int32_t xdrop, int32_t width,
                                  const sa_pair *pairs, int64_t np, int device, sa_scorer **out)
 {
@@ -254,7 +358,36 @@ int sa_scorer_run(sa_scorer *s, const void *d_text, const void *d_pattern, void 
             return fail(SA_ERR_UNSUPPORTED, "sa_scorer_run: the scorer's variant has no kernel instance");
         HIP_TRY(hipGetLastError());
     }
-    if (s->spec.seeded)
+    if (s->spec.chained)
+    {
+        // the gap items, the global program in a launch of its own plan (R and grid from the gaps' shapes), then the
+        // combine of the pairs
+        if (s->gaps.num_pairs)
+        {
+            WaveArgs a = {};
+            a.sa = score_args(s->gaps, d_text, d_pattern, nullptr, s->d_gap_order, s->gaps.num_pairs, s->d_table, s->d_gap_rows, s->d_gap_out,
+                              s->d_ctrl + 2);
+            a.items = s->d_gap_items;
+            if (!launch_wave<false>(wave_choice(s->gaps.spec, s->gaps.mode), s->gaps.R, s->A <= 4, s->gaps.grid, st, a))
+                return fail(SA_ERR_UNSUPPORTED, "sa_scorer_run: the chains scorer's gap items have no kernel instance");
+            HIP_TRY(hipGetLastError());
+        }
+        ChainsCombineArgs c;
+        c.text = (const int8_t *)d_text;
+        c.pattern = (const int8_t *)d_pattern;
+        c.pairs = s->d_chain_pairs;
+        c.seeds = s->d_chain_seeds;
+        c.order = nullptr;
+        c.table = s->d_table;
+        c.end_out = s->d_out;
+        c.gap_out = s->d_gap_out;
+        c.out = s->d_seed_out;
+        c.ctrl = s->d_ctrl;
+        c.A = s->A;
+        launch_chains_combine(c, s->seed_pairs, st);
+        HIP_TRY(hipGetLastError());
+    }
+    else if (s->spec.seeded)
     {
         SeedsCombineArgs c;
         c.text = (const int8_t *)d_text;
@@ -280,12 +413,12 @@ int sa_scorer_fetch_seeds(sa_scorer *s, sa_seed_result *out, void *stream)
     DeviceGuard dg(s->device);
     if (!dg.ok) return fail(SA_ERR_HIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
-    uint32_t ctrl[2] = {0, 0};
+    uint32_t ctrl[4] = {0, 0, 0, 0};  // [3]: the bad-input flag of a chains scorer's gap launch
     HIP_TRY(hipMemcpyAsync(ctrl, s->d_ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
     if (s->seed_pairs)
         HIP_TRY(hipMemcpyAsync(out, s->d_seed_out, (size_t)s->seed_pairs * sizeof(sa_seed_result), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (ctrl[1]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
+    if (ctrl[1] || ctrl[3]) return fail(SA_ERR_INVALID, "a text or pattern byte is outside the alphabet (0..A-1)");
     return SA_OK;
 }
 
@@ -317,8 +450,10 @@ int sa_scorer_fetch(sa_scorer *s, sa_score_result *out, void *stream)
 int sa_scorer_info(const sa_scorer *s, int64_t *num_waves, int32_t *rows_per_lane, uint64_t *device_bytes)
 {
     if (!s) return fail(SA_ERR_INVALID, "sa_scorer_info: null scorer");
-    if (num_waves) *num_waves = s->grid;
-    if (rows_per_lane) *rows_per_lane = s->R;
+    // a chains scorer: the larger of its two launches' grids, and the rows per lane of the launch with more cells
+    const bool by_gaps = s->spec.chained && s->gaps.padded_cells > s->padded_cells;
+    if (num_waves) *num_waves = s->spec.chained ? std::max(s->grid, s->gaps.grid) : s->grid;
+    if (rows_per_lane) *rows_per_lane = by_gaps ? s->gaps.R : s->R;
     if (device_bytes) *device_bytes = s->device_bytes;
     return SA_OK;
 }

@@ -339,4 +339,152 @@ int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pai
     return SA_OK;
 }
 
+int make_chains_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                           ChainsScorePlan *out, std::string *err)
+{
+    if (!out || !spec.extend)
+    {
+        *err = "chains scorer: null argument";
+        return SA_ERR_INVALID;
+    }
+    *out = ChainsScorePlan();
+    if (spec.ext_band || spec.banded || spec.band_at)
+    {
+        *err = "chained seeds inside a band (band, bands or width with chains) are not built";
+        return SA_ERR_UNSUPPORTED;
+    }
+    WaveSpec ext = spec;  // the extension each end item runs; make_score_plan takes no seeded spec
+    ext.seeded = ext.chained = false;
+    ext.seeds = nullptr;
+    ext.chain_off = nullptr;
+    // the mode, the xdrop and the limits, on the whole pairs: the sum of a pair's pieces stays under the bound of
+    // its (n, m), and so does every key
+    ScorePlan whole;
+    if (int rc = make_score_plan(P, ext, pairs, np, num_cu, kn, &whole, err)) return rc;
+    const sa_seed *const seeds = spec.seeds;
+    const uint64_t *const off = spec.chain_off;
+    if (np > 0 && (!seeds || !off))
+    {
+        *err = !seeds ? "seeds is null" : "chain_off is null";
+        return SA_ERR_INVALID;
+    }
+    if (np > 0 && off[0] != 0)
+    {
+        *err = "pair 0: chain_off[0] is " + std::to_string(off[0]) + ", not 0";
+        return SA_ERR_INVALID;
+    }
+    ChainItems &ci = out->items;
+    ci.pairs.resize((size_t)np);
+    const int64_t go = spec.gap_open, ge = spec.gap_extend;
+    for (int64_t p = 0; p < np; ++p)
+    {
+        const std::string who = "pair " + std::to_string(p);
+        if (off[p + 1] < off[p])
+        {
+            *err = who + ": chain_off decreases from " + std::to_string(off[p]) + " to " + std::to_string(off[p + 1]);
+            return SA_ERR_INVALID;
+        }
+        if (off[p + 1] == off[p])
+        {
+            *err = who + " has no seed: a chain holds at least one";
+            return SA_ERR_INVALID;
+        }
+        if (off[p + 1] > (uint64_t)INT32_MAX)
+        {
+            *err = "more than 2^31-1 seeds";
+            return SA_ERR_UNSUPPORTED;
+        }
+        const uint64_t n = pairs[p].text_len, m = pairs[p].pattern_len, c = off[p + 1] - off[p];
+        ChainPair &cp = ci.pairs[p];
+        cp = ChainPair();
+        cp.text_base = pairs[p].text_offset;
+        cp.pattern_base = pairs[p].pattern_offset;
+        cp.seed_begin = (int32_t)off[p];
+        cp.seed_end = (int32_t)off[p + 1];
+        cp.gap_begin = (int32_t)ci.gaps.size();
+        cp.left = cp.right = -1;
+        int64_t closed = 0;
+        uint64_t te = 0, pe = 0;  // the end of the seed before
+        for (uint64_t i = 0; i < c; ++i)
+        {
+            const sa_seed &sd = seeds[off[p] + i];
+            const uint64_t ts = sd.text_pos, ps = sd.pattern_pos, L = sd.length;
+            const std::string what = who + ", seed " + std::to_string(i) + " {" + std::to_string(ts) + ", " + std::to_string(ps) + ", " + std::to_string(L) + "}";
+            // n, m < 2^24: compared so that no sum wraps
+            if (ts > n || L > n - ts || ps > m || L > m - ps)
+            {
+                *err = what + " does not lie inside " + std::to_string(n) + " text and " + std::to_string(m) + " pattern letters";
+                return SA_ERR_INVALID;
+            }
+            if (i > 0 && (ts < te || ps < pe))
+            {
+                *err = what + " begins before the end (" + std::to_string(te) + ", " + std::to_string(pe) + ") of the seed before it: a chain is colinear and its seeds do not overlap";
+                return SA_ERR_INVALID;
+            }
+            if (i == 0)
+            {
+                cp.ts = ts;
+                cp.ps = ps;
+                if (ts > 0 && ps > 0)
+                {
+                    cp.left = (int32_t)ci.ends.size();
+                    ci.ends.push_back(SeedItem{pairs[p].text_offset + ts - 1, pairs[p].pattern_offset + ps - 1, (uint32_t)ts, (uint32_t)ps, -1, (int32_t)p});
+                }
+            }
+            else
+            {
+                const uint64_t gn = ts - te, gm = ps - pe;
+                if (gn > 0 && gm > 0)
+                {
+                    ci.seeds.back().gap = (int32_t)ci.gaps.size();
+                    ci.gaps.push_back(SeedItem{pairs[p].text_offset + te, pairs[p].pattern_offset + pe, (uint32_t)gn, (uint32_t)gm, 1, (int32_t)p});
+                }
+                else if (gn + gm > 0)
+                {
+                    closed -= go + ((int64_t)(gn + gm) - 1) * ge;  // inside int32 under the whole pair's limit
+                    cp.closed_cols += (uint32_t)(gn + gm);
+                }
+            }
+            ci.seeds.push_back(ChainSeed{pairs[p].text_offset + ts, pairs[p].pattern_offset + ps, L, -1, 0});
+            te = ts + L;
+            pe = ps + L;
+        }
+        cp.te = te;
+        cp.pe = pe;
+        cp.gap_end = (int32_t)ci.gaps.size();
+        cp.closed_score = (int32_t)closed;
+        if (n - te > 0 && m - pe > 0)
+        {
+            cp.right = (int32_t)ci.ends.size();
+            ci.ends.push_back(SeedItem{pairs[p].text_offset + te, pairs[p].pattern_offset + pe, (uint32_t)(n - te), (uint32_t)(m - pe), 1, (int32_t)p});
+        }
+    }
+    // the end items as extension pairs, the gap items as global pairs: each launch has its own cost, R, order by
+    // cells, grid and boundary rows
+    auto as_pairs = [](const std::vector<SeedItem> &items) {
+        std::vector<sa_pair> ip(items.size());
+        for (size_t k = 0; k < ip.size(); ++k) ip[k] = sa_pair{0, items[k].n, 0, items[k].m};
+        return ip;
+    };
+    const std::vector<sa_pair> ep = as_pairs(ci.ends), gp = as_pairs(ci.gaps);
+    if (int rc = make_score_plan(P, ext, ep.data(), (int64_t)ep.size(), num_cu, kn, &out->ends, err)) return rc;
+    out->ends.spec.seeded = out->ends.spec.chained = true;
+    // gap open == gap extend is the linear recurrence of that penalty: the linear items instances
+    sa_params gparams = *P;
+    WaveSpec gspec = WaveSpec::gaps(spec.gap_open, spec.gap_extend);
+    gspec.traced = spec.traced;
+    if (!spec.traced && spec.gap_open == spec.gap_extend)
+    {
+        gparams.gap_penalty = spec.gap_open;
+        gspec = WaveSpec();
+    }
+    if (int rc = make_score_plan(&gparams, gspec, gp.data(), (int64_t)gp.size(), num_cu, kn, &out->gaps, err)) return rc;
+    out->gaps.spec.seeded = true;
+    out->device_bytes = whole.input_bytes + (out->ends.device_bytes - out->ends.input_bytes) + (out->gaps.device_bytes - out->gaps.input_bytes) +
+                        (uint64_t)(ep.size() + gp.size()) * (sizeof(SeedItem) - 24) + (uint64_t)ci.seeds.size() * sizeof(ChainSeed) +
+                        (uint64_t)np * (sizeof(ChainPair) + sizeof(sa_seed_result));
+    out->ends.input_bytes = whole.input_bytes;
+    return SA_OK;
+}
+
 }  // namespace sa

@@ -60,6 +60,8 @@ struct WaveSpec {
     int32_t width = 0;             // sa_score_batch_extend_band): one half-width per call, both halves of a seed
     bool seeded = false;           // seed extension (sa_hip.h sa_seed, one per pair): an extension to both
     const sa_seed *seeds = nullptr;  // sides of the caller's seeds, planned by the make_seeds_* planners
+    bool chained = false;          // chained seeds (sa_hip.h sa_score_batch_chains; with seeded): pair k owns
+    const uint64_t *chain_off = nullptr;  // seeds[chain_off[k] .. chain_off[k + 1]), planned by the make_chains_* planners
     bool traced = false;           // the aligners' instances: direction words, affine whatever the penalties
 
     static WaveSpec gaps(int32_t open, int32_t extend)
@@ -103,6 +105,13 @@ struct WaveSpec {
         WaveSpec s = *this;
         s.seeded = true;
         s.seeds = per_pair;
+        return s;
+    }
+    WaveSpec from_chains(const sa_seed *flat, const uint64_t *off) const
+    {
+        WaveSpec s = from_seeds(flat);
+        s.chained = true;
+        s.chain_off = off;
         return s;
     }
 };
@@ -264,6 +273,51 @@ struct SeedItems {
 // 8 bytes above a pair descriptor and, per pair, a SeedPair and a sa_seed_result.
 int make_seeds_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
                           const ScoreKnobs &kn, ScorePlan *out, SeedItems *items, std::string *err);
+
+// Chained seeds (sa_hip.h sa_score_batch_chains): a pair becomes its two end items, the left half of its first
+// seed and the right half of its last (SeedItem, as the seeds scorer has them), and one gap item per rectangle
+// between two consecutive seeds, a SeedItem with dir +1 that the global program fills (kVarItems,
+// kVarAffineItems). A piece with an empty side is no item: an empty end scores 0 as ever, and an empty-side gap is
+// one gap run whose closed-form score and length go into the pair's record.
+struct ChainSeed {
+    uint64_t text_off, pattern_off, len;  // the arena offsets of the seed's first letters
+    int32_t gap, pad;                     // the gap item between this seed and the next, -1: none, or one with an empty side
+};
+// One pair of a chains call as the combine, walk and join kernels take it.
+struct ChainPair {
+    uint64_t text_base, pattern_base;  // the arena offsets of the pair's first letters
+    uint64_t ts, ps;                 // the first seed's position in the pair
+    uint64_t te, pe;                 // the last seed's end
+    int32_t seed_begin, seed_end;    // the pair's seeds in ChainItems::seeds (the caller's chain_off)
+    int32_t gap_begin, gap_end;      // its gap items in ChainItems::gaps, in chain order
+    int32_t left, right;             // its end items in ChainItems::ends, -1: that end is empty
+    int32_t closed_score;            // the sum of its empty-side gaps' scores, -(gap_open + (k - 1) gap_extend) each
+    uint32_t closed_cols;            // and of their lengths k
+};
+struct ChainItems {
+    std::vector<SeedItem> ends;      // pair by pair, left before right
+    std::vector<SeedItem> gaps;      // pair by pair, in chain order
+    std::vector<ChainSeed> seeds;
+    std::vector<ChainPair> pairs;
+};
+// The chains scorer's plan: two launches on one stream, each with its own R, grid, boundary rows and work order.
+// `ends` is the seeds scorer's plan of the end items (spec.seeded and spec.chained set), `gaps` the global
+// scorer's plan of the gap items (spec.seeded set and spec.extend not: the items variants; linear when gap open
+// equals gap extend, unless traced). ends.input_bytes is the whole pairs'; device_bytes is the sum of both
+// launches' and of the per-pair records, seeds and results.
+struct ChainsScorePlan {
+    ScorePlan ends, gaps;
+    ChainItems items;
+    uint64_t device_bytes = 0;
+};
+// Plans the chains scorer; `spec` is an extension's with from_chains(). SA_ERR_INVALID, the message naming the
+// pair and (where one is at fault) the seed's index in its chain, for: seeds or chain_off null with pairs,
+// chain_off[0] != 0, chain_off decreasing, a pair without a seed, a seed outside its pair, and a seed that
+// begins before the one before it ends, on either side. A width (ext_band) is SA_ERR_UNSUPPORTED, as a band of
+// either kind is for every extension. The mode, the xdrop and the limits are make_score_plan's for the extension
+// scorer on the whole pairs' (n, m).
+int make_chains_score_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                           ChainsScorePlan *out, std::string *err);
 
 // Resident waves per SIMD the grid is sized for at R rows per lane (register budget of the
 // instances).

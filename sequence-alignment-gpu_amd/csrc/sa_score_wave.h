@@ -19,6 +19,8 @@
 //   kVarAffineSeeds    Affine Extend Seed              global               gap_extend, xdrop, items
 //   kVarExtendBand     Affine Band BandAt Extend       global               gap_extend, xdrop, width
 //   kVarSeedsBand      Affine Band BandAt Extend Seed  global               gap_extend, xdrop, width, items
+//   kVarItems          Seed                            global               items
+//   kVarAffineItems    Affine Seed                     global               gap_extend, items
 //
 // Untraced, every row exists at R = 1, 2, 4, 8; with Trace added, the affine rows exist at R = 8. The
 // static_asserts of score_wave are the rule for a legal combination, the table of sa_wave_launch.h is the
@@ -200,6 +202,12 @@
 // `if constexpr (SEED)` or a constant condition, so the other instances compile to what they were. The
 // planner makes no item of an empty half, and the guards c0 < n and row1 + r < m keep a backward read at
 // or after the half's last letter, the pair's first.
+//
+// SEED without EXT (kVarItems, kVarAffineItems) is the global program on work items: the gap pieces of chained
+// seeds, sa_hip.h sa_score_batch_chains, each the rectangle between two consecutive seeds of a pair. The
+// addressing is SEED's two loads, here always with dir = +1; the cells, the borders, the traced nibble and the
+// result, H[m][n] written to out[item], are the global program's, and no line of the program names the
+// combination. The planner makes no item with an empty side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -280,6 +288,7 @@ constexpr unsigned kVarExtend = kWaveExtend, kVarAffineExtend = kWaveAffine | kW
 constexpr unsigned kVarSeeds = kVarExtend | kWaveSeed, kVarAffineSeeds = kVarAffineExtend | kWaveSeed;
 constexpr unsigned kVarExtendBand = kVarAffineExtend | kWaveBand | kWaveBandAt;  // extension inside a width
 constexpr unsigned kVarSeedsBand = kVarExtendBand | kWaveSeed;
+constexpr unsigned kVarItems = kWaveSeed, kVarAffineItems = kWaveAffine | kWaveSeed;  // the global program on work items
 
 // The kernel argument of every instance: the base arguments, then (traced instances) the direction arena,
 // then one int and one pointer whose meaning is the variant's, then the width of a banded extension, which has
@@ -347,7 +356,8 @@ __device__ __forceinline__ void score_wave(const ScoreArgs &a, int gap_extend, i
     static_assert(!BAT || (BAND && (ENDS || MODE == SA_LOCAL || EXT)),
                   "band-at instances: banded; local, ends-free (global and fit are two of its flag sets), or an extension inside its width");
     static_assert(!EXT || (MODE == SA_GLOBAL && (!BAND || BAT) && !ENDS), "extension instances: the global borders, no band but its width's, no free ends");
-    static_assert(!SEED || EXT, "seeds instances: extension alignment of a work item");
+    static_assert(!SEED || EXT || (MODE == SA_GLOBAL && !BAND && !ENDS),
+                  "work items: extension alignment of a seed's half, or the plain global program on a chain's gap piece");
     constexpr bool LOCAL = MODE == SA_LOCAL, FIT = MODE == SA_FIT;
     constexpr bool BEST = LOCAL || EXT;  // the result is the best cell: per-row running best and the key
     constexpr int SENT = kBandSentinel;

@@ -115,4 +115,23 @@ struct SeedTracePlan : TracePlan {
 int make_seeds_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, const sa_seed *seeds, int64_t np, int num_cu,
                           const ScoreKnobs &kn, uint64_t budget, SeedTracePlan *out, std::string *err);
 
+// The chains aligner (sa_hip.h sa_align_pairs_chains): two traced fills per chunk, of the chunk's end items
+// (`score`, its order cut by chunk_begin; dir_bytes and dir_off per end item) and of its gap items (`gaps`, cut by
+// gap_chunk_begin; gap_dir_bytes and gap_dir_off per gap item), into one arena. Every piece is charged
+// trace_dir_bytes of its own rectangle, never of n x m; a piece with an empty side has no item and no bytes. The
+// chunks are cut over the pairs, ordered by the cells of all their pieces, so that a pair's pieces share a chunk;
+// inside a chunk each launch's items are ordered by cells. A pair is SA_ERR_UNSUPPORTED only when its pieces
+// together exceed `budget`. slot_off is per pair, its text_len + pattern_len bytes.
+struct ChainTracePlan : TracePlan {
+    ScorePlan gaps;
+    ChainItems items;
+    std::vector<uint64_t> gap_dir_bytes, gap_dir_off;
+    std::vector<int64_t> gap_chunk_begin;
+    std::vector<int32_t> pair_order;
+    std::vector<int64_t> pair_chunk_begin;
+    int64_t num_pairs = 0;
+};
+int make_chains_trace_plan(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int num_cu, const ScoreKnobs &kn,
+                           uint64_t budget, ChainTracePlan *out, std::string *err);
+
 }  // namespace sa

@@ -50,6 +50,7 @@ struct WaveChoice {
 
 // The single mode -> program mapping.
 //  - Extension (and seeds) is the global program; inside a width it is the affine band-at instance of it.
+//  - Work items without an extension (the gap pieces of chained seeds) are the global program, linear or affine.
 //  - Per-pair bands: SA_LOCAL is the local program; every other mode runs as the ends-free mode it equals,
 //    SA_GLOBAL with no flag and SA_FIT with the text's two.
 //  - Ends-free is the fit program when the text's end is free and the global program otherwise.
@@ -61,6 +62,7 @@ constexpr WaveChoice wave_choice(const WaveSpec &sp, int mode)
     const unsigned aff = sp.affine ? kWaveAffine : 0u;
     if (sp.extend && sp.ext_band) return WaveChoice{kVarExtendBand | (sp.seeded ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop, sp.width};
     if (sp.extend) return WaveChoice{aff | kWaveExtend | (sp.seeded ? kWaveSeed : 0u), SA_GLOBAL, sp.xdrop, 0};
+    if (sp.seeded) return WaveChoice{aff | kWaveSeed, SA_GLOBAL, 0, 0};
     if (sp.band_at && mode == SA_LOCAL) return WaveChoice{kVarBandAtLocal, SA_LOCAL, 0, 0};
     const int ends = sp.band_at && mode == SA_GLOBAL ? 0
                      : sp.band_at && mode == SA_FIT  ? SA_FREE_TEXT_BEGIN | SA_FREE_TEXT_END
@@ -108,6 +110,8 @@ static_assert(is(wave_choice(spec(true, false, false, true, false, true), SA_GLO
               "extension inside a width: the affine band-at instance of the global program");
 static_assert(is(wave_choice(spec(true, false, false, true, true, true), SA_GLOBAL), kVarSeedsBand, SA_GLOBAL, 9, 5),
               "seeds inside a width: the same of a work item");
+static_assert(is(wave_choice(spec(true, false, false, false, true), SA_GLOBAL), kVarAffineItems, SA_GLOBAL, 0), "a chain's gap pieces: the global program of a work item");
+static_assert(is(wave_choice(spec(false, false, false, false, true), SA_GLOBAL), kVarItems, SA_GLOBAL, 0), "the same, linear");
 }  // namespace wave_choice_check
 
 // One row of the table: a variant and the programs it has instances of.
@@ -131,7 +135,9 @@ using WaveTable = std::tuple<
     WaveRow<kVarSeeds,        SA_GLOBAL>,                    // xdrop, items
     WaveRow<kVarAffineSeeds,  SA_GLOBAL>,                    // xdrop, items
     WaveRow<kVarExtendBand,   SA_GLOBAL>,                    // xdrop, width
-    WaveRow<kVarSeedsBand,    SA_GLOBAL>>;                   // xdrop, width, items
+    WaveRow<kVarSeedsBand,    SA_GLOBAL>,                    // xdrop, width, items
+    WaveRow<kVarItems,        SA_GLOBAL>,                    // items
+    WaveRow<kVarAffineItems,  SA_GLOBAL>>;                   // items
 
 template <bool TRACE>
 using WaveArgsT = ArgsOf<TRACE ? kWaveTrace : 0u>;

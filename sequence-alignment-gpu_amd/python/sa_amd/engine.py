@@ -45,7 +45,8 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_score_batch_extend", "sa_scorer_create_extend", "sa_align_pairs_extend",
            "sa_score_batch_seeds", "sa_scorer_create_seeds", "sa_scorer_fetch_seeds", "sa_align_pairs_seeds",
            "sa_score_batch_extend_band", "sa_scorer_create_extend_band", "sa_align_pairs_extend_band",
-           "sa_score_batch_seeds_band", "sa_scorer_create_seeds_band", "sa_align_pairs_seeds_band")
+           "sa_score_batch_seeds_band", "sa_scorer_create_seeds_band", "sa_align_pairs_seeds_band",
+           "sa_score_batch_chains", "sa_scorer_create_chains", "sa_align_pairs_chains")
 
 
 class SaParams(ctypes.Structure):
@@ -168,6 +169,11 @@ def _load():
                                               ctypes.POINTER(P)]
     L.sa_align_pairs_seeds_band.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, I32, P, P, ctypes.c_int64, I,
                                             ctypes.POINTER(SaResult), P, P]
+    L.sa_score_batch_chains.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, P, ctypes.c_int64, I, P]
+    L.sa_scorer_create_chains.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, ctypes.POINTER(SaPair), ctypes.c_int64, I,
+                                          ctypes.POINTER(P)]
+    L.sa_align_pairs_chains.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, P, ctypes.c_int64, I,
+                                        ctypes.POINTER(SaResult), P, P]
     L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
     L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -246,13 +252,39 @@ def _seeds(seeds, num_pairs: int, xdrop, band, bands) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
-def _variant(gap: int, gap_extend, band, bands, xdrop, seeds, num_pairs: int, width=None):
+def _chains(chains, num_pairs: int, xdrop, seeds, band, bands, width):
+    """`chains` (per pair, a list of (text_pos, pattern_pos, length) triples) as the flat (total, 3) uint64 array of
+    sa_seed and the num_pairs + 1 uint64 chain_off the chains functions take, after the checks the three callers
+    share: chains= excludes seeds=, band=, bands= and width=, and requires xdrop= (NO_XDROP for none)."""
+    for name, other in (("seeds", seeds), ("band", band), ("bands", bands), ("width", width)):
+        if other is not None:
+            raise ValueError(f"chains= and {name}= exclude each other" + ("" if name == "seeds" else ": chained seeds inside a band are not built"))
+    if xdrop is None:
+        raise ValueError("chains= requires xdrop= (NO_XDROP for none)")
+    if len(chains) != num_pairs:
+        raise ValueError(f"chains holds {len(chains)} chains for {num_pairs} pairs")
+    per = [np.asarray(c, dtype=np.int64).reshape(-1, 3) for c in chains]
+    if any((c < 0).any() for c in per):
+        raise ValueError("chains= holds a negative value")
+    flat = np.ascontiguousarray(np.concatenate(per) if per else np.zeros((0, 3)), dtype=np.uint64)
+    off = np.zeros(num_pairs + 1, np.uint64)
+    off[1:] = np.cumsum([len(c) for c in per], dtype=np.uint64)
+    # one word more than the seeds: a call without any seed still passes an address, and the library names the pair
+    return np.ascontiguousarray(np.concatenate([flat.ravel(), [0]]).astype(np.uint64)), off
+
+
+def _variant(gap: int, gap_extend, band, bands, xdrop, seeds, num_pairs: int, width=None, chains=None):
     """The variant that the keywords of score_batch, Scorer and align_pairs_affine name, resolved once: the
     suffix of the C function (sa_score_batch<suffix>, sa_scorer_create<suffix>, sa_align_pairs<suffix>), the
     arguments that go between params and the pairs, and the array those point into, to keep alive over the
     call. Without `gap_extend` the gap is linear, gap_open = gap_extend = gap; with nothing else either, there
     is no gap model: the suffix is empty. `width` (an extension's or a seeds call's half-width about the anchor's
-    diagonal) is checked after everything else, so a call that was refused before is refused by the same words."""
+    diagonal) is checked after everything else, so a call that was refused before is refused by the same words.
+    `chains` (chained seeds, a list of triples per pair) is checked first: it excludes every keyword but xdrop."""
+    if chains is not None:
+        flat, off = _chains(chains, num_pairs, xdrop, seeds, band, bands, width)
+        ge = gap if gap_extend is None else gap_extend
+        return "_chains", (gap, ge, xdrop, flat.ctypes.data, off.ctypes.data), (flat, off)
     if band is not None and bands is not None:
         raise ValueError("band= and bands= exclude each other")
     if xdrop is not None and (band is not None or bands is not None):
@@ -375,7 +407,7 @@ def align_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
 
 def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
                        gap_extend: int, device: int = 0, strings: bool = True, band: int | None = None,
-                       bands=None, xdrop: int | None = None, seeds=None, width: int | None = None) -> list[dict]:
+                       bands=None, xdrop: int | None = None, seeds=None, width: int | None = None, chains=None) -> list[dict]:
     """sa_align_pairs_affine: independent pairs from host memory aligned on `device` under gap open /
     gap extend (synchronous). The keys are those of Plan.all_alignments; without strings, the scalar
     ones. With gap_open == gap_extend == g every value is align_pair's for gap g. `mode` may also be FIT
@@ -391,8 +423,11 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
     start_text and start_pattern are the 0-based indices of the first aligned letters. With `width` (>= 0;
     requires `xdrop`, takes neither `band` nor `bands`), sa_align_pairs_extend_band or, with `seeds`,
     sa_align_pairs_seeds_band: the same inside |j - i| <= width of each extension's own matrix, with direction
-    bytes for the band only."""
-    variant = _variant(gap_open, gap_extend, band, bands, xdrop, seeds, len(texts), width)
+    bytes for the band only. With `chains` (per pair, a list of colinear (text_pos, pattern_pos, length) seeds;
+    requires `xdrop`, excludes `seeds`, `band`, `bands` and `width`), sa_align_pairs_chains: the extension at the
+    chain's two ends and the global alignment of every rectangle between two consecutive seeds, joined with the
+    seeds' letters, with direction bytes for those pieces only."""
+    variant = _variant(gap_open, gap_extend, band, bands, xdrop, seeds, len(texts), width, chains)
     if gap_extend is None and xdrop is None:  # as ever: without a gap model, align_batch on one device, band or no band
         return align_batch(mode, texts, patterns, S, gap_open, 1, None, strings)
     return _align_host_pairs(mode, texts, patterns, S, gap_open, device, None, strings, variant)
@@ -508,7 +543,7 @@ assert SCORE_DTYPE.itemsize == ctypes.sizeof(SaScoreResult)
 
 def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap: int,
                 device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                bands=None, xdrop: int | None = None, seeds=None, width: int | None = None) -> np.ndarray:
+                bands=None, xdrop: int | None = None, seeds=None, width: int | None = None, chains=None) -> np.ndarray:
     """sa_score_batch: the score and scored cell of every pair from host memory (SCORE_DTYPE), without
     direction planes or traceback (synchronous). With `gap_extend`, sa_score_batch_affine: `gap` is
     the gap-open penalty and a gap of k letters costs gap + (k - 1) * gap_extend. With `band`,
@@ -525,12 +560,15 @@ def score_batch(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], 
     SEED_DTYPE array (score, status, begin_text, begin_pattern, end_text, end_pattern). With `width` (>= 0;
     requires `xdrop`, takes neither `band` nor `bands`), sa_score_batch_extend_band or, with `seeds`,
     sa_score_batch_seeds_band: the extension inside |j - i| <= width of its own matrix, the same width on both
-    sides of a seed; a width of max(n, m) or more is the unbanded call."""
-    suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(texts), width)
+    sides of a seed; a width of max(n, m) or more is the unbanded call. With `chains` (per pair, a list of colinear,
+    non-overlapping (text_pos, pattern_pos, length) seeds; requires `xdrop`, mode SA_GLOBAL; excludes `seeds`,
+    `band`, `bands` and `width`), sa_score_batch_chains: the seeds' scores, the global score of every rectangle
+    between two consecutive seeds and the extensions of the chain's two ends, as a SEED_DTYPE array."""
+    suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(texts), width, chains)
     p, S_keep, alpha_keep = _params(mode, S, gap, None, rows_per_lane)
     hp, ts, ps = _host_pairs(texts, patterns)
     n = len(ts)
-    out = np.zeros(max(1, n), SEED_DTYPE if seeds is not None else SCORE_DTYPE)
+    out = np.zeros(max(1, n), SEED_DTYPE if seeds is not None or chains is not None else SCORE_DTYPE)
     _check(getattr(lib, "sa_score_batch" + suffix)(ctypes.byref(p), *args, hp, n, device, out.ctypes.data))
     return out[:n]
 
@@ -543,19 +581,21 @@ class Scorer:
     `xdrop`, an extension scorer (sa_scorer_create_extend; mode SA_GLOBAL, no band). With `seeds` (one
     (text_pos, pattern_pos, length) per pair; requires `xdrop`), a seeds scorer (sa_scorer_create_seeds):
     results() is then a SEED_DTYPE array. With `width` (requires `xdrop`), the banded extension scorer or seeds
-    scorer (sa_scorer_create_extend_band, sa_scorer_create_seeds_band). `mode` as score_batch takes it."""
+    scorer (sa_scorer_create_extend_band, sa_scorer_create_seeds_band). With `chains` (per pair, a list of seeds;
+    requires `xdrop`, excludes `seeds`, `band`, `bands` and `width`), a chains scorer (sa_scorer_create_chains):
+    results() is a SEED_DTYPE array, as a seeds scorer's. `mode` as score_batch takes it."""
 
     def __init__(self, mode: int, S: np.ndarray, gap: int, pairs: list[tuple[int, int, int, int]],
                  device: int = 0, rows_per_lane: int = 0, gap_extend: int | None = None, band: int | None = None,
-                 bands=None, xdrop: int | None = None, seeds=None, width: int | None = None):
-        suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(pairs), width)
+                 bands=None, xdrop: int | None = None, seeds=None, width: int | None = None, chains=None):
+        suffix, args, keep = _variant(gap, gap_extend, band, bands, xdrop, seeds, len(pairs), width, chains)
         self._p, self._S, self._alpha = _params(mode, S, gap, None, rows_per_lane)
         arr = (SaPair * max(1, len(pairs)))(*[SaPair(*pr) for pr in pairs])
         self.num_pairs = len(pairs)
         self.pairs = pairs
         self.device = device
         h = ctypes.c_void_p()
-        self.seeded = seeds is not None
+        self.seeded = seeds is not None or chains is not None
         _check(getattr(lib, "sa_scorer_create" + suffix)(ctypes.byref(self._p), *args, arr, len(pairs), device, ctypes.byref(h)))
         self.handle = h
 

@@ -68,6 +68,19 @@ report holds (a) / (b) with (b)'s own min-max spread and (a) / (c) beside the ra
 costs. A second table has each window clipped to the read's span +- 32 letters. Then align_pairs_affine(seeds=)
 end to end on 4000 of the pairs beside the two-call host composition, whose strings it must equal.
 
+With --mode chain the chains scorer and aligner (sa_hip.h: sa_scorer_create_chains, sa_align_pairs_chains): 2048
+DNA reads, each its own 10000-letter text mutated with substitutions and deletions so that its path drifts by
+some hundred diagonals. A read's chain is the exact-match runs of at least 15 columns of its banded global
+alignment under 11 / 2, computed once and cached under bench_out/. Alternated round by round after a warm-up (7
+rounds, device events, median with min and max): (a) the chains scorer; (b) the composition of existing calls on
+host-sliced pieces, one extension scorer per end and one affine global scorer over all gap rectangles as
+separate pairs (the same cells and programs: the yardstick), whose sum with the seeds' scores the chained scores
+are asserted equal to at the timed size; (c) the band-at global scorer on the narrowest band per pair that holds
+the chain's diagonals +- 16, the alternative a caller has without chains. Beside each measured ratio the
+planner's step-model ratio, and the mean shape of a gap piece with what the model charges for it. Then (d)
+align_pairs_affine(chains=) on 64 of the pairs beside bands= with (c)'s bands: arena bytes, chunks, fill, walk
+and end-to-end wall time.
+    python3 tools/score_bench.py --mode chain [--small] --out profiles/r22/score_chain_bench.json
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
 With --mode extend --width W.. the banded extension (sa_hip.h: sa_scorer_create_extend_band,
 sa_align_pairs_extend_band) on the chimeric pairs under --exit-gap, without a drop and at --xdrop: per X, the
@@ -707,6 +720,187 @@ def seeds_aligned_row(args, engine, w, seeds, go: int, ge: int, xdrop) -> dict:
             "seeds_over_composition": round(statistics.median(ms["seeds"]) / statistics.median(ms["composition"]), 4)}
 
 
+def chain_workload(small: bool) -> dict:
+    """Reads of 10000 letters: every text mutated on its own (5 % substitutions, 5 % deletions, 2 % of the letters
+    redrawn: synthetic.mutate), so that the read's path ends some 500 diagonals from where it starts."""
+    from sa_amd import synthetic
+    npairs, n = (128 if small else 2048), 10000
+    text = synthetic.random_sequence(23, npairs * n, 4)
+    pats = [synthetic.mutate(text[k * n:(k + 1) * n], 2300 + k, 4) for k in range(npairs)]
+    po = np.concatenate([[0], np.cumsum([len(x) for x in pats])])
+    return {"name": "long_reads", "S": synthetic.blast_matrix(), "text": text, "pattern": np.ascontiguousarray(np.concatenate(pats)).astype(np.int8),
+            "pairs": [(k * n, n, int(po[k]), len(pats[k])) for k in range(npairs)]}
+
+
+def exact_match_chains(engine, w, go: int, ge: int, min_len: int = 15, band: int = 256):
+    """Per pair the chain of its exact-match runs of at least `min_len` columns in its banded global alignment
+    (half-width `band` about the corner-to-corner diagonals), as (text_pos, pattern_pos, length) triples; cached."""
+    cache = os.path.join(ROOT, "bench_out", f"chain_seeds_{len(w['pairs'])}_{go}_{ge}_{min_len}.npz")
+    if os.path.exists(cache):
+        z = np.load(cache)
+        return [z["flat"][a:b].tolist() for a, b in zip(z["off"][:-1], z["off"][1:])]
+    chains, pairs = [], w["pairs"]
+    for lo in range(0, len(pairs), 256):
+        part = pairs[lo:lo + 256]
+        texts = [w["text"][p[0]:p[0] + p[1]] for p in part]
+        pats = [w["pattern"][p[2]:p[2] + p[3]] for p in part]
+        for r in engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, band=band):
+            a = np.frombuffer(r["aligned_text"].encode(), dtype=np.uint8)
+            b = np.frombuffer(r["aligned_pattern"].encode(), dtype=np.uint8)
+            eq = np.concatenate([[0], (a == b).astype(np.int8), [0]])
+            edges = np.flatnonzero(np.diff(eq))
+            starts, ends = edges[0::2], edges[1::2]
+            keep = ends - starts >= min_len
+            tpos = np.concatenate([[0], np.cumsum(a != ord("-"))])  # text letters before column c
+            ppos = np.concatenate([[0], np.cumsum(b != ord("-"))])
+            chains.append([(int(tpos[c]), int(ppos[c]), int(e - c)) for c, e in zip(starts[keep], ends[keep])])
+    os.makedirs(os.path.dirname(cache), exist_ok=True)
+    off = np.concatenate([[0], np.cumsum([len(c) for c in chains])])
+    np.savez(cache, flat=np.array([s for c in chains for s in c], dtype=np.int64).reshape(-1, 3), off=off)
+    return chains
+
+
+def chain_pieces(w, chains):
+    """The pieces of every chained pair as the workloads of the composition: the left ends reversed on the host, the
+    right ends sliced, and every gap rectangle with two non-empty sides a pair of its own. Per pair also the sum
+    of its seeds' scores and of its empty-side gaps' closed forms (under go, ge given later: the lengths)."""
+    S = np.asarray(w["S"])
+    lt, lp, rt, rp, gt, gp, gap_pair, seed_score, closed = [], [], [], [], [], [], [], [], []
+    for k, ((to, n, po, m), ch) in enumerate(zip(w["pairs"], chains)):
+        t, p = w["text"][to:to + n], w["pattern"][po:po + m]
+        sd = np.array(ch, dtype=np.int64).reshape(-1, 3)
+        ts0, ps0 = int(sd[0, 0]), int(sd[0, 1])
+        te, pe = int(sd[-1, 0] + sd[-1, 2]), int(sd[-1, 1] + sd[-1, 2])
+        lt.append(t[:ts0][::-1]), lp.append(p[:ps0][::-1]), rt.append(t[te:]), rp.append(p[pe:])
+        total = int(sd[:, 2].sum())
+        before = np.concatenate([[0], np.cumsum(sd[:, 2])[:-1]])
+        col = np.arange(total)
+        seed_score.append(int(S[p[np.repeat(sd[:, 1] - before, sd[:, 2]) + col], t[np.repeat(sd[:, 0] - before, sd[:, 2]) + col]].sum()))
+        runs = []
+        for (a, b, L), (c, d, _) in zip(ch, ch[1:]):
+            gn, gm = c - a - L, d - b - L
+            if gn and gm:
+                gt.append(t[a + L:c]), gp.append(p[b + L:d]), gap_pair.append(k)
+            elif gn + gm:
+                runs.append(gn + gm)
+        closed.append(runs)
+
+    def pack(ts_, ps_):
+        to = np.concatenate([[0], np.cumsum([len(x) for x in ts_])])
+        po = np.concatenate([[0], np.cumsum([len(x) for x in ps_])])
+        cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0)).astype(np.int8)  # noqa: E731
+        return {"text": cat(ts_), "pattern": cat(ps_), "pairs": [(int(to[k]), len(ts_[k]), int(po[k]), len(ps_[k])) for k in range(len(ts_))]}
+    return pack(lt, lp), pack(rt, rp), pack(gt, gp), np.array(gap_pair, dtype=np.int64), np.array(seed_score), closed
+
+
+def chain_bands(w, chains, margin: int = 16):
+    """The narrowest band per pair that holds the chain's diagonals, the origin's and the far corner's, +- margin."""
+    out = []
+    for (_, n, _, m), ch in zip(w["pairs"], chains):
+        d = [ts - ps for ts, ps, _ in ch] + [0, n - m]
+        out.append((min(d) - margin, max(d) + margin))
+    return out
+
+
+def chain_rows(args, engine, w, chains, go: int, ge: int, xdrop) -> dict:
+    """(a), (b) and (c) of --mode chain, alternated round by round."""
+    import torch
+    pairs = w["pairs"]
+    x = engine.NO_XDROP if xdrop is None else xdrop
+    left, right, gaps, gap_pair, seed_score, closed = chain_pieces(w, chains)
+    bands = chain_bands(w, chains)
+    dev = {k: (torch.from_numpy(v["text"]).cuda(), torch.from_numpy(v["pattern"]).cuda()) for k, v in (("w", w), ("l", left), ("r", right), ("g", gaps))}
+    sc = {"chains": engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, xdrop=x, chains=chains),
+          "left": engine.Scorer(0, w["S"], go, left["pairs"], gap_extend=ge, xdrop=x),
+          "right": engine.Scorer(0, w["S"], go, right["pairs"], gap_extend=ge, xdrop=x),
+          "gaps": engine.Scorer(0, w["S"], go, gaps["pairs"], gap_extend=ge),
+          "band_at": engine.Scorer(0, w["S"], go, pairs, gap_extend=ge, bands=bands)}
+    ptr = {"chains": dev["w"], "band_at": dev["w"], "left": dev["l"], "right": dev["r"], "gaps": dev["g"]}
+    run = {k: (lambda k=k: sc[k].run(ptr[k][0].data_ptr(), ptr[k][1].data_ptr())) for k in sc}
+    gshape = np.array([(p[3], p[1]) for p in gaps["pairs"]], dtype=np.int64).reshape(-1, 2)
+    row = {"name": w["name"] + ("_xdrop" if xdrop is not None else "_no_xdrop"), "pairs": len(pairs), "cells": sum(p[1] * p[3] for p in pairs),
+           "gap_open": go, "gap_extend": ge, "xdrop": xdrop, "scorers": {k: s.info() for k, s in sc.items()},
+           "seeds_per_pair": round(float(np.mean([len(c) for c in chains])), 1), "seed_columns_per_pair": round(float(np.mean([sum(s[2] for s in c) for c in chains])), 1),
+           "gap_items": len(gaps["pairs"]), "gap_rows_mean": round(float(gshape[:, 0].mean()), 1), "gap_columns_mean": round(float(gshape[:, 1].mean()), 1),
+           "gap_columns_max": int(gshape[:, 1].max()), "gap_rows_max": int(gshape[:, 0].max()),
+           "piece_cells": int(sum(p[1] * p[3] for p in gaps["pairs"] + left["pairs"] + right["pairs"])),
+           "band_width_mean": round(float(np.mean([hi - lo + 1 for lo, hi in bands])), 1)}
+    res = {}
+    for _ in range(2):  # warm-up
+        for k in sc:
+            run[k]()
+            res[k] = sc[k].results().copy()
+    want = res["left"]["score"].astype(np.int64) + res["right"]["score"] + seed_score
+    np.add.at(want, gap_pair, res["gaps"]["score"])
+    want -= np.array([sum(go + (k - 1) * ge for k in runs) for runs in closed], dtype=np.int64)
+    g = res["chains"]
+    assert (g["score"] == want).all(), "a chained score differs from the composition"
+    sd0 = np.array([c[0] for c in chains], dtype=np.int64)
+    end = np.array([(c[-1][0] + c[-1][2], c[-1][1] + c[-1][2]) for c in chains], dtype=np.int64)
+    assert (g["begin_text"] == sd0[:, 0] - res["left"]["end_text"]).all() and (g["begin_pattern"] == sd0[:, 1] - res["left"]["end_pattern"]).all()
+    assert (g["end_text"] == end[:, 0] + res["right"]["end_text"]).all() and (g["end_pattern"] == end[:, 1] + res["right"]["end_pattern"]).all()
+    row["chained_scores_equal_the_composition"] = True
+    row["chains_reach_both_corners"] = int(((g["begin_text"] == 0) & (g["begin_pattern"] == 0)).sum()), int(sum(
+        int(a["end_text"]) == p[1] and int(a["end_pattern"]) == p[3] for a, p in zip(g, pairs)))
+    row["band_at_scores_equal_chains"] = int((res["band_at"]["score"] == g["score"]).sum())
+    ms = {"chains": [], "composition": [], "band_at": []}
+
+    def composed():
+        run["left"]()
+        run["right"]()
+        run["gaps"]()
+    for _ in range(args.rounds):
+        ms["chains"].append(timed(run["chains"], lambda: sc["chains"].results()))
+        ms["composition"].append(timed(composed, lambda: (sc["left"].results(), sc["right"].results(), sc["gaps"].results())))
+        ms["band_at"].append(timed(run["band_at"], lambda: sc["band_at"].results()))
+    for k, v in ms.items():
+        row[k + "_run"] = stats(v)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    # the step model: the gaps as global pairs and the ends as extension pairs, each at its scorer's rows per lane, over
+    # the band-at global program on the pairs' bands
+    Rg, Re = row["scorers"]["gaps"]["rows_per_lane"], max(row["scorers"]["left"]["rows_per_lane"], 1)
+    affine = go != ge
+    m_gaps = model_cost(gaps["pairs"], Rg, False, affine)
+    m_ends = model_cost(left["pairs"] + right["pairs"], Re, True, affine)
+    m_band = band_at_model_cost(pairs, bands, row["scorers"]["band_at"]["rows_per_lane"])
+    spread = max(ms["composition"]) - min(ms["composition"])
+    row["chains_over_composition"] = round(med["chains"] / med["composition"], 4)
+    row["composition_spread_ms"] = round(spread, 3)
+    row["chains_within_composition_plus_its_spread"] = bool(med["chains"] <= med["composition"] + spread)
+    row["chains_over_band_at"] = round(med["chains"] / med["band_at"], 4)
+    row["model_chains_over_band_at"] = round((m_gaps + m_ends) / m_band, 4)
+    row["model_gap_share_of_chains"] = round(m_gaps / (m_gaps + m_ends), 4)
+    # what the model charges a mean gap item against the cells it holds: n + 63 steps of one strip for rows x n cells
+    nbar, mbar = float(gshape[:, 1].mean()), float(gshape[:, 0].mean())
+    row["gap_item_steps_mean"] = round(nbar + 63, 1)
+    row["gap_item_lane_steps_used"] = round(nbar * mbar / ((nbar + 63) * 64 * Rg), 4)
+    row["chains_us_per_gap_item"] = round(med["chains"] * 1e3 / max(len(gaps["pairs"]), 1), 4)
+    for s in sc.values():
+        s.close()
+    return row
+
+
+def chain_aligned_row(args, engine, w, chains, go: int, ge: int, xdrop) -> dict:
+    """(d): align_pairs_affine(chains=) on 64 of the pairs beside bands= with the chain's bands, end to end."""
+    nal = min(len(w["pairs"]), 64)
+    pairs, ch = w["pairs"][:nal], chains[:nal]
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in pairs]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in pairs]
+    bands = chain_bands(dict(w, pairs=pairs), ch)
+    x = engine.NO_XDROP if xdrop is None else xdrop
+    rounds = max(3, args.rounds // 2)
+    a, got = aligned_stats(engine, lambda: engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, xdrop=x, chains=ch), rounds)
+    b, alt = aligned_stats(engine, lambda: engine.align_pairs_affine(0, texts, pats, w["S"], go, ge, bands=bands), rounds)
+    sc = engine.score_batch(0, texts, pats, w["S"], go, gap_extend=ge, xdrop=x, chains=ch)
+    assert [r["score"] for r in got] == sc["score"].tolist(), "the chains aligner's scores differ from the chains scorer's"
+    full = sum(64 * ((p[1] + 126) // 64) * 256 * -(-p[3] // 512) for p in pairs)
+    return {"name": w["name"] + "_aligned", "pairs": nal, "gap_open": go, "gap_extend": ge, "xdrop": xdrop, "chains": a, "band_at": b,
+            "full_rectangle_dir_bytes": full, "equal_scores": int(sum(r["score"] == q["score"] for r, q in zip(got, alt))),
+            "equal_strings": int(sum(r["aligned_text"] == q["aligned_text"] and r["aligned_pattern"] == q["aligned_pattern"] for r, q in zip(got, alt))),
+            "chains_over_band_at_wall": round(a["end_to_end_wall"]["median_ms"] / b["end_to_end_wall"]["median_ms"], 4),
+            "chains_over_band_at_arena": round(a["arena_bytes"] / max(b["arena_bytes"], 1), 4)}
+
+
 def width_model_cost(pairs, width: int, R: int, local: bool) -> int:
     """The planner's instruction count of a banded pair (sa_score_plan.h: band_ext, band_window_at): the affine
     step of the local (an extension) or the global program, charged jmax - jmin + 64 times per strip that holds
@@ -1023,7 +1217,7 @@ def main() -> int:
     ap.add_argument("--exit-gap", type=int, nargs=2, default=[16, 4], metavar=("OPEN", "EXTEND"),
                     help="--mode extend: the penalties of the early-exit comparison")
     ap.add_argument("--xdrop", type=int, default=100, help="--mode extend: the X-drop of the early-exit comparison")
-    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds"], default=None,
+    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds", "chain"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
                          "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload; "
                          "mapped: the band-at fit scorer around each read's true offset against the unbanded fit scorer "
@@ -1031,7 +1225,9 @@ def main() -> int:
                          "extend: the extension scorers against the local ones, with and without an X-drop "
                          "(profiles/r17/score_extend_bench.json); "
                          "seeds: the seeds scorer and aligner against two extension calls on host-reversed halves and "
-                         "against the fit scorer (profiles/r18/score_seeds_bench.json)")
+                         "against the fit scorer (profiles/r18/score_seeds_bench.json); "
+                         "chain: the chains scorer and aligner on 10000-letter reads against the composition of existing calls "
+                         "and against the band-at global scorer (profiles/r22/score_chain_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--width", type=int, nargs="+", default=None,
@@ -1041,7 +1237,7 @@ def main() -> int:
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
     if args.rounds is None:
-        args.rounds = 7 if args.mode in ("extend", "seeds") else 5
+        args.rounds = 7 if args.mode in ("extend", "seeds", "chain") else 5
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
@@ -1049,6 +1245,7 @@ def main() -> int:
                                                     ("r16", "score_mapped_bench.json") if args.mode == "mapped" else
                                                     ("r21", "score_extend_band_bench.json") if args.mode == "extend" and args.width else
                                                     ("r21", "score_seeds_band_bench.json") if args.mode == "seeds" and args.width else
+                                                    ("r22", "score_chain_bench.json") if args.mode == "chain" else
                                                     ("r17", "score_extend_bench.json") if args.mode == "extend" else
                                                     ("r18", "score_seeds_bench.json") if args.mode == "seeds" else ("r09", "score_bench.json")))
     if args.tree:
@@ -1131,6 +1328,17 @@ def main() -> int:
                     report["workloads"].append(row)
                     print(json.dumps(row), flush=True)
         row = seeds_aligned_row(args, engine, w, seeds, args.gap_open, ge, args.xdrop)
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
+    elif args.mode == "chain":
+        w = chain_workload(args.small)
+        ge = args.gap_extend if args.gap_extend is not None else 2
+        chains = exact_match_chains(engine, w, args.gap_open, ge)
+        for xdrop in (None, args.xdrop):
+            row = chain_rows(args, engine, w, chains, args.gap_open, ge, xdrop)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+        row = chain_aligned_row(args, engine, w, chains, args.gap_open, ge, args.xdrop)
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
     elif args.mode == "ends":
