@@ -22,6 +22,8 @@
 #include <utility>
 #include <vector>
 
+struct sa_align_spec;  // sa_hip.h: what alignSequencesGPUCigar takes
+
 namespace SequenceAlignment
 {
 enum programArgs
@@ -258,6 +260,26 @@ uint64_t scoreSequencesGPUChains(const Request *requests, uint64_t numRequests, 
 uint64_t alignSequencesGPUChains(const Request *requests, Response *responses, uint64_t numRequests, int device,
                                  int gapOpen, int gapExtend, int xdrop, const uint64_t *seedCount,
                                  const uint64_t *seedTextPos, const uint64_t *seedPatternPos, const uint64_t *seedLength);
+
+/// Extension: CIGAR output (sa_align_pairs_cigar; sa_hip.h has the definition). `spec` (sa_hip.h sa_align_spec) names
+/// the align...GPU... function the call stands for by that function's arguments: gap_open and gap_extend alone
+/// alignSequencesGPUAffine, band >= 0 ...Banded, bands ...BandAt, extend with xdrop ...Extend, width >= 0 with it
+/// ...ExtendBand, seeds (one per request) ...Seeds or ...SeedsBand, seeds with chain_off (numRequests + 1 offsets
+/// into them) ...Chains. The mode is Request::alignmentType's, or with freeEnds 0..15 the ends-free mode of those
+/// flags, and an extension's is global. Every request is aligned exactly as that function aligns it; instead of
+/// two strings a CigarResponse gets the run-length ops of the alignment, BAM-packed (length << 4 | code; with
+/// `eqx` = 7 and X 8, else M 0; I 1: the pattern has a letter the text lacks; D 2), and the column counts, which
+/// are counted from the letters whatever `eqx` is. The strings stay on the device and are never copied.
+/// Returns 0, or 1 with the message on stdout.
+struct CigarResponse
+{
+    int score = 0;
+    uint64_t numAlignmentBytes = 0, startInAlignedText = 0, startInAlignedPattern = 0;
+    std::vector<uint32_t> ops;
+    uint32_t matches = 0, mismatches = 0, textGapLetters = 0, patternGapLetters = 0, gapOpens = 0;
+};
+uint64_t alignSequencesGPUCigar(const Request *requests, CigarResponse *responses, uint64_t numRequests, int device,
+                                const ::sa_align_spec &spec, bool eqx = true, int freeEnds = -1);
 
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);

@@ -627,9 +627,82 @@ int sa_align_pairs_chains(const sa_params *params, int32_t gap_open, int32_t gap
                           const uint64_t *chain_off, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
                           char *const *aligned_text, char *const *aligned_pattern);
 
+/* ---- CIGAR output: run-length alignments from every sa_align_pairs_* variant -------------------- */
+
+/* Take a pair's aligned strings at and ap exactly as the sa_align_pairs_* function of the same variant returns
+ * them: L = num_alignment_bytes columns, the gap letter is alphabet[alphabet_size]. Column c is
+ *   I  if at[c] is the gap letter: the pattern (the query) has a letter the text lacks
+ *   D  if ap[c] is the gap letter
+ *   otherwise, under SA_CIGAR_EQX: = if at[c] == ap[c] as characters, else X
+ *   otherwise, under SA_CIGAR_M (flags = 0): M
+ * The CIGAR is the run-length encoding of that column sequence in forward order, each op one BAM-packed
+ * uint32: len << 4 | code, with M = 0, I = 1, D = 2, = = 7, X = 8.
+ * Identity: (G1) the ops and the counts are this function of the strings and nothing else, so every tie rule and
+ * quirk of every mode carries over. sa_cigar_from_strings below is that function on the host.
+ * sa_align_pairs_cigar runs the variant that `spec` names (sa_align_spec: the arguments of the sa_align_pairs_*
+ * function it stands for) through that function's own planner, fill and walks, leaves the strings on the device,
+ * and encodes them there: cigar_encode_kernel, one wave per pair, once to count each pair's ops and once to write
+ * them into an array of exactly the counted size, which one copy brings to the host. results[k] holds pair k's
+ * sa_result fields verbatim, where its ops lie in the call's op array (ops_off is the exclusive sum of num_ops in
+ * pair order) and the counts: matches and mismatches are counted from the letters, under SA_CIGAR_M too;
+ * text_gap_letters are the columns of I, pattern_gap_letters those of D, and gap_opens the runs of I plus the runs
+ * of D; the four column counts add up to num_alignment_bytes. *out owns the op array until sa_cigars_destroy; on
+ * failure it stays NULL.
+ * Refusals: SA_ERR_INVALID before any device call, the message naming the fields, for spec == NULL, out == NULL
+ * with num_pairs > 0, flags other than SA_CIGAR_M or SA_CIGAR_EQX, band with bands, a band of either kind with
+ * extend, width without extend, seeds without extend, chain_off without seeds and chain_off with width.
+ * SA_ERR_UNSUPPORTED for a pair with text_len + pattern_len >= 2^28: a run must fit 28 bits. Everything else is
+ * refused as the named variant refuses it, in that variant's words.
+ * sa_cigar_from_strings serves the callers of the plans and of sa_align_pair, which have no device CIGAR: ops
+ * (cap entries) may be NULL with cap 0, counts may be NULL; a cap below the number of ops is SA_ERR_INVALID with
+ * counts->num_ops still set to the number needed. It fills the counts and num_alignment_bytes = len; score,
+ * status, the starts and ops_off are 0. sa_cigar_format writes the ops as text ("12=1X3I", NUL-terminated) and
+ * returns SA_ERR_INVALID when cap bytes do not hold it or an op's code is none of the five. */
+enum sa_cigar_flags { SA_CIGAR_M = 0, SA_CIGAR_EQX = 1 };
+enum sa_cigar_op { SA_CIGAR_OP_M = 0, SA_CIGAR_OP_I = 1, SA_CIGAR_OP_D = 2, SA_CIGAR_OP_EQ = 7, SA_CIGAR_OP_X = 8 };
+
+typedef struct sa_align_spec {      /* which sa_align_pairs_* function this call stands for */
+    int32_t gap_open, gap_extend;
+    int32_t band;                   /* >= 0: _banded; -1 none */
+    int32_t xdrop;                  /* with extend != 0: SA_NO_XDROP or 0 .. 2^30 - 1 */
+    int32_t width;                  /* >= 0: _extend_band / _seeds_band; -1 none */
+    int32_t extend;                 /* 0 / 1: extension alignment (required by seeds and chain_off) */
+    const sa_band *bands;           /* non-NULL: _band_at */
+    const sa_seed *seeds;           /* non-NULL: _seeds, or with chain_off _chains */
+    const uint64_t *chain_off;
+} sa_align_spec;
+
+typedef struct sa_cigar_result {
+    int32_t score, status;
+    uint64_t num_alignment_bytes, start_text, start_pattern;   /* sa_result's, verbatim */
+    uint64_t ops_off;               /* first op of this pair in the call's op array */
+    uint32_t num_ops;
+    uint32_t matches, mismatches;   /* under SA_CIGAR_M too: counted from the letters */
+    uint32_t text_gap_letters;      /* columns of I */
+    uint32_t pattern_gap_letters;   /* columns of D */
+    uint32_t gap_opens;             /* runs of I plus runs of D */
+} sa_cigar_result;
+
+typedef struct sa_cigars sa_cigars; /* owns the call's host op array */
+
+int sa_align_pairs_cigar(const sa_params *params, const sa_align_spec *spec, int32_t flags, const sa_host_pair *pairs,
+                         int64_t num_pairs, int device, sa_cigar_result *results, sa_cigars **out);
+const uint32_t *sa_cigars_ops(const sa_cigars *cigars);   /* NULL when there are 0 ops */
+uint64_t sa_cigars_num_ops(const sa_cigars *cigars);
+int sa_cigars_destroy(sa_cigars *cigars);
+
+/* host only, no device call */
+int sa_cigar_from_strings(const char *at, const char *ap, uint64_t len, char gap_letter, int32_t flags, uint32_t *ops,
+                          uint64_t cap, sa_cigar_result *counts);
+int sa_cigar_format(const uint32_t *ops, uint64_t num_ops, char *buf, uint64_t cap);
+/* For benches and tests only, as sa_affine_last_stats below (which reports the fill and the walks of the call as
+ * for the string call): the calling thread's last sa_align_pairs_cigar. Device time of the two encoder passes in
+ * milliseconds, the bytes of ops copied to the host, and the bytes of the two string arenas that were not. */
+int sa_cigar_last_stats(double *encode_ms, uint64_t *ops_bytes, uint64_t *string_bytes_not_copied);
+
 /* For benches and tests only, not a stable part of the ABI (it may change or go without a new
  * SA_ABI_VERSION). Debug record of the calling thread's last sa_align_pairs_affine, sa_align_pairs_banded, sa_align_pairs_band_at, sa_align_pairs_extend, sa_align_pairs_seeds,
- * sa_align_pairs_extend_band, sa_align_pairs_seeds_band, sa_align_pairs_chains or sa_search_affine (k > 0): device
+ * sa_align_pairs_extend_band, sa_align_pairs_seeds_band, sa_align_pairs_chains, sa_align_pairs_cigar or sa_search_affine (k > 0): device
  * time of the traced fills and of the walks in milliseconds (summed over the chunks), the bytes of the
  * direction arena and the number of chunks. Each pointer may be NULL. */
 int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes, int32_t *num_chunks);

@@ -446,6 +446,41 @@ uint64_t SequenceAlignment::alignSequencesGPUChains(const Request *requests, Res
     return alignRequests(v, requests, responses, numRequests, device);
 }
 
+uint64_t SequenceAlignment::alignSequencesGPUCigar(const Request *requests, CigarResponse *responses, uint64_t numRequests, int device,
+                                                   const sa_align_spec &spec, bool eqx, int freeEnds)
+{
+    if (numRequests == 0) return 0;
+    if (freeEnds != -1 && !endsFlagsOk(freeEnds, "alignSequencesGPUCigar")) return 1;
+    Variant v("alignSequencesGPUCigar", spec.gap_open, spec.gap_extend);
+    if (spec.extend) v.xdrop = &spec.xdrop;  // an extension's mode is SA_GLOBAL, whatever alignmentType says
+    if (freeEnds != -1) v.ends = &freeEnds;
+    Packed k;
+    if (!pack(v, requests, nullptr, numRequests, &k)) return 1;
+    std::vector<sa_cigar_result> res(numRequests);
+    sa_cigars *cigars = nullptr;
+    const int rc = sa_align_pairs_cigar(&k.params[0], &spec, eqx ? SA_CIGAR_EQX : SA_CIGAR_M, k.pairs.data(), (int64_t)numRequests, device,
+                                        res.data(), &cigars);
+    if (rc != SA_OK) return reportFailure(rc);
+    const uint32_t *ops = sa_cigars_ops(cigars);
+    for (uint64_t i = 0; i < numRequests; ++i)
+    {
+        CigarResponse &rs = responses[i];
+        rs.score = res[i].score;
+        rs.numAlignmentBytes = res[i].num_alignment_bytes;
+        rs.startInAlignedText = res[i].start_text;
+        rs.startInAlignedPattern = res[i].start_pattern;
+        rs.ops.clear();
+        if (res[i].num_ops) rs.ops.assign(ops + res[i].ops_off, ops + res[i].ops_off + res[i].num_ops);
+        rs.matches = res[i].matches;
+        rs.mismatches = res[i].mismatches;
+        rs.textGapLetters = res[i].text_gap_letters;
+        rs.patternGapLetters = res[i].pattern_gap_letters;
+        rs.gapOpens = res[i].gap_opens;
+    }
+    sa_cigars_destroy(cigars);
+    return 0;
+}
+
 uint64_t SequenceAlignment::scoreSequencesGPUSeeds(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
                                                    int xdrop, const uint64_t *seedTextPos, const uint64_t *seedPatternPos,
                                                    const uint64_t *seedLength, int *scores)

@@ -8,6 +8,8 @@
 
 namespace sa {
 
+struct CigarSink;  // sa_cigar.h
+
 // Aligns `np` pairs addressed in the device arenas d_text / d_pattern (alphabet indices) on `device`
 // under the gap model of `spec`: the traced Gotoh fill and the walk, chunk by chunk of the work order
 // (sa_trace_plan.h), on the null stream; synchronous. results: np entries. aligned_text /
@@ -15,8 +17,15 @@ namespace sa {
 // `spec` banded: inside the diagonal band of that half-width (sa_align_pairs_banded); band_at: inside
 // bands[p] for pair p (sa_align_pairs_band_at; null bands with pairs is SA_ERR_INVALID); extend: extension
 // alignment under that X-drop (sa_align_pairs_extend); seeded: align_seeds_device below.
+// `cigar` (sa_align_pairs_cigar; aligned_text and aligned_pattern are then null): the strings are made on the device
+// as for a call that takes them, stay there, and are encoded into the sink's ops and counts before the call returns.
 int align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
+                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern,
+                        CigarSink *cigar = nullptr);
+
+// Every sa_align_pairs_*: the host pairs packed into two arenas and uploaded, then align_affine_device.
+int align_host_pairs(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
+                     char *const *aligned_text, char *const *aligned_pattern, CigarSink *cigar = nullptr);
 
 // Seed extension (sa_hip.h sa_score_batch_seeds): seeds_combine_kernel (sa_score.hip), one wave per pair
 // after the items' fill, shared by the seeds scorer and the seeds aligner. It sums the seed's scores, flags
@@ -55,12 +64,14 @@ void launch_chains_combine(const ChainsCombineArgs &a, int64_t np, void *stream)
 // sa_align_pairs_seeds on device arenas: the traced fill of the work items, the combine and the seeded walk,
 // chunk by chunk (sa_trace_plan.h SeedTracePlan); arguments as align_affine_device, the seeds are spec.seeds.
 int align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                       const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
+                       const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern,
+                       CigarSink *cigar = nullptr);
 
 // sa_align_pairs_chains on device arenas: per chunk (sa_trace_plan.h ChainTracePlan) the traced fills of the gap
 // items and of the end items, the combine, the walk of every item at once and the join of the pairs; arguments as
 // align_affine_device, the chains are spec.seeds and spec.chain_off.
 int align_chains_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern);
+                        const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern,
+                        CigarSink *cigar = nullptr);
 
 }  // namespace sa

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sa_affine.h"
+#include "sa_cigar.h"
 #include "sa_hip.h"
 #include "sa_host.h"
 #include "sa_score_wave.h"
@@ -627,6 +628,7 @@ struct TracedCall {
     const void *d_text, *d_pattern;
     sa_result *results;
     char *const *aligned_text, *const *aligned_pattern;
+    CigarSink *cigar = nullptr;  // set: the strings stay on the device and are encoded there (aligned_* null)
 };
 
 // The device side of one traced run. The driver owns what every aligner has; the aligner's setup adds its
@@ -649,7 +651,9 @@ struct TracedRun {
 // The traced run both aligners are: the checks, `plan` (which fills `pl`), the statistics, the common buffers,
 // `setup`, then chunk after chunk a traced fill and a walk that reuses the arena, timed by three events, and the
 // results and strings brought back. A pair's string is a head piece at the start of its slot and a tail piece at
-// the slot's end.
+// the slot's end. With a CIGAR sink the arenas are allocated and written as for a call with strings, neither is
+// copied to the host, and once no check below has failed the encoder (sa_cigar.hip) reads them where they lie, on
+// the same stream: pl.string_bytes covers the whole call, so every chunk's pairs are still there.
 template <typename PLAN, typename SETUP>
 int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
 {
@@ -662,15 +666,16 @@ int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
     std::string err;
     if (int rc = plan(&err)) return fail(rc, err);
     if (!c.P->alphabet) return fail(SA_ERR_INVALID, who + ": params->alphabet is null");
+    if (c.cigar && c.aligned_text) return fail(SA_ERR_INVALID, who + ": a call takes strings or a CIGAR sink, not both");
     g_stats = AffineStats();
     g_stats.arena_bytes = pl.arena_bytes;
     g_stats.chunks = (int32_t)pl.num_chunks();
-    if (np == 0) return SA_OK;
+    if (np == 0) return c.cigar ? cigar_encode(nullptr, nullptr, nullptr, 0, nullptr, nullptr, {}, 0, c.cigar) : SA_OK;
     if ((!c.d_text || !c.d_pattern) && pl.score.input_bytes) return fail(SA_ERR_INVALID, who + ": null arena");
 
     TracedRun r;
     r.A = pl.score.A;
-    const bool strings = c.aligned_text != nullptr;
+    const bool strings = c.aligned_text != nullptr || c.cigar;
     int rc;
     if ((rc = r.ws.alloc(&r.d_table, 32 * 32 * 4)) || (rc = r.ws.alloc(&r.d_rows, (size_t)pl.score.grid * pl.score.row_stride * 8)) ||
         (rc = r.ws.alloc(&r.d_ctrl, 256)) || (rc = r.ws.alloc(&r.d_dirs, pl.arena_bytes)) || (rc = r.ws.alloc(&r.d_alpha, 64)) ||
@@ -729,6 +734,12 @@ int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
     for (int64_t p = 0; p < np; ++p)
         if (c.results[p].status != SA_OK)
             return fail(SA_ERR_HIP, std::string(c.walk) + " of pair " + std::to_string(p) + " did not end within " + c.moves);
+    if (c.cigar)
+    {
+        std::vector<CigarSlot> slots((size_t)np);
+        for (int64_t p = 0; p < np; ++p) slots[p] = CigarSlot{pl.slot_off[p], c.pairs[p].text_len + c.pairs[p].pattern_len};
+        return cigar_encode(st, r.d_ot, r.d_op, pl.string_bytes, r.d_results, r.d_tail, slots, c.P->alphabet[r.A], c.cigar);
+    }
     if (strings && pl.string_bytes)
     {
         std::vector<char> ht(pl.string_bytes), hp(pl.string_bytes);
@@ -758,10 +769,11 @@ int traced_run(const TracedCall &c, const TracePlan &pl, PLAN plan, SETUP setup)
 }  // namespace
 
 int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern,
+                            CigarSink *cigar)
 {
-    if (spec.chained) return align_chains_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern);
-    if (spec.seeded) return align_seeds_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern);
+    if (spec.chained) return align_chains_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern, cigar);
+    if (spec.seeded) return align_seeds_device(P, spec, pairs, np, device, d_text, d_pattern, results, aligned_text, aligned_pattern, cigar);
     TracePlan pl;
     TracedWaveArgs fa = {};
     WalkArgs wa;
@@ -837,20 +849,20 @@ int sa::align_affine_device(const sa_params *P, const WaveSpec &spec, const sa_p
         return SA_OK;
     };
     return traced_run({"affine aligner", "affine walk", "text_len + pattern_len moves", P, pairs, np, device, d_text, d_pattern, results,
-                       aligned_text, aligned_pattern},
+                       aligned_text, aligned_pattern, cigar},
                       pl, plan, setup);
 }
 
 // every sa_align_pairs_*: the host pairs packed into two arenas, then the device path
-static int align_host_pairs(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
-                            char *const *aligned_text, char *const *aligned_pattern)
+int sa::align_host_pairs(const sa_params *P, const WaveSpec &spec, const sa_host_pair *pairs, int64_t np, int device, sa_result *results,
+                         char *const *aligned_text, char *const *aligned_pattern, CigarSink *cigar)
 {
     const char *const fn = spec.chained ? "sa_align_pairs_chains" : spec.seeded ? "sa_align_pairs_seeds" : "sa_align_pairs_affine";
     if (!P || np < 0 || (np > 0 && (!pairs || !results)) || ((aligned_text == nullptr) != (aligned_pattern == nullptr)))
         return fail(SA_ERR_INVALID, std::string(fn) + ": null argument");
     HostArenas in;
     if (int rc = upload_host_pairs(fn, pairs, np, device, &in)) return rc;
-    return align_affine_device(P, spec, in.pairs.data(), np, device, in.text.p, in.pattern.p, results, aligned_text, aligned_pattern);
+    return align_affine_device(P, spec, in.pairs.data(), np, device, in.text.p, in.pattern.p, results, aligned_text, aligned_pattern, cigar);
 }
 
 extern "C" {
@@ -926,7 +938,8 @@ int sa_affine_last_stats(double *fill_ms, double *walk_ms, uint64_t *arena_bytes
 }  // extern "C"
 
 int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                           const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+                           const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern,
+                           CigarSink *cigar)
 {
     SeedTracePlan pl;
     TracedWaveArgs fa = {};
@@ -1007,12 +1020,13 @@ int sa::align_seeds_device(const sa_params *P, const WaveSpec &spec, const sa_pa
         return SA_OK;
     };
     return traced_run({"seeds aligner", "seeded walk", "its halves' moves", P, pairs, np, device, d_text, d_pattern, results, aligned_text,
-                       aligned_pattern},
+                       aligned_pattern, cigar},
                       pl, plan, setup);
 }
 
 int sa::align_chains_device(const sa_params *P, const WaveSpec &spec, const sa_pair *pairs, int64_t np, int device, const void *d_text,
-                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern)
+                            const void *d_pattern, sa_result *results, char *const *aligned_text, char *const *aligned_pattern,
+                            CigarSink *cigar)
 {
     ChainTracePlan pl;
     TracedWaveArgs fe = {}, fg = {};  // the fill of the end items and of the gap items
@@ -1140,6 +1154,6 @@ int sa::align_chains_device(const sa_params *P, const WaveSpec &spec, const sa_p
         return SA_OK;
     };
     return traced_run({"chains aligner", "chained walk", "its pieces' moves", P, pairs, np, device, d_text, d_pattern, results, aligned_text,
-                       aligned_pattern},
+                       aligned_pattern, cigar},
                       pl, plan, setup);
 }

@@ -46,7 +46,12 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_score_batch_seeds", "sa_scorer_create_seeds", "sa_scorer_fetch_seeds", "sa_align_pairs_seeds",
            "sa_score_batch_extend_band", "sa_scorer_create_extend_band", "sa_align_pairs_extend_band",
            "sa_score_batch_seeds_band", "sa_scorer_create_seeds_band", "sa_align_pairs_seeds_band",
-           "sa_score_batch_chains", "sa_scorer_create_chains", "sa_align_pairs_chains")
+           "sa_score_batch_chains", "sa_scorer_create_chains", "sa_align_pairs_chains",
+           "sa_align_pairs_cigar", "sa_cigars_ops", "sa_cigars_num_ops", "sa_cigars_destroy", "sa_cigar_from_strings",
+           "sa_cigar_format", "sa_cigar_last_stats")
+# flags of align_pairs_cigar and cigar_from_strings (sa_hip.h sa_cigar_flags) and the BAM op codes
+CIGAR_M, CIGAR_EQX = 0, 1
+CIGAR_OPS = {0: "M", 1: "I", 2: "D", 7: "=", 8: "X"}
 
 
 class SaParams(ctypes.Structure):
@@ -71,6 +76,20 @@ class SaScoreResult(ctypes.Structure):
 
 class SaBand(ctypes.Structure):
     _fields_ = [("lo", ctypes.c_int32), ("hi", ctypes.c_int32)]
+
+
+class SaAlignSpec(ctypes.Structure):
+    _fields_ = [("gap_open", ctypes.c_int32), ("gap_extend", ctypes.c_int32), ("band", ctypes.c_int32),
+                ("xdrop", ctypes.c_int32), ("width", ctypes.c_int32), ("extend", ctypes.c_int32),
+                ("bands", ctypes.c_void_p), ("seeds", ctypes.c_void_p), ("chain_off", ctypes.c_void_p)]
+
+
+class SaCigarResult(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("num_alignment_bytes", ctypes.c_uint64),
+                ("start_text", ctypes.c_uint64), ("start_pattern", ctypes.c_uint64), ("ops_off", ctypes.c_uint64),
+                ("num_ops", ctypes.c_uint32), ("matches", ctypes.c_uint32), ("mismatches", ctypes.c_uint32),
+                ("text_gap_letters", ctypes.c_uint32), ("pattern_gap_letters", ctypes.c_uint32),
+                ("gap_opens", ctypes.c_uint32)]
 
 
 class SaError(RuntimeError):
@@ -174,6 +193,17 @@ def _load():
                                           ctypes.POINTER(P)]
     L.sa_align_pairs_chains.argtypes = [ctypes.POINTER(SaParams), I32, I32, I32, P, P, P, ctypes.c_int64, I,
                                         ctypes.POINTER(SaResult), P, P]
+    L.sa_align_pairs_cigar.argtypes = [ctypes.POINTER(SaParams), ctypes.POINTER(SaAlignSpec), I32, P, ctypes.c_int64, I,
+                                       ctypes.POINTER(SaCigarResult), ctypes.POINTER(P)]
+    L.sa_cigars_ops.argtypes = [P]
+    L.sa_cigars_ops.restype = P
+    L.sa_cigars_num_ops.argtypes = [P]
+    L.sa_cigars_num_ops.restype = U64
+    L.sa_cigars_destroy.argtypes = [P]
+    L.sa_cigar_from_strings.argtypes = [ctypes.c_char_p, ctypes.c_char_p, U64, ctypes.c_char, I32, P, U64,
+                                        ctypes.POINTER(SaCigarResult)]
+    L.sa_cigar_format.argtypes = [P, U64, P, U64]
+    L.sa_cigar_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]
     L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
     L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -431,6 +461,110 @@ def align_pairs_affine(mode: int, texts: list[np.ndarray], patterns: list[np.nda
     if gap_extend is None and xdrop is None:  # as ever: without a gap model, align_batch on one device, band or no band
         return align_batch(mode, texts, patterns, S, gap_open, 1, None, strings)
     return _align_host_pairs(mode, texts, patterns, S, gap_open, device, None, strings, variant)
+
+
+CIGAR_COUNTS = ("matches", "mismatches", "text_gap_letters", "pattern_gap_letters", "gap_opens")
+
+
+def _align_spec(variant, gap_open: int) -> SaAlignSpec:
+    """The sa_align_spec of a variant that _variant resolved: the arguments between params and the pairs of the
+    sa_align_pairs<suffix> function, by name. Without a gap model (suffix "") the gap is linear."""
+    suffix, args, _ = variant
+    spec = SaAlignSpec(gap_open, gap_open, -1, NO_XDROP, -1, 0, None, None, None)
+    names = {"": (), "_affine": ("gap_open", "gap_extend"), "_banded": ("gap_open", "gap_extend", "band"),
+             "_band_at": ("gap_open", "gap_extend", "bands"), "_extend": ("gap_open", "gap_extend", "xdrop"),
+             "_extend_band": ("gap_open", "gap_extend", "xdrop", "width"),
+             "_seeds": ("gap_open", "gap_extend", "xdrop", "seeds"),
+             "_seeds_band": ("gap_open", "gap_extend", "xdrop", "width", "seeds"),
+             "_chains": ("gap_open", "gap_extend", "xdrop", "seeds", "chain_off")}[suffix]
+    for name, value in zip(names, args):
+        setattr(spec, name, value)
+    spec.extend = int("xdrop" in names)
+    return spec
+
+
+def cigar_format(ops) -> str:
+    """sa_cigar_format: BAM-packed ops (len << 4 | code) as text, "12=1X3I"."""
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    buf = ctypes.create_string_buffer(12 * len(ops) + 1)
+    _check(lib.sa_cigar_format(ops.ctypes.data, len(ops), buf, len(buf)))
+    return buf.value.decode()
+
+
+def cigar_from_strings(aligned_text, aligned_pattern, gap_letter="-", eqx: bool = True, cap: int | None = None) -> dict:
+    """sa_cigar_from_strings (host only, no device call): the CIGAR of two aligned strings as sa_hip.h defines it,
+    for the callers of Plan, align_pair and align_batch. `cap` (default: as many ops as there are columns) is
+    the size of the op buffer; one that is too small raises SaError. Returns cigar (uint32 ops), cigar_string,
+    num_ops and the five counts."""
+    at = aligned_text.encode() if isinstance(aligned_text, str) else bytes(aligned_text)
+    ap = aligned_pattern.encode() if isinstance(aligned_pattern, str) else bytes(aligned_pattern)
+    if len(at) != len(ap):
+        raise ValueError(f"the aligned strings have {len(at)} and {len(ap)} columns")
+    gap = gap_letter.encode() if isinstance(gap_letter, str) else bytes(gap_letter)
+    cap = len(at) if cap is None else cap
+    ops = np.zeros(max(1, cap), np.uint32)
+    res = SaCigarResult()
+    _check(lib.sa_cigar_from_strings(at, ap, len(at), gap, CIGAR_EQX if eqx else CIGAR_M, ops.ctypes.data, cap, ctypes.byref(res)))
+    ops = ops[: res.num_ops].copy()
+    d = {"cigar": ops, "cigar_string": cigar_format(ops), "num_ops": res.num_ops}
+    d.update({k: getattr(res, k) for k in CIGAR_COUNTS})
+    return d
+
+
+def align_pairs_cigar(mode: int, texts: list[np.ndarray], patterns: list[np.ndarray], S: np.ndarray, gap_open: int,
+                      gap_extend: int, device: int = 0, eqx: bool = True, band: int | None = None, bands=None,
+                      xdrop: int | None = None, seeds=None, width: int | None = None, chains=None) -> list[dict]:
+    """sa_align_pairs_cigar: the pairs aligned as align_pairs_affine aligns them under the same keywords (which are
+    resolved and refused by the same rules and words), with each alignment returned as a CIGAR instead of two
+    strings: the strings are made on the device, encoded there and never copied to the host. The dicts are those
+    of align_pairs_affine(strings=False) plus cigar (uint32 BAM ops, len << 4 | code, = and X under `eqx`, else M),
+    cigar_string, num_ops, ops_off (the pair's first op in the call's op array) and matches, mismatches,
+    text_gap_letters (columns of I), pattern_gap_letters (columns of D) and gap_opens, which are counted from the
+    letters whatever `eqx` is. Without `gap_extend` (None) the gap is linear: gap_extend = gap_open."""
+    variant = _variant(gap_open, gap_extend, band, bands, xdrop, seeds, len(texts), width, chains)
+    spec = _align_spec(variant, gap_open)
+    p, S_keep, alpha_keep = _params(mode, S, gap_open, None, 0)
+    hp, ts, ps = _host_pairs(texts, patterns)
+    n = len(ts)
+    res = (SaCigarResult * max(1, n))()
+    handle = ctypes.c_void_p()
+    _check(lib.sa_align_pairs_cigar(ctypes.byref(p), ctypes.byref(spec), CIGAR_EQX if eqx else CIGAR_M, hp, n, device, res,
+                                    ctypes.byref(handle)))
+    try:
+        total = lib.sa_cigars_num_ops(handle)
+        addr = lib.sa_cigars_ops(handle)
+        ops = np.ctypeslib.as_array(ctypes.cast(addr, ctypes.POINTER(ctypes.c_uint32)), (total,)).copy() if addr else np.zeros(0, np.uint32)
+    finally:
+        lib.sa_cigars_destroy(handle)
+    # the records as tuples of Python ints in one pass (a ctypes field read per value costs more than the rest)
+    rows = np.frombuffer(res, dtype=CIGAR_DTYPE, count=n).tolist()
+    keys = tuple(k for k in CIGAR_DTYPE.names if k != "status")
+    cap = 12 * max([r[6] for r in rows], default=0) + 1
+    buf = ctypes.create_string_buffer(cap)  # one text buffer for every pair: an op is at most 9 digits and a letter
+    base, out = ops.ctypes.data, []
+    for r in rows:
+        off, num = r[5], r[6]
+        _check(lib.sa_cigar_format(base + 4 * off, num, buf, cap))
+        d = dict(zip(keys, r[:1] + r[2:]))
+        d["cigar"] = ops[off: off + num]
+        d["cigar_string"] = buf.value.decode()
+        out.append(d)
+    return out
+
+
+# numpy view of sa_cigar_result (include/sa_hip.h), the names those of the dicts align_pairs_cigar returns
+CIGAR_DTYPE = np.dtype([("score", "<i4"), ("status", "<i4"), ("num_bytes", "<u8"), ("start_text", "<u8"), ("start_pattern", "<u8"),
+                        ("ops_off", "<u8"), ("num_ops", "<u4"), ("matches", "<u4"), ("mismatches", "<u4"),
+                        ("text_gap_letters", "<u4"), ("pattern_gap_letters", "<u4"), ("gap_opens", "<u4")])
+assert CIGAR_DTYPE.itemsize == ctypes.sizeof(SaCigarResult)
+
+
+def cigar_last_stats() -> dict:
+    """sa_cigar_last_stats: the calling thread's last align_pairs_cigar (device ms of the two encoder passes, bytes
+    of ops copied to the host, bytes of the two string arenas that were not)."""
+    e, o, s = ctypes.c_double(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _check(lib.sa_cigar_last_stats(ctypes.byref(e), ctypes.byref(o), ctypes.byref(s)))
+    return {"encode_ms": e.value, "ops_bytes": o.value, "string_bytes_not_copied": s.value}
 
 
 def affine_last_stats() -> dict:

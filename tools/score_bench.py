@@ -82,6 +82,12 @@ align_pairs_affine(chains=) on 64 of the pairs beside bands= with (c)'s bands: a
 and end-to-end wall time.
     python3 tools/score_bench.py --mode chain [--small] --out profiles/r22/score_chain_bench.json
     python3 tools/score_bench.py [--out profiles/r09/score_bench.json] [--rounds 5] [--small]
+With --mode cigar the CIGAR output (sa_hip.h: sa_align_pairs_cigar): align_pairs_affine with strings and
+align_pairs_cigar with the same keywords, alternated in one process, on the long reads of --mode chain with their
+chains (all 2048, and the first 64) and on the first 4000 reads of --mode mapped with their seeds: wall time end to
+end, the device times of the fill, the walks and the encoder, and the bytes each call copies to the host.
+    python3 tools/score_bench.py --mode cigar [--small] --out profiles/r23/score_cigar_bench.json
+
 With --mode extend --width W.. the banded extension (sa_hip.h: sa_scorer_create_extend_band,
 sa_align_pairs_extend_band) on the chimeric pairs under --exit-gap, without a drop and at --xdrop: per X, the
 unbanded extension scorer and, per width, the banded extension scorer and the band-at global scorer on {-w, w},
@@ -901,6 +907,45 @@ def chain_aligned_row(args, engine, w, chains, go: int, ge: int, xdrop) -> dict:
             "chains_over_band_at_arena": round(a["arena_bytes"] / max(b["arena_bytes"], 1), 4)}
 
 
+def cigar_row(args, engine, name: str, texts, pats, S, go: int, ge: int, kw: dict) -> dict:
+    """--mode cigar: align_pairs_affine with strings and align_pairs_cigar on the same pairs and keywords, alternated
+    round by round in this process after one warm-up each: wall time end to end (host arrays in, Python dicts out),
+    the device times of the fill, the walks and the encoder, and the bytes each call copies to the host beside its
+    per-pair records. The CIGARs are checked against cigar_from_strings of the string call's strings first."""
+    import time
+    strings = lambda: engine.align_pairs_affine(0, texts, pats, S, go, ge, **kw)  # noqa: E731
+    cigars = lambda: engine.align_pairs_cigar(0, texts, pats, S, go, ge, **kw)  # noqa: E731
+    want, got = strings(), cigars()
+    for w_, g in zip(want, got):
+        ref = engine.cigar_from_strings(w_["aligned_text"], w_["aligned_pattern"])
+        assert g["cigar_string"] == ref["cigar_string"] and g["score"] == w_["score"], "a device CIGAR differs from its strings'"
+    ms = {k: {"wall": [], "fill": [], "walk": [], "encode": []} for k in ("strings", "cigar")}
+    st = {}
+    for _ in range(args.rounds):
+        for k, call in (("strings", strings), ("cigar", cigars)):
+            t0 = time.perf_counter()
+            call()
+            ms[k]["wall"].append((time.perf_counter() - t0) * 1e3)
+            a = engine.affine_last_stats()
+            ms[k]["fill"].append(a["fill_ms"]), ms[k]["walk"].append(a["walk_ms"])
+            if k == "cigar":
+                st = engine.cigar_last_stats()
+                ms[k]["encode"].append(st["encode_ms"])
+    row = {"name": name, "pairs": len(texts), "gap_open": go, "gap_extend": ge, "keywords": sorted(kw), "cigars_equal_the_strings": True,
+           "mean_letters": round(float(np.mean([len(t) + len(p) for t, p in zip(texts, pats)])) / 2, 1),
+           "mean_ops": round(float(np.mean([g["num_ops"] for g in got])), 1)}
+    for k in ms:
+        row[k] = {"end_to_end_wall": stats(ms[k]["wall"]), "fill": stats(ms[k]["fill"]), "walk": stats(ms[k]["walk"])}
+        row[k]["non_device_ms"] = round(row[k]["end_to_end_wall"]["median_ms"] - row[k]["fill"]["median_ms"] - row[k]["walk"]["median_ms"], 3)
+    row["cigar"]["encode"] = stats(ms["cigar"]["encode"])
+    row["cigar"]["non_device_ms"] = round(row["cigar"]["non_device_ms"] - row["cigar"]["encode"]["median_ms"], 3)
+    row["strings"]["string_bytes_to_host"] = st["string_bytes_not_copied"]
+    row["cigar"]["ops_bytes_to_host"] = st["ops_bytes"]
+    row["cigar"]["string_bytes_not_copied"] = st["string_bytes_not_copied"]
+    row["cigar_over_strings_wall"] = round(row["cigar"]["end_to_end_wall"]["median_ms"] / row["strings"]["end_to_end_wall"]["median_ms"], 4)
+    return row
+
+
 def width_model_cost(pairs, width: int, R: int, local: bool) -> int:
     """The planner's instruction count of a banded pair (sa_score_plan.h: band_ext, band_window_at): the affine
     step of the local (an extension) or the global program, charged jmax - jmin + 64 times per strip that holds
@@ -1217,7 +1262,7 @@ def main() -> int:
     ap.add_argument("--exit-gap", type=int, nargs=2, default=[16, 4], metavar=("OPEN", "EXTEND"),
                     help="--mode extend: the penalties of the early-exit comparison")
     ap.add_argument("--xdrop", type=int, default=100, help="--mode extend: the X-drop of the early-exit comparison")
-    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds", "chain"], default=None,
+    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds", "chain", "cigar"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
                          "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload; "
                          "mapped: the band-at fit scorer around each read's true offset against the unbanded fit scorer "
@@ -1227,7 +1272,9 @@ def main() -> int:
                          "seeds: the seeds scorer and aligner against two extension calls on host-reversed halves and "
                          "against the fit scorer (profiles/r18/score_seeds_bench.json); "
                          "chain: the chains scorer and aligner on 10000-letter reads against the composition of existing calls "
-                         "and against the band-at global scorer (profiles/r22/score_chain_bench.json)")
+                         "and against the band-at global scorer (profiles/r22/score_chain_bench.json); "
+                         "cigar: align_pairs_cigar against align_pairs_affine with strings on the chain workload (all its reads, "
+                         "and the first 64) and on 4000 reads of the seeds workload (profiles/r23/score_cigar_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--width", type=int, nargs="+", default=None,
@@ -1237,7 +1284,7 @@ def main() -> int:
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
     if args.rounds is None:
-        args.rounds = 7 if args.mode in ("extend", "seeds", "chain") else 5
+        args.rounds = 7 if args.mode in ("extend", "seeds", "chain", "cigar") else 5
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
@@ -1246,6 +1293,7 @@ def main() -> int:
                                                     ("r21", "score_extend_band_bench.json") if args.mode == "extend" and args.width else
                                                     ("r21", "score_seeds_band_bench.json") if args.mode == "seeds" and args.width else
                                                     ("r22", "score_chain_bench.json") if args.mode == "chain" else
+                                                    ("r23", "score_cigar_bench.json") if args.mode == "cigar" else
                                                     ("r17", "score_extend_bench.json") if args.mode == "extend" else
                                                     ("r18", "score_seeds_bench.json") if args.mode == "seeds" else ("r09", "score_bench.json")))
     if args.tree:
@@ -1339,6 +1387,26 @@ def main() -> int:
             report["workloads"].append(row)
             print(json.dumps(row), flush=True)
         row = chain_aligned_row(args, engine, w, chains, args.gap_open, ge, args.xdrop)
+        report["workloads"].append(row)
+        print(json.dumps(row), flush=True)
+    elif args.mode == "cigar":
+        ge = args.gap_extend if args.gap_extend is not None else 2
+        x = engine.NO_XDROP if args.xdrop is None else args.xdrop
+        w = chain_workload(args.small)
+        chains = exact_match_chains(engine, w, args.gap_open, ge)
+        texts = [w["text"][p[0]:p[0] + p[1]] for p in w["pairs"]]
+        pats = [w["pattern"][p[2]:p[2] + p[3]] for p in w["pairs"]]
+        for count in (len(texts), 64):
+            row = cigar_row(args, engine, f"long_reads_chains_{count}", texts[:count], pats[:count], w["S"], args.gap_open, ge,
+                            {"xdrop": x, "chains": chains[:count]})
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
+        w = mapped_workload(args.small)
+        w = dict(w, pairs=w["pairs"][:4000])
+        seeds, _ = longest_match_seeds(engine, w, args.gap_open, ge)
+        texts = [w["text"][p[0]:p[0] + p[1]] for p in w["pairs"]]
+        pats = [w["pattern"][p[2]:p[2] + p[3]] for p in w["pairs"]]
+        row = cigar_row(args, engine, "mapped_seeds_4000", texts, pats, w["S"], args.gap_open, ge, {"xdrop": x, "seeds": seeds})
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
     elif args.mode == "ends":
