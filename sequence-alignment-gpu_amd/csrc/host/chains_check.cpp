@@ -9,51 +9,11 @@
 // must equal the aligner's.
 //   usage: sa_chains_check <n> <count> [seeds] [device]
 // Prints the first difference, or "OK <count>" as its last line; exit status 0 iff all equal.
-#include <algorithm>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <string>
-#include <vector>
-
-#include "SequenceAlignment.hpp"
-#include "sa_hip.h"
+// With --expected: the digest of the requests, chains and pieces (check_ref.h) and nothing of either library.
+#include "check_ref.h"
 
 namespace
 {
-const int blast[16] = {5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5};
-
-uint64_t next(uint64_t &s)
-{
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return s >> 33;
-}
-
-void scheme(SequenceAlignment::Request &r)
-{
-    r.deviceType = SequenceAlignment::programArgs::GPU;
-    r.sequenceType = SequenceAlignment::programArgs::DNA;
-    r.alignmentType = SequenceAlignment::programArgs::GLOBAL;
-    r.alphabet = SequenceAlignment::DNA_ALPHABET;
-    r.alphabetSize = SequenceAlignment::NUM_DNA_CHARS;
-    r.gapPenalty = 5;  // ignored by the extend, the affine and the chains calls
-    std::memcpy(r.scoreMatrix, blast, sizeof(blast));
-}
-
-// a request over letters [from, from + len) of `src`, forwards, or backwards from letter from + len - 1
-void slice(SequenceAlignment::Request &r, const SequenceAlignment::Request &src, uint64_t tFrom, uint64_t tLen, uint64_t pFrom,
-           uint64_t pLen, bool reversed)
-{
-    scheme(r);
-    r.textNumBytes = tLen;
-    r.patternNumBytes = pLen;
-    r.textBytes = new char[std::max<uint64_t>(tLen, 1)];
-    r.patternBytes = new char[std::max<uint64_t>(pLen, 1)];
-    for (uint64_t x = 0; x < tLen; ++x) r.textBytes[x] = src.textBytes[reversed ? tFrom + tLen - 1 - x : tFrom + x];
-    for (uint64_t x = 0; x < pLen; ++x) r.patternBytes[x] = src.patternBytes[reversed ? pFrom + pLen - 1 - x : pFrom + x];
-}
-
 // a gap rectangle with two non-empty sides: its request and where it lies
 struct GapPiece {
     uint64_t request, tFrom, tLen, pFrom, pLen;
@@ -62,6 +22,7 @@ struct GapPiece {
 
 int main(int argc, char **argv)
 {
+    const bool expectedOnly = check::takeExpected(argc, argv);
     if (argc < 3)
     {
         std::cout << "usage: sa_chains_check <n> <count> [seeds] [device]\n";
@@ -79,22 +40,22 @@ int main(int argc, char **argv)
     for (uint64_t i = 0; i < count; ++i)
     {
         SequenceAlignment::Request &r = reqs[i];
-        scheme(r);
-        r.textNumBytes = 1 + next(seed) % maxLen;
+        check::scheme(r);
+        r.textNumBytes = 1 + check::next(seed) % maxLen;
         r.textBytes = new char[r.textNumBytes];
-        for (uint64_t x = 0; x < r.textNumBytes; ++x) r.textBytes[x] = (char)(next(seed) % 4);
+        for (uint64_t x = 0; x < r.textNumBytes; ++x) r.textBytes[x] = (char)(check::next(seed) % 4);
         // the pattern: the text with substitutions, insertions and deletions, so that the path drifts
         std::vector<char> pat;
         std::vector<uint64_t> from;  // the text letter a pattern letter was copied from
         for (uint64_t x = 0; x < r.textNumBytes; ++x)
         {
-            const uint64_t roll = next(seed) % 32;
+            const uint64_t roll = check::next(seed) % 32;
             if (roll == 0) continue;  // a deletion
-            pat.push_back(roll == 1 ? (char)(next(seed) % 4) : r.textBytes[x]);
+            pat.push_back(roll == 1 ? (char)(check::next(seed) % 4) : r.textBytes[x]);
             from.push_back(x);
             if (roll == 2)
             {
-                pat.push_back((char)(next(seed) % 4));  // an insertion
+                pat.push_back((char)(check::next(seed) % 4));  // an insertion
                 from.push_back(x);
             }
         }
@@ -108,18 +69,18 @@ int main(int argc, char **argv)
         std::memcpy(r.patternBytes, pat.data(), pat.size());
         // the chain: seeds at ascending pattern letters, each where its letter came from in the text
         first[i] = ts.size();
-        const uint64_t want = 1 + next(seed) % maxSeeds;
+        const uint64_t want = 1 + check::next(seed) % maxSeeds;
         uint64_t te = 0, pe = 0;
         for (uint64_t k = 0; k < want; ++k)
         {
-            const uint64_t kind = next(seed) % 6;
-            uint64_t p0 = pe + (kind == 0 ? 0 : next(seed) % (1 + (pat.size() - pe) / (want - k)));
+            const uint64_t kind = check::next(seed) % 6;
+            uint64_t p0 = pe + (kind == 0 ? 0 : check::next(seed) % (1 + (pat.size() - pe) / (want - k)));
             if (p0 > pat.size()) break;
             uint64_t t0 = p0 < pat.size() ? from[p0] : r.textNumBytes;
             if (kind == 0 || t0 < te) t0 = te;               // adjacent on the text's side, or kept colinear
             if (kind == 1) p0 = pe;                          // a gap with an empty pattern side
             const uint64_t room = std::min(r.textNumBytes - t0, pat.size() - p0);
-            const uint64_t L = kind == 2 ? 0 : next(seed) % (std::min<uint64_t>(room, 24) + 1);
+            const uint64_t L = kind == 2 ? 0 : check::next(seed) % (std::min<uint64_t>(room, 24) + 1);
             ts.push_back(t0);
             ps.push_back(p0);
             len.push_back(L);
@@ -128,8 +89,8 @@ int main(int argc, char **argv)
         }
         num[i] = ts.size() - first[i];
         const uint64_t a = first[i], z = ts.size() - 1;
-        slice(left[i], r, 0, ts[a], 0, ps[a], true);
-        slice(right[i], r, ts[z] + len[z], r.textNumBytes - ts[z] - len[z], ps[z] + len[z], r.patternNumBytes - ps[z] - len[z], false);
+        check::slice(left[i], r, 0, ts[a], 0, ps[a], true);
+        check::slice(right[i], r, ts[z] + len[z], r.textNumBytes - ts[z] - len[z], ps[z] + len[z], r.patternNumBytes - ps[z] - len[z], false);
         for (uint64_t k = a; k < z; ++k)
         {
             const uint64_t t0 = ts[k] + len[k], p0 = ps[k] + len[k];
@@ -137,10 +98,19 @@ int main(int argc, char **argv)
         }
     }
     std::vector<SequenceAlignment::Request> gaps(pieces.size());  // a Request owns its letters: filled in place, never copied
-    for (size_t k = 0; k < pieces.size(); ++k) slice(gaps[k], reqs[pieces[k].request], pieces[k].tFrom, pieces[k].tLen, pieces[k].pFrom, pieces[k].pLen, false);
+    for (size_t k = 0; k < pieces.size(); ++k) check::slice(gaps[k], reqs[pieces[k].request], pieces[k].tFrom, pieces[k].tLen, pieces[k].pFrom, pieces[k].pLen, false);
+    const int xdrops[2] = {20, SA_NO_XDROP};
+    if (expectedOnly)
+    {
+        check::Digest sent;
+        sent.requests(reqs);
+        sent.numbers(num), sent.numbers(ts), sent.numbers(ps), sent.numbers(len);
+        sent.requests(left), sent.requests(right), sent.requests(gaps);
+        for (int xdrop : xdrops) sent.number(xdrop);
+        return check::printExpected("sa_chains_check", argc, argv, sent, nullptr);
+    }
     std::vector<SequenceAlignment::Response> respGaps(gaps.size());
     if (!gaps.empty() && SequenceAlignment::alignSequencesGPUAffine(gaps.data(), respGaps.data(), gaps.size(), device, gapOpen, gapExtend)) return 1;
-    const int xdrops[2] = {20, SA_NO_XDROP};
     for (int xdrop : xdrops)
     {
         std::vector<SequenceAlignment::Response> resp(count), respLeft(count), respRight(count);
@@ -158,61 +128,48 @@ int main(int argc, char **argv)
         {
             const SequenceAlignment::Response &g = resp[i], &l = respLeft[i], &r = respRight[i];
             const char gapLetter = reqs[i].alphabet[reqs[i].alphabetSize];
-            int want = l.score + r.score;
-            std::string wantText, wantPattern;
-            uint64_t leftText = 0, leftPattern = 0;
-            for (uint64_t x = l.numAlignmentBytes; x-- > 0;)
-            {
-                wantText += l.alignedTextBytes[x];
-                wantPattern += l.alignedPatternBytes[x];
-                leftText += l.alignedTextBytes[x] != gapLetter;
-                leftPattern += l.alignedPatternBytes[x] != gapLetter;
-            }
+            // the left extension backwards, then seeds and gaps in turn, then the right extension
+            check::Expected want;
+            uint64_t leftText, leftPattern;
+            check::countLetters(l, gapLetter, leftText, leftPattern);
+            check::appendStrings(want, l, true);
+            want.score = l.score + r.score;
             for (uint64_t k = first[i]; k < first[i] + num[i]; ++k)
             {
                 for (uint64_t q = 0; q < len[k]; ++q)
                 {
                     const int ct = reqs[i].textBytes[ts[k] + q], cp = reqs[i].patternBytes[ps[k] + q];
-                    want += blast[cp * 4 + ct];
-                    wantText += reqs[i].alphabet[ct];
-                    wantPattern += reqs[i].alphabet[cp];
+                    want.score += check::blast[cp * 4 + ct];
+                    want.text += reqs[i].alphabet[ct];
+                    want.pattern += reqs[i].alphabet[cp];
                 }
                 if (k + 1 == first[i] + num[i]) break;
                 const uint64_t t0 = ts[k] + len[k], p0 = ps[k] + len[k], gn = ts[k + 1] - t0, gm = ps[k + 1] - p0;
                 if (gn && gm)
                 {
                     const SequenceAlignment::Response &gr = respGaps[nextGap++];
-                    want += gr.score;
-                    wantText.append(gr.alignedTextBytes, gr.numAlignmentBytes);
-                    wantPattern.append(gr.alignedPatternBytes, gr.numAlignmentBytes);
+                    want.score += gr.score;
+                    check::appendStrings(want, gr, false);
                 }
                 else if (gn + gm)
                 {
-                    want -= gapOpen + ((int)(gn + gm) - 1) * gapExtend;
+                    want.score -= gapOpen + ((int)(gn + gm) - 1) * gapExtend;
                     for (uint64_t q = 0; q < gn + gm; ++q)
                     {
-                        wantText += gn ? reqs[i].alphabet[(int)reqs[i].textBytes[t0 + q]] : gapLetter;
-                        wantPattern += gm ? reqs[i].alphabet[(int)reqs[i].patternBytes[p0 + q]] : gapLetter;
+                        want.text += gn ? reqs[i].alphabet[(int)reqs[i].textBytes[t0 + q]] : gapLetter;
+                        want.pattern += gm ? reqs[i].alphabet[(int)reqs[i].patternBytes[p0 + q]] : gapLetter;
                     }
                 }
             }
-            wantText.append(r.alignedTextBytes, r.numAlignmentBytes);
-            wantPattern.append(r.alignedPatternBytes, r.numAlignmentBytes);
-            const char *field = nullptr;
-            if (scores[i] != g.score) field = "scoreSequencesGPUChains against alignSequencesGPUChains";
-            else if (g.score != want) field = "score against the pieces";
-            else if (g.startInAlignedText != ts[first[i]] - leftText || g.startInAlignedPattern != ps[first[i]] - leftPattern) field = "a start";
-            else if (g.numAlignmentBytes != wantText.size()) field = "numAlignmentBytes";
-            else if (std::memcmp(g.alignedTextBytes, wantText.data(), wantText.size()) != 0) field = "alignedTextBytes";
-            else if (std::memcmp(g.alignedPatternBytes, wantPattern.data(), wantPattern.size()) != 0) field = "alignedPatternBytes";
-            if (field)
-            {
-                std::cout << "request " << i << " (" << reqs[i].textNumBytes << "x" << reqs[i].patternNumBytes << ", " << num[i]
-                          << " seeds from " << ts[first[i]] << ":" << ps[first[i]] << ":" << len[first[i]] << ") at xdrop " << xdrop << ": " << field
-                          << " differs: chains score " << g.score << " (scorer " << scores[i] << ") length " << g.numAlignmentBytes
-                          << ", the pieces' score " << want << " length " << wantText.size() << "\n";
-                return 1;
-            }
+            check::appendStrings(want, r, false);
+            want.startText = ts[first[i]] - leftText;
+            want.startPattern = ps[first[i]] - leftPattern;
+            const auto scorers = {check::Scored{"scoreSequencesGPUChains against alignSequencesGPUChains", scores[i], g.score}};
+            if (const char *field = check::firstDifference(g, want, scorers))
+                return check::reportDifference(i, reqs[i], std::to_string(num[i]) + " seeds from " + std::to_string(ts[first[i]]) + ":" +
+                                                               std::to_string(ps[first[i]]) + ":" + std::to_string(len[first[i]]) + " at xdrop " +
+                                                               std::to_string(xdrop),
+                                               field, g, want, scorers);
         }
     }
     std::cout << "OK " << count << "\n";

@@ -7,27 +7,11 @@
 // score, the length and the two starts must be that function's.
 //   usage: sa_cigar_check <n> <count> [device]
 // Prints the first difference, or "OK <count>" as its last line; exit status 0 iff all equal.
-#include <algorithm>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <string>
-#include <vector>
-
-#include "SequenceAlignment.hpp"
-#include "sa_hip.h"
+// With --expected: the digest of the requests, seeds and chains (check_ref.h) and nothing of either library.
+#include "check_ref.h"
 
 namespace
 {
-const int blast[16] = {5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5};
-
-uint64_t next(uint64_t &s)
-{
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return s >> 33;
-}
-
 sa_align_spec plain(int gapOpen, int gapExtend)
 {
     sa_align_spec s;
@@ -45,6 +29,7 @@ sa_align_spec plain(int gapOpen, int gapExtend)
 
 int main(int argc, char **argv)
 {
+    const bool expectedOnly = check::takeExpected(argc, argv);
     if (argc < 3)
     {
         std::cout << "usage: sa_cigar_check <n> <count> [device]\n";
@@ -62,23 +47,17 @@ int main(int argc, char **argv)
     for (uint64_t i = 0; i < count; ++i)
     {
         SequenceAlignment::Request &r = reqs[i];
-        r.deviceType = SequenceAlignment::programArgs::GPU;
-        r.sequenceType = SequenceAlignment::programArgs::DNA;
-        r.alignmentType = SequenceAlignment::programArgs::GLOBAL;
-        r.alphabet = SequenceAlignment::DNA_ALPHABET;
-        r.alphabetSize = SequenceAlignment::NUM_DNA_CHARS;
-        r.gapPenalty = 5;  // ignored by every call here
-        std::memcpy(r.scoreMatrix, blast, sizeof(blast));
-        r.textNumBytes = 1 + next(seed) % maxLen;
+        check::scheme(r);
+        r.textNumBytes = 1 + check::next(seed) % maxLen;
         r.textBytes = new char[r.textNumBytes];
-        for (uint64_t x = 0; x < r.textNumBytes; ++x) r.textBytes[x] = (char)(next(seed) % 4);
+        for (uint64_t x = 0; x < r.textNumBytes; ++x) r.textBytes[x] = (char)(check::next(seed) % 4);
         std::vector<char> pat;
         for (uint64_t x = 0; x < r.textNumBytes; ++x)
         {
-            const uint64_t roll = next(seed) % 24;
+            const uint64_t roll = check::next(seed) % 24;
             if (roll == 0) continue;  // a deletion
-            pat.push_back(roll == 1 ? (char)(next(seed) % 4) : r.textBytes[x]);
-            if (roll == 2) pat.push_back((char)(next(seed) % 4));  // an insertion
+            pat.push_back(roll == 1 ? (char)(check::next(seed) % 4) : r.textBytes[x]);
+            if (roll == 2) pat.push_back((char)(check::next(seed) % 4));  // an insertion
         }
         if (pat.empty()) pat.push_back(0);
         r.patternNumBytes = pat.size();
@@ -86,8 +65,8 @@ int main(int argc, char **argv)
         std::memcpy(r.patternBytes, pat.data(), pat.size());
         // two seeds on the main diagonal, in the first and in the second half of the shorter side
         const uint64_t side = std::min<uint64_t>(r.textNumBytes, r.patternNumBytes), half = side / 2;
-        const uint64_t a = next(seed) % (half + 1), la = next(seed) % (half - a + 1);
-        const uint64_t b = half + next(seed) % (side - half + 1), lb = next(seed) % (side - b + 1);
+        const uint64_t a = check::next(seed) % (half + 1), la = check::next(seed) % (half - a + 1);
+        const uint64_t b = half + check::next(seed) % (side - half + 1), lb = check::next(seed) % (side - b + 1);
         seeds[i] = sa_seed{a, a, la};
         chain.push_back(sa_seed{a, a, la});
         chain.push_back(sa_seed{b, b, lb});
@@ -98,6 +77,15 @@ int main(int argc, char **argv)
     std::vector<uint64_t> sts(count), sps(count), slen(count);
     for (uint64_t i = 0; i < count; ++i) sts[i] = seeds[i].text_pos, sps[i] = seeds[i].pattern_pos, slen[i] = seeds[i].length;
 
+    if (expectedOnly)
+    {
+        check::Digest sent;
+        sent.requests(reqs);
+        sent.numbers(sts), sent.numbers(sps), sent.numbers(slen);
+        sent.numbers(num), sent.numbers(ts), sent.numbers(ps), sent.numbers(len), sent.numbers(chainOff);
+        sent.number(xdrop), sent.number(band);
+        return check::printExpected("sa_cigar_check", argc, argv, sent, nullptr);
+    }
     const char *names[6] = {"affine global", "affine local", "banded", "extend", "seeds", "chains"};
     for (int variant = 0; variant < 6; ++variant)
     {

@@ -13,38 +13,13 @@
 // The scorer's score must equal the aligner's and both starts of an extension must be 0.
 //   usage: sa_extend_band_check <n> <count> [device]
 // Prints the first difference, or "OK <count>" as its last line; exit status 0 iff all equal.
-#include <algorithm>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <vector>
-
-#include "SequenceAlignment.hpp"
-#include "sa_hip.h"
+// With --expected: the digest of the requests, seeds and widths (check_ref.h) and nothing of either library.
+#include "check_ref.h"
 
 namespace
 {
 using SequenceAlignment::Request;
 using SequenceAlignment::Response;
-
-uint64_t next(uint64_t &s)
-{
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return s >> 33;
-}
-
-void scheme(Request &r)
-{
-    static const int blast[16] = {5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5};
-    r.deviceType = SequenceAlignment::programArgs::GPU;
-    r.sequenceType = SequenceAlignment::programArgs::DNA;
-    r.alignmentType = SequenceAlignment::programArgs::GLOBAL;
-    r.alphabet = SequenceAlignment::DNA_ALPHABET;
-    r.alphabetSize = SequenceAlignment::NUM_DNA_CHARS;
-    r.gapPenalty = 5;  // ignored by the calls of this program
-    std::memcpy(r.scoreMatrix, blast, sizeof(blast));
-}
 
 bool sameStrings(const Response &a, const Response &b)
 {
@@ -62,6 +37,7 @@ int differs(uint64_t i, const char *what, int width, int xdrop)
 
 int main(int argc, char **argv)
 {
+    const bool expectedOnly = check::takeExpected(argc, argv);
     if (argc < 3)
     {
         std::cout << "usage: sa_extend_band_check <n> <count> [device]\n";
@@ -77,27 +53,31 @@ int main(int argc, char **argv)
     for (uint64_t i = 0; i < count; ++i)
     {
         Request &r = reqs[i];
-        scheme(r);
-        r.textNumBytes = 1 + next(seed) % maxLen;
-        r.patternNumBytes = 1 + next(seed) % maxLen;
-        r.textBytes = new char[r.textNumBytes];
-        r.patternBytes = new char[r.patternNumBytes];
-        for (uint64_t x = 0; x < r.textNumBytes; ++x) r.textBytes[x] = (char)(next(seed) % 4);
+        check::scheme(r);
+        r.textNumBytes = 1 + check::next(seed) % maxLen;
+        r.patternNumBytes = 1 + check::next(seed) % maxLen;
+        check::randomText(r, seed);
         // the pattern: the text with substitutions and a few letters left out up to letter `related`,
         // unrelated letters from there on
-        const uint64_t related = next(seed) % (r.patternNumBytes + 1);
-        uint64_t src = 0;
-        for (uint64_t x = 0; x < r.patternNumBytes; ++x, ++src)
-        {
-            if (next(seed) % 64 == 0) src += next(seed) % 4;
-            r.patternBytes[x] = x < related && src < r.textNumBytes && next(seed) % 8 ? r.textBytes[src] : (char)(next(seed) % 4);
-        }
-        seedT[i] = next(seed) % (r.textNumBytes + 1);
-        seedP[i] = next(seed) % (r.patternNumBytes + 1);
-        seedL[i] = next(seed) % (std::min(r.textNumBytes - seedT[i], r.patternNumBytes - seedP[i]) + 1);
+        const uint64_t related = check::next(seed) % (r.patternNumBytes + 1);
+        check::relatedPattern(r, seed, 0, related, true, 4);
+        seedT[i] = check::next(seed) % (r.textNumBytes + 1);
+        seedP[i] = check::next(seed) % (r.patternNumBytes + 1);
+        seedL[i] = check::next(seed) % (std::min(r.textNumBytes - seedT[i], r.patternNumBytes - seedP[i]) + 1);
     }
     const int xdrops[2] = {20, SA_NO_XDROP};
     const int widths[2] = {5, 64};
+    const int wide = (int)std::min<uint64_t>(maxLen, 1u << 30);  // W1: a width that admits every cell
+    if (expectedOnly)
+    {
+        check::Digest sent;
+        sent.requests(reqs);
+        sent.numbers(seedT), sent.numbers(seedP), sent.numbers(seedL);
+        for (int xdrop : xdrops) sent.number(xdrop);
+        for (int width : widths) sent.number(width);
+        sent.number(wide);
+        return check::printExpected("sa_extend_band_check", argc, argv, sent, nullptr);
+    }
     for (int xdrop : xdrops)
     {
         std::vector<int> full(count), narrower(count, 0);
@@ -116,23 +96,12 @@ int main(int argc, char **argv)
             std::vector<int> lo(count, -width), hi(count, width);
             for (uint64_t i = 0; i < count; ++i)
             {
-                const char gapLetter = reqs[i].alphabet[reqs[i].alphabetSize];
-                uint64_t endText = 0, endPattern = 0;
-                for (uint64_t x = 0; x < resp[i].numAlignmentBytes; ++x)
-                {
-                    endText += resp[i].alignedTextBytes[x] != gapLetter;
-                    endPattern += resp[i].alignedPatternBytes[x] != gapLetter;
-                }
+                uint64_t endText, endPattern;
+                check::countLetters(resp[i], reqs[i].alphabet[reqs[i].alphabetSize], endText, endPattern);
                 if (endText > reqs[i].textNumBytes || endPattern > reqs[i].patternNumBytes) return differs(i, "the letters of the strings", width, xdrop);
                 const int64_t off = (int64_t)endText - (int64_t)endPattern;
                 if (off < -width || off > width) return differs(i, "the end cell's diagonal (out of band)", width, xdrop);
-                scheme(pre[i]);
-                pre[i].textNumBytes = endText;
-                pre[i].patternNumBytes = endPattern;
-                pre[i].textBytes = new char[std::max<uint64_t>(endText, 1)];
-                pre[i].patternBytes = new char[std::max<uint64_t>(endPattern, 1)];
-                std::memcpy(pre[i].textBytes, reqs[i].textBytes, endText);
-                std::memcpy(pre[i].patternBytes, reqs[i].patternBytes, endPattern);
+                check::slice(pre[i], reqs[i], 0, endText, 0, endPattern, false);
             }
             if (SequenceAlignment::alignSequencesGPUBandAt(pre.data(), respPrefix.data(), count, device, gapOpen, gapExtend, 0, lo.data(), hi.data()))
                 return 1;
@@ -148,8 +117,7 @@ int main(int argc, char **argv)
                 narrower[i] = g.score;
             }
         }
-        // W1: a width that admits every cell
-        const int wide = (int)std::min<uint64_t>(maxLen, 1u << 30);
+        // W1
         std::vector<Response> a(count), b(count), c(count), d(count);
         std::vector<int> s1(count), s2(count), s3(count);
         if (SequenceAlignment::scoreSequencesGPUExtendBand(reqs.data(), count, device, gapOpen, gapExtend, xdrop, wide, s1.data())) return 1;

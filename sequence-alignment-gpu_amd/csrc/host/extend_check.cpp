@@ -8,39 +8,12 @@
 // be 0, and the score without a drop must be no smaller than the score at X-drop 20.
 //   usage: sa_extend_check <n> <count> [device]
 // Prints the first difference, or "OK <count>" as its last line; exit status 0 iff all equal.
-#include <algorithm>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <iostream>
-#include <vector>
-
-#include "SequenceAlignment.hpp"
-#include "sa_hip.h"
-
-namespace
-{
-uint64_t next(uint64_t &s)
-{
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return s >> 33;
-}
-
-void scheme(SequenceAlignment::Request &r)
-{
-    static const int blast[16] = {5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5, -4, -4, -4, -4, 5};
-    r.deviceType = SequenceAlignment::programArgs::GPU;
-    r.sequenceType = SequenceAlignment::programArgs::DNA;
-    r.alignmentType = SequenceAlignment::programArgs::GLOBAL;
-    r.alphabet = SequenceAlignment::DNA_ALPHABET;
-    r.alphabetSize = SequenceAlignment::NUM_DNA_CHARS;
-    r.gapPenalty = 5;  // ignored by the affine and the extend calls
-    std::memcpy(r.scoreMatrix, blast, sizeof(blast));
-}
-}  // namespace
+// With --expected: the digest of the requests (check_ref.h) and nothing of either library.
+#include "check_ref.h"
 
 int main(int argc, char **argv)
 {
+    const bool expectedOnly = check::takeExpected(argc, argv);
     if (argc < 3)
     {
         std::cout << "usage: sa_extend_check <n> <count> [device]\n";
@@ -50,29 +23,29 @@ int main(int argc, char **argv)
     const uint64_t count = std::strtoull(argv[2], nullptr, 10);
     const int device = argc > 3 ? std::atoi(argv[3]) : 0;
     const int gapOpen = 11, gapExtend = 2;
+    const int xdrops[2] = {20, SA_NO_XDROP};
     std::vector<SequenceAlignment::Request> reqs(count);
     uint64_t seed = 97531;
     for (uint64_t i = 0; i < count; ++i)
     {
         SequenceAlignment::Request &r = reqs[i];
-        scheme(r);
-        r.textNumBytes = 1 + next(seed) % maxLen;
-        r.patternNumBytes = 1 + next(seed) % maxLen;
-        r.textBytes = new char[r.textNumBytes];
-        r.patternBytes = new char[r.patternNumBytes];
-        for (uint64_t x = 0; x < r.textNumBytes; ++x) r.textBytes[x] = (char)(next(seed) % 4);
+        check::scheme(r);
+        r.textNumBytes = 1 + check::next(seed) % maxLen;
+        r.patternNumBytes = 1 + check::next(seed) % maxLen;
+        check::randomText(r, seed);
         // the pattern: the text with substitutions and a few letters left out up to letter `related`,
         // unrelated letters from there on
-        const uint64_t related = next(seed) % (r.patternNumBytes + 1);
-        uint64_t src = 0;
-        for (uint64_t x = 0; x < r.patternNumBytes; ++x, ++src)
-        {
-            if (next(seed) % 64 == 0) src += next(seed) % 4;
-            r.patternBytes[x] = x < related && src < r.textNumBytes && next(seed) % 8 ? r.textBytes[src] : (char)(next(seed) % 4);
-        }
+        const uint64_t related = check::next(seed) % (r.patternNumBytes + 1);
+        check::relatedPattern(r, seed, 0, related, true, 4);
+    }
+    if (expectedOnly)
+    {
+        check::Digest sent;
+        sent.requests(reqs);
+        for (int xdrop : xdrops) sent.number(xdrop);
+        return check::printExpected("sa_extend_check", argc, argv, sent, nullptr);
     }
     std::vector<int> previous(count, 0);
-    const int xdrops[2] = {20, SA_NO_XDROP};
     for (int xdrop : xdrops)
     {
         std::vector<SequenceAlignment::Response> resp(count), respPrefix(count);
@@ -83,47 +56,30 @@ int main(int argc, char **argv)
         std::vector<SequenceAlignment::Request> pre(count);
         for (uint64_t i = 0; i < count; ++i)
         {
-            const char gapLetter = reqs[i].alphabet[reqs[i].alphabetSize];
-            uint64_t endText = 0, endPattern = 0;
-            for (uint64_t x = 0; x < resp[i].numAlignmentBytes; ++x)
-            {
-                endText += resp[i].alignedTextBytes[x] != gapLetter;
-                endPattern += resp[i].alignedPatternBytes[x] != gapLetter;
-            }
+            uint64_t endText, endPattern;
+            check::countLetters(resp[i], reqs[i].alphabet[reqs[i].alphabetSize], endText, endPattern);
             if (endText > reqs[i].textNumBytes || endPattern > reqs[i].patternNumBytes)
             {
                 std::cout << "request " << i << " at xdrop " << xdrop << ": the strings hold more letters than the sequences\n";
                 return 1;
             }
-            scheme(pre[i]);
-            pre[i].textNumBytes = endText;
-            pre[i].patternNumBytes = endPattern;
-            pre[i].textBytes = new char[std::max<uint64_t>(endText, 1)];
-            pre[i].patternBytes = new char[std::max<uint64_t>(endPattern, 1)];
-            std::memcpy(pre[i].textBytes, reqs[i].textBytes, endText);
-            std::memcpy(pre[i].patternBytes, reqs[i].patternBytes, endPattern);
+            check::slice(pre[i], reqs[i], 0, endText, 0, endPattern, false);
         }
         if (SequenceAlignment::alignSequencesGPUAffine(pre.data(), respPrefix.data(), count, device, gapOpen, gapExtend)) return 1;
         for (uint64_t i = 0; i < count; ++i)
         {
-            const SequenceAlignment::Response &g = resp[i], &a = respPrefix[i];
-            const char *field = nullptr;
-            if (scores[i] != g.score) field = "scoreSequencesGPUExtend against alignSequencesGPUExtend";
-            else if (g.score < 0) field = "a negative score";
-            else if (g.startInAlignedText != 0 || g.startInAlignedPattern != 0) field = "a start";
-            else if (g.score != a.score) field = "score against the global alignment of the prefixes";
-            else if (g.numAlignmentBytes != a.numAlignmentBytes) field = "numAlignmentBytes";
-            else if (std::memcmp(g.alignedTextBytes, a.alignedTextBytes, g.numAlignmentBytes) != 0) field = "alignedTextBytes";
-            else if (std::memcmp(g.alignedPatternBytes, a.alignedPatternBytes, g.numAlignmentBytes) != 0) field = "alignedPatternBytes";
-            else if (xdrop == SA_NO_XDROP && g.score < previous[i]) field = "the score without a drop against the score at xdrop 20";
+            const SequenceAlignment::Response &g = resp[i];
+            // the global alignment of the prefixes, and both starts 0
+            check::Expected want = check::expectedOf(respPrefix[i]);
+            want.startText = want.startPattern = 0;
+            const auto scorers = {check::Scored{"scoreSequencesGPUExtend against alignSequencesGPUExtend", scores[i], g.score}};
+            const char *field = check::firstDifference(g, want, scorers);
+            if (!field && g.score < 0) field = "a negative score";
+            if (!field && xdrop == SA_NO_XDROP && g.score < previous[i]) field = "the score without a drop against the score at xdrop 20";
             if (field)
-            {
-                std::cout << "request " << i << " (" << reqs[i].textNumBytes << "x" << reqs[i].patternNumBytes << ") at xdrop " << xdrop
-                          << ": " << field << " differs: extend score " << g.score << " (scorer " << scores[i] << ") length "
-                          << g.numAlignmentBytes << ", prefixes " << pre[i].textNumBytes << "x" << pre[i].patternNumBytes << " score "
-                          << a.score << " length " << a.numAlignmentBytes << "\n";
-                return 1;
-            }
+                return check::reportDifference(i, reqs[i], "xdrop " + std::to_string(xdrop) + ", prefixes " + std::to_string(pre[i].textNumBytes) + "x" +
+                                                               std::to_string(pre[i].patternNumBytes),
+                                               field, g, want, scorers);
             previous[i] = g.score;
         }
     }
