@@ -22,7 +22,8 @@
 #include <utility>
 #include <vector>
 
-struct sa_align_spec;  // sa_hip.h: what alignSequencesGPUCigar takes
+struct sa_align_spec;    // sa_hip.h: what alignSequencesGPUCigar takes
+struct sa_chain_params;  // sa_hip.h: what chainAnchorsGPU takes
 
 namespace SequenceAlignment
 {
@@ -280,6 +281,24 @@ struct CigarResponse
 };
 uint64_t alignSequencesGPUCigar(const Request *requests, CigarResponse *responses, uint64_t numRequests, int device,
                                 const ::sa_align_spec &spec, bool eqx = true, int freeEnds = -1);
+
+/// Extension: chaining (sa_chain_anchors; sa_hip.h has the definition). Pair k carries anchorCount[k] >= 0 anchors, a
+/// seeder's unfiltered exact matches {anchorTextPos, anchorPatternPos, anchorLength}, length >= 1, in canonical order
+/// (non-decreasing text end, pattern end, length); the anchors of all pairs lie one pair after another in the three
+/// arrays, as the ...Chains functions carry their seeds. No sequences are taken: the letters are not looked at. Each
+/// pair gets the best colinear chain without overlaps under `params` (sa_hip.h sa_chain_params): its score, the index
+/// of the anchor it ends in, and its seeds in forward order, which are what the ...Chains functions take as the seeds
+/// of a request (a pair without anchors has no seeds; leave it out of such a call). A pair out of order fails the
+/// whole call. Returns 0, or 1 with the message on stdout.
+struct ChainResponse
+{
+    int score = 0;
+    uint32_t lastAnchor = 0;
+    std::vector<uint64_t> seedTextPos, seedPatternPos, seedLength;
+};
+uint64_t chainAnchorsGPU(ChainResponse *responses, uint64_t numPairs, int device, const ::sa_chain_params &params,
+                         const uint64_t *anchorCount, const uint64_t *anchorTextPos, const uint64_t *anchorPatternPos,
+                         const uint64_t *anchorLength);
 
 /// Host tracebacks over a full (m+1)x(n+1) byte DIRECTION matrix (used by the CPU device).
 void traceBackNW(const char *, const uint64_t, const uint64_t, const Request &, Response *);

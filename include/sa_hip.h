@@ -627,6 +627,79 @@ int sa_align_pairs_chains(const sa_params *params, int32_t gap_open, int32_t gap
                           const uint64_t *chain_off, const sa_host_pair *pairs, int64_t num_pairs, int device, sa_result *results,
                           char *const *aligned_text, char *const *aligned_pattern);
 
+/* ---- chaining: one colinear chain per pair from a seeder's unfiltered anchors ------------------- */
+
+/* Pair k owns the anchors anchors[anchor_off[k] .. anchor_off[k + 1]) of one flat sa_seed array; anchor_off has
+ * num_pairs + 1 entries, anchor_off[0] == 0, and is non-decreasing. A pair may have no anchors. An anchor
+ * {x, y, L} is {text_pos, pattern_pos, length} with L >= 1; its ends are ex = x + L and ey = y + L. Its letters
+ * are not looked at: the functions take no sequences, so repeats, overlaps and off-diagonal hits are welcome.
+ *   order:      a pair's anchors come in canonical order, non-decreasing (ex, ey, L) lexicographically; equal
+ *               keys are identical anchors and are allowed. The order is checked in one pass and a call out of
+ *               order is refused: nothing here sorts
+ *   transition: for j < i within one pair, o = max(0, ex_j - x_i, ey_j - y_i) letters are cut from the front
+ *               of i; dx = x_i + o - ex_j, dy = y_i + o - ey_j, dd = |dx - dy|. j -> i is admissible iff
+ *               o < L_i, dx <= max_gap, dy <= max_gap, dd <= max_diag and i - j <= lookback, and then
+ *               value(j -> i) = match (L_i - o) - (dd ? gap_open + (dd - 1) gap_extend : 0) - skip min(dx, dy)
+ *   recurrence: f(i) = max(match L_i, max over admissible j of f(j) + value(j -> i)); pred(i) is the j that
+ *               attains it. A predecessor is taken only when it is strictly better than starting anew at i,
+ *               and among equal predecessors the largest j wins
+ *   result:     the chain ends at the anchor with the largest f, ties to the lowest index (last_anchor), and is
+ *               followed back through pred. Its seeds in forward order are {x_i + o_i, y_i + o_i, L_i - o_i},
+ *               the first with o = 0; score = f(end). A pair without anchors has score 0, no seeds and
+ *               last_anchor 0. status is SA_OK
+ * All arithmetic is that of exact integers. f < 2^30 is enforced below, so a cost that reaches 2^30 can never be
+ * chosen, and an implementation may saturate there (the device kernel does, the host function does not).
+ * Identities: (K1) the output of every pair with anchors is a chain as sa_score_batch_chains defines one:
+ * colinear, no overlap, every L >= 1; each seed is the tail of one input anchor on that anchor's diagonal and
+ * shares its end. (K2) sa_chain_anchors equals sa_chain_anchors_host in every field and every seed. (K3) With
+ * lookback >= the pair's anchor count the score is the maximum over all index-increasing subsequences with
+ * admissible consecutive transitions. (K4) Anchors that already form a valid chain come back unchanged, with
+ * score match sum(L), under gap_open = gap_extend = skip = 0, no limits and lookback >= 1. (K5) A pair's result
+ * does not depend on the other pairs of the call (seeds_off apart), and adding (cx, cy) to every anchor of a
+ * pair adds the same constant to its seeds and changes nothing else.
+ * sa_chain_anchors runs chain_dp_kernel (one wave per pair, drawn from a counter, most anchors first; the last
+ * `lookback` anchors in an LDS ring; 64 predecessors per round) and, once the host has turned the chain lengths
+ * into offsets, chain_walk_kernel, which writes every pair's seeds into an array of exactly the counted size
+ * that one copy brings back. sa_chain_anchors_host is the definition on the host and makes no device call.
+ * *out owns the seeds and their offsets until sa_chain_set_destroy; on failure it stays NULL.
+ * sa_chain_set_seeds and sa_chain_set_off are exactly the `seeds` and `chain_off` arguments of
+ * sa_score_batch_chains, sa_scorer_create_chains and sa_align_pairs_chains and of sa_align_spec. Those functions
+ * refuse a pair without a seed, so a caller first drops the pairs whose num_seeds == 0 (and their entries of
+ * chain_off); they also want every seed inside its pair's sequences, which a seeder's anchors are.
+ * Refusals, all before any device call, sa_last_error() naming the pair and the anchor (its index within the
+ * pair) where one is at fault. SA_ERR_INVALID: params, results or out NULL; a parameter outside the ranges
+ * below; num_pairs < 0; anchors or anchor_off NULL with num_pairs > 0; anchor_off[0] != 0 or anchor_off
+ * decreasing; L == 0; a pair out of canonical order. SA_ERR_UNSUPPORTED: x + L or y + L at or above 2^31 - 1;
+ * a pair with match sum(L) >= 2^30; num_pairs >= 2^31.
+ * Not built: finding the anchors on the device, sorting them, secondary chains, and a handle that keeps the
+ * anchors on the device between calls. */
+#define SA_CHAIN_NO_LIMIT INT32_MAX
+typedef struct sa_chain_params {
+    int32_t match;                  /* 1 .. 1024 */
+    int32_t gap_open, gap_extend;   /* 0 .. 2^20: a diagonal change of dd costs gap_open + (dd - 1) gap_extend */
+    int32_t skip;                   /* 0 .. 2^20, per letter of min(dx, dy) */
+    int32_t max_gap, max_diag;      /* >= 0, or SA_CHAIN_NO_LIMIT */
+    int32_t lookback;               /* 1 .. 1024 */
+} sa_chain_params;
+typedef struct sa_chain_result {
+    int32_t score, status;
+    uint64_t seeds_off;             /* first seed of this pair's chain = chain_off[k] */
+    uint32_t num_seeds;
+    uint32_t last_anchor;           /* index, within the pair, of the anchor the chain ends in; 0 without anchors */
+} sa_chain_result;
+typedef struct sa_chain_set sa_chain_set;   /* owns the call's host seed array and its chain_off */
+
+int sa_chain_anchors(const sa_chain_params *params, const sa_seed *anchors, const uint64_t *anchor_off,
+                     int64_t num_pairs, int device, sa_chain_result *results, sa_chain_set **out);
+int sa_chain_anchors_host(const sa_chain_params *params, const sa_seed *anchors, const uint64_t *anchor_off,
+                          int64_t num_pairs, sa_chain_result *results, sa_chain_set **out);   /* no device call */
+const sa_seed *sa_chain_set_seeds(const sa_chain_set *set);     /* NULL when there are none */
+const uint64_t *sa_chain_set_off(const sa_chain_set *set);      /* num_pairs + 1 entries */
+int sa_chain_set_destroy(sa_chain_set *set);
+/* For benches and tests only: the calling thread's last sa_chain_anchors. Device time of chain_dp_kernel and of
+ * chain_walk_kernel in milliseconds and the bytes of device memory the call held. Each pointer may be NULL. */
+int sa_chain_last_stats(double *dp_ms, double *walk_ms, uint64_t *device_bytes);
+
 /* ---- CIGAR output: run-length alignments from every sa_align_pairs_* variant -------------------- */
 
 /* Take a pair's aligned strings at and ap exactly as the sa_align_pairs_* function of the same variant returns

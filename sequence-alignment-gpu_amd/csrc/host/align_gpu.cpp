@@ -481,6 +481,47 @@ uint64_t SequenceAlignment::alignSequencesGPUCigar(const Request *requests, Ciga
     return 0;
 }
 
+uint64_t SequenceAlignment::chainAnchorsGPU(ChainResponse *responses, uint64_t numPairs, int device, const sa_chain_params &params,
+                                            const uint64_t *anchorCount, const uint64_t *anchorTextPos, const uint64_t *anchorPatternPos,
+                                            const uint64_t *anchorLength)
+{
+    if (numPairs == 0) return 0;
+    if (!responses || !anchorCount)
+    {
+        std::cout << "error: chainAnchorsGPU: null argument\n";
+        return 1;
+    }
+    std::vector<uint64_t> off(numPairs + 1, 0);
+    for (uint64_t k = 0; k < numPairs; ++k) off[k + 1] = off[k] + anchorCount[k];
+    if (off[numPairs] > 0 && (!anchorTextPos || !anchorPatternPos || !anchorLength))
+    {
+        std::cout << "error: chainAnchorsGPU: null anchor array\n";
+        return 1;
+    }
+    std::vector<sa_seed> anchors(off[numPairs] + 1);  // one more: a call without any anchor still passes an address
+    for (uint64_t a = 0; a < off[numPairs]; ++a) anchors[a] = sa_seed{anchorTextPos[a], anchorPatternPos[a], anchorLength[a]};
+    std::vector<sa_chain_result> res(numPairs);
+    sa_chain_set *set = nullptr;
+    const int rc = sa_chain_anchors(&params, anchors.data(), off.data(), (int64_t)numPairs, device, res.data(), &set);
+    if (rc != SA_OK) return reportFailure(rc);
+    const sa_seed *seeds = sa_chain_set_seeds(set);
+    for (uint64_t k = 0; k < numPairs; ++k)
+    {
+        ChainResponse &rs = responses[k];
+        rs.score = res[k].score;
+        rs.lastAnchor = res[k].last_anchor;
+        rs.seedTextPos.clear(), rs.seedPatternPos.clear(), rs.seedLength.clear();
+        for (uint64_t s = res[k].seeds_off; s < res[k].seeds_off + res[k].num_seeds; ++s)
+        {
+            rs.seedTextPos.push_back(seeds[s].text_pos);
+            rs.seedPatternPos.push_back(seeds[s].pattern_pos);
+            rs.seedLength.push_back(seeds[s].length);
+        }
+    }
+    sa_chain_set_destroy(set);
+    return 0;
+}
+
 uint64_t SequenceAlignment::scoreSequencesGPUSeeds(const Request *requests, uint64_t numRequests, int device, int gapOpen, int gapExtend,
                                                    int xdrop, const uint64_t *seedTextPos, const uint64_t *seedPatternPos,
                                                    const uint64_t *seedLength, int *scores)

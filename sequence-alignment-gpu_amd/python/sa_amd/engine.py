@@ -48,7 +48,9 @@ EXPORTS = ("sa_align_pair", "sa_plan_create", "sa_plan_destroy", "sa_plan_fill",
            "sa_score_batch_seeds_band", "sa_scorer_create_seeds_band", "sa_align_pairs_seeds_band",
            "sa_score_batch_chains", "sa_scorer_create_chains", "sa_align_pairs_chains",
            "sa_align_pairs_cigar", "sa_cigars_ops", "sa_cigars_num_ops", "sa_cigars_destroy", "sa_cigar_from_strings",
-           "sa_cigar_format", "sa_cigar_last_stats")
+           "sa_cigar_format", "sa_cigar_last_stats",
+           "sa_chain_anchors", "sa_chain_anchors_host", "sa_chain_set_seeds", "sa_chain_set_off", "sa_chain_set_destroy",
+           "sa_chain_last_stats")
 # flags of align_pairs_cigar and cigar_from_strings (sa_hip.h sa_cigar_flags) and the BAM op codes
 CIGAR_M, CIGAR_EQX = 0, 1
 CIGAR_OPS = {0: "M", 1: "I", 2: "D", 7: "=", 8: "X"}
@@ -90,6 +92,20 @@ class SaCigarResult(ctypes.Structure):
                 ("num_ops", ctypes.c_uint32), ("matches", ctypes.c_uint32), ("mismatches", ctypes.c_uint32),
                 ("text_gap_letters", ctypes.c_uint32), ("pattern_gap_letters", ctypes.c_uint32),
                 ("gap_opens", ctypes.c_uint32)]
+
+
+# max_gap= and max_diag= of chain_anchors (sa_hip.h SA_CHAIN_NO_LIMIT)
+NO_LIMIT = 2 ** 31 - 1
+
+
+class SaChainParams(ctypes.Structure):
+    _fields_ = [("match", ctypes.c_int32), ("gap_open", ctypes.c_int32), ("gap_extend", ctypes.c_int32), ("skip", ctypes.c_int32),
+                ("max_gap", ctypes.c_int32), ("max_diag", ctypes.c_int32), ("lookback", ctypes.c_int32)]
+
+
+class SaChainResult(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("seeds_off", ctypes.c_uint64),
+                ("num_seeds", ctypes.c_uint32), ("last_anchor", ctypes.c_uint32)]
 
 
 class SaError(RuntimeError):
@@ -204,6 +220,14 @@ def _load():
                                         ctypes.POINTER(SaCigarResult)]
     L.sa_cigar_format.argtypes = [P, U64, P, U64]
     L.sa_cigar_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+    L.sa_chain_anchors.argtypes = [ctypes.POINTER(SaChainParams), P, P, ctypes.c_int64, I, P, ctypes.POINTER(P)]
+    L.sa_chain_anchors_host.argtypes = [ctypes.POINTER(SaChainParams), P, P, ctypes.c_int64, P, ctypes.POINTER(P)]
+    L.sa_chain_set_seeds.argtypes = [P]
+    L.sa_chain_set_seeds.restype = P
+    L.sa_chain_set_off.argtypes = [P]
+    L.sa_chain_set_off.restype = P
+    L.sa_chain_set_destroy.argtypes = [P]
+    L.sa_chain_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64)]
     L.sa_band_reachable.argtypes = [I32, U64, U64, SaBand]
     L.sa_band_reachable.restype = I
     L.sa_affine_last_stats.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -565,6 +589,69 @@ def cigar_last_stats() -> dict:
     e, o, s = ctypes.c_double(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
     _check(lib.sa_cigar_last_stats(ctypes.byref(e), ctypes.byref(o), ctypes.byref(s)))
     return {"encode_ms": e.value, "ops_bytes": o.value, "string_bytes_not_copied": s.value}
+
+
+# numpy view of sa_chain_result (include/sa_hip.h)
+CHAIN_DTYPE = np.dtype([("score", "<i4"), ("status", "<i4"), ("seeds_off", "<u8"), ("num_seeds", "<u4"), ("last_anchor", "<u4")])
+assert CHAIN_DTYPE.itemsize == ctypes.sizeof(SaChainResult)
+
+
+def canonical_order(anchors) -> np.ndarray:
+    """One pair's anchors, an (A, 3) array of (text_pos, pattern_pos, length), in the canonical order the chaining
+    functions want: non-decreasing (text end, pattern end, length)."""
+    a = np.asarray(anchors, dtype=np.int64).reshape(-1, 3)
+    return a[np.lexsort((a[:, 2], a[:, 1] + a[:, 2], a[:, 0] + a[:, 2]))]
+
+
+def chain_anchors(anchors, match: int, gap_open: int, gap_extend: int, skip: int = 0, max_gap: int = NO_LIMIT,
+                  max_diag: int = NO_LIMIT, lookback: int = 64, device: int = 0, host: bool = False, sort: bool = True):
+    """sa_chain_anchors: one colinear, overlap-free chain per pair out of a seeder's unfiltered anchors (the
+    definition is in sa_hip.h). `anchors` holds one (A_k, 3) array or list of (text_pos, pattern_pos, length)
+    triples per pair; a pair may have none. Returns (results, chains): results[k] is a dict of score, seeds_off,
+    num_seeds and last_anchor (an index into the pair's anchors in canonical order), chains[k] the pair's chain as
+    an (num_seeds, 3) int64 array, the form chains= of score_batch, Scorer, align_pairs_affine and
+    align_pairs_cigar accepts. Those refuse a pair without a seed: drop the pairs whose num_seeds is 0 first.
+    sort=True puts each pair's anchors in canonical order first (np.lexsort, on the host); with sort=False a pair
+    out of order is refused. host=True calls sa_chain_anchors_host, the same definition without a device."""
+    per = [np.asarray(a, dtype=np.int64).reshape(-1, 3) for a in anchors]
+    if any((a < 0).any() for a in per):
+        raise ValueError("anchors holds a negative value")
+    if sort:
+        per = [canonical_order(a) for a in per]
+    n = len(per)
+    flat = np.concatenate(per + [np.zeros((1, 3), np.int64)]).astype(np.uint64)  # one triple more: never a null address
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(a) for a in per], dtype=np.uint64)
+    cp = SaChainParams(match, gap_open, gap_extend, skip, max_gap, max_diag, lookback)
+    res = (SaChainResult * max(1, n))()
+    handle = ctypes.c_void_p()
+    if host:
+        _check(lib.sa_chain_anchors_host(ctypes.byref(cp), flat.ctypes.data, off.ctypes.data, n, res, ctypes.byref(handle)))
+    else:
+        _check(lib.sa_chain_anchors(ctypes.byref(cp), flat.ctypes.data, off.ctypes.data, n, device, res, ctypes.byref(handle)))
+    try:
+        rows = np.frombuffer(res, dtype=CHAIN_DTYPE, count=n)
+        coff = np.ctypeslib.as_array(ctypes.cast(lib.sa_chain_set_off(handle), ctypes.POINTER(ctypes.c_uint64)), (n + 1,)).copy()
+        addr = lib.sa_chain_set_seeds(handle)
+        total = int(coff[n])
+        seeds = (np.ctypeslib.as_array(ctypes.cast(addr, ctypes.POINTER(ctypes.c_uint64)), (total, 3)).astype(np.int64) if addr
+                 else np.zeros((0, 3), np.int64))
+    finally:
+        lib.sa_chain_set_destroy(handle)
+    if len(seeds) != total or (n and not (coff[:-1] == rows["seeds_off"]).all()):
+        raise SaError(1, "sa_chain_anchors: the seed offsets do not add up")
+    keys = ("score", "seeds_off", "num_seeds", "last_anchor")
+    results = [dict(zip(keys, (r[0], r[2], r[3], r[4]))) for r in rows.tolist()]
+    chains = [seeds[int(coff[k]): int(coff[k + 1])] for k in range(n)]
+    return results, chains
+
+
+def chain_last_stats() -> dict:
+    """sa_chain_last_stats: the calling thread's last chain_anchors on a device (device ms of the recurrence and of
+    the walk, bytes of device memory held)."""
+    d, w, b = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
+    _check(lib.sa_chain_last_stats(ctypes.byref(d), ctypes.byref(w), ctypes.byref(b)))
+    return {"dp_ms": d.value, "walk_ms": w.value, "device_bytes": b.value}
 
 
 def affine_last_stats() -> dict:

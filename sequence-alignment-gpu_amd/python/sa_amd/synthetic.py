@@ -65,3 +65,38 @@ def blast_matrix() -> np.ndarray:
     S = np.full((4, 4), -4, dtype=np.int32)
     np.fill_diagonal(S, 5)
     return S
+
+
+def kmer_anchors(text: np.ndarray, pattern: np.ndarray, k: int) -> np.ndarray:
+    """The maximal exact-match diagonal runs of length >= k between `text` and `pattern`, every diagonal and every
+    repeat, as an (A, 3) int64 array of (text_pos, pattern_pos, length) in the canonical order
+    engine.chain_anchors wants: non-decreasing (text end, pattern end, length). A helper for the tests and the
+    chaining bench, in numpy on the host (memory grows with the number of k-mer hits): it stands in for a seeder
+    and is not one for users."""
+    t, p = np.asarray(text, dtype=np.int64), np.asarray(pattern, dtype=np.int64)
+    none = np.zeros((0, 3), np.int64)
+    if k < 1 or len(t) < k or len(p) < k:
+        return none
+    win = np.lib.stride_tricks.sliding_window_view
+    words = np.concatenate([win(t, k), win(p, k)])
+    base = int(max(t.max(), p.max())) + 1
+    if min(t.min(), p.min()) >= 0 and base ** k < 2 ** 62:
+        ident = words @ (base ** np.arange(k - 1, -1, -1, dtype=np.int64))  # the k-mer as a number in that base: exact
+    else:
+        ident = np.unique(words, axis=0, return_inverse=True)[1].ravel()    # equal k-mers, equal numbers
+    ti, pi = ident[: len(t) - k + 1], ident[len(t) - k + 1:]
+    by = np.argsort(ti, kind="stable")
+    lo, hi = np.searchsorted(ti[by], pi, "left"), np.searchsorted(ti[by], pi, "right")
+    hits = hi - lo
+    if hits.sum() == 0:
+        return none
+    i = np.repeat(np.arange(len(pi)), hits)                                   # pattern position of every k-mer hit
+    j = by[np.repeat(lo, hits) + np.arange(hits.sum()) - np.repeat(np.cumsum(hits) - hits, hits)]  # its text position
+    o = np.lexsort((j, j - i))                                                # along each diagonal
+    i, j = i[o], j[o]
+    start = np.ones(len(i), bool)
+    start[1:] = (np.diff(j - i) != 0) | (np.diff(j) != 1)
+    first = np.flatnonzero(start)
+    length = np.diff(np.append(first, len(i))) + k - 1
+    a = np.stack([j[first], i[first], length], axis=1).astype(np.int64)
+    return a[np.lexsort((a[:, 2], a[:, 1] + a[:, 2], a[:, 0] + a[:, 2]))]

@@ -88,6 +88,12 @@ chains (all 2048, and the first 64) and on the first 4000 reads of --mode mapped
 end, the device times of the fill, the walks and the encoder, and the bytes each call copies to the host.
     python3 tools/score_bench.py --mode cigar [--small] --out profiles/r23/score_cigar_bench.json
 
+With --mode chaining the chaining (sa_hip.h: sa_chain_anchors) on the long reads of --mode chain, their anchors the
+maximal exact matches of at least k = 11 and k = 15 letters (synthetic.kmer_anchors), under 5 / gap-open / gap-extend,
+max_diag 500 and lookback 64: (a) the C call end to end, with the device time of its two kernels, against
+sa_chain_anchors_host on the same anchors, alternated round by round, on all reads and on the first 64; (b) the chains
+scorer on these chains and on the alignment-derived ones of --mode chain, pair by pair.
+    python3 tools/score_bench.py --mode chaining [--small] [--out profiles/r24/score_chaining_bench.json]
 With --mode extend --width W.. the banded extension (sa_hip.h: sa_scorer_create_extend_band,
 sa_align_pairs_extend_band) on the chimeric pairs under --exit-gap, without a drop and at --xdrop: per X, the
 unbanded extension scorer and, per width, the banded extension scorer and the band-at global scorer on {-w, w},
@@ -126,6 +132,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 
@@ -907,6 +914,83 @@ def chain_aligned_row(args, engine, w, chains, go: int, ge: int, xdrop) -> dict:
             "chains_over_band_at_arena": round(a["arena_bytes"] / max(b["arena_bytes"], 1), 4)}
 
 
+def chaining_call(engine, anchors, cp: dict):
+    """The raw C calls of --mode chaining on anchors packed once: (device, host), each returning (results, flat
+    seeds, offsets) of one call, the chain set destroyed."""
+    import ctypes
+    n = len(anchors)
+    flat = np.ascontiguousarray(np.concatenate(list(anchors) + [np.zeros((1, 3), np.int64)]).astype(np.uint64))
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(a) for a in anchors], dtype=np.uint64)
+    params = engine.SaChainParams(cp["match"], cp["gap_open"], cp["gap_extend"], cp["skip"], cp["max_gap"], cp["max_diag"], cp["lookback"])
+    res = (engine.SaChainResult * max(1, n))()
+
+    def call(host: bool):
+        handle = ctypes.c_void_p()
+        head = (ctypes.byref(params), flat.ctypes.data, off.ctypes.data, n)
+        rc = engine.lib.sa_chain_anchors_host(*head, res, ctypes.byref(handle)) if host else engine.lib.sa_chain_anchors(*head, 0, res, ctypes.byref(handle))
+        if rc != 0:
+            raise engine.SaError(rc, engine.lib.sa_last_error().decode())
+        return handle
+
+    def fetch(handle):
+        rows = np.frombuffer(res, dtype=engine.CHAIN_DTYPE, count=n).copy()
+        coff = np.ctypeslib.as_array(ctypes.cast(engine.lib.sa_chain_set_off(handle), ctypes.POINTER(ctypes.c_uint64)), (n + 1,)).copy()
+        addr = engine.lib.sa_chain_set_seeds(handle)
+        seeds = np.ctypeslib.as_array(ctypes.cast(addr, ctypes.POINTER(ctypes.c_uint64)), (int(coff[n]), 3)).copy() if addr else np.zeros((0, 3), np.uint64)
+        engine.lib.sa_chain_set_destroy(handle)
+        return rows, seeds, coff
+    return call, fetch, engine.lib.sa_chain_set_destroy
+
+
+def chaining_rows(args, engine, name: str, anchors, cp: dict) -> dict:
+    """(a) of --mode chaining: sa_chain_anchors end to end (the C call: validation, upload, both kernels, the copies
+    back) with its dp_ms and walk_ms, against sa_chain_anchors_host on the same anchors, alternated round by round."""
+    call, fetch, destroy = chaining_call(engine, anchors, cp)
+    dev, host = fetch(call(False)), fetch(call(True))  # warm-up, and (K2) on the workload
+    assert all((a == b).all() for a, b in zip(dev, host)), "the device chains differ from the host function's"
+    counts = np.array([len(a) for a in anchors])
+    row = {"name": name, "pairs": len(anchors), "params": cp, "anchors_per_pair": round(float(counts.mean()), 1), "anchors_max": int(counts.max()),
+           "seeds_per_pair": round(float(dev[0]["num_seeds"].mean()), 1), "device_equals_host": True}
+    ms = {"device": [], "host": [], "dp": [], "walk": []}
+    for _ in range(args.rounds):
+        for key in ("device", "host"):
+            t0 = time.perf_counter()
+            handle = call(key == "host")
+            ms[key].append((time.perf_counter() - t0) * 1e3)
+            destroy(handle)
+            if key == "device":
+                st = engine.chain_last_stats()
+                ms["dp"].append(st["dp_ms"]), ms["walk"].append(st["walk_ms"])
+                row["device_bytes"] = st["device_bytes"]
+    row.update({"device_end_to_end_wall": stats(ms["device"]), "host_wall": stats(ms["host"]), "dp_kernel": stats(ms["dp"]), "walk_kernel": stats(ms["walk"])})
+    row["device_over_host"] = round(statistics.median(ms["device"]) / statistics.median(ms["host"]), 4)
+    return row
+
+
+def chaining_scores_row(args, engine, w, chained, derived, go: int, ge: int, xdrop, k: int) -> dict:
+    """(b) of --mode chaining: the chains scorer on the chains of sa_chain_anchors and on the alignment-derived ones of
+    exact_match_chains, pair by pair. A pair whose chain is empty is left out of both calls."""
+    keep = [i for i, c in enumerate(chained) if len(c)]
+    pairs = [w["pairs"][i] for i in keep]
+    texts = [w["text"][p[0]:p[0] + p[1]] for p in pairs]
+    pats = [w["pattern"][p[2]:p[2] + p[3]] for p in pairs]
+    x = engine.NO_XDROP if xdrop is None else xdrop
+    a = engine.score_batch(0, texts, pats, w["S"], go, gap_extend=ge, xdrop=x, chains=[chained[i] for i in keep])["score"].astype(np.int64)
+    b = engine.score_batch(0, texts, pats, w["S"], go, gap_extend=ge, xdrop=x, chains=[derived[i] for i in keep])["score"].astype(np.int64)
+    return {"name": f"{w['name']}_chains_scores_k{k}", "pairs": len(keep), "pairs_without_a_chain": len(chained) - len(keep), "gap_open": go, "gap_extend": ge,
+            "xdrop": xdrop, "equal": int((a == b).sum()), "chained_higher": int((a > b).sum()), "chained_lower": int((a < b).sum()),
+            "largest_deficit": int(max(0, (b - a).max())), "largest_surplus": int(max(0, (a - b).max())),
+            "seeds_per_pair_chained": round(float(np.mean([len(chained[i]) for i in keep])), 1),
+            "seeds_per_pair_derived": round(float(np.mean([len(derived[i]) for i in keep])), 1)}
+
+
+def next_profile_dir() -> str:
+    """The next unused profiles/rNN."""
+    taken = [int(d[1:]) for d in os.listdir(os.path.join(ROOT, "profiles")) if d[0] == "r" and d[1:].isdigit()]
+    return f"r{max(taken, default=0) + 1:02d}"
+
+
 def cigar_row(args, engine, name: str, texts, pats, S, go: int, ge: int, kw: dict) -> dict:
     """--mode cigar: align_pairs_affine with strings and align_pairs_cigar on the same pairs and keywords, alternated
     round by round in this process after one warm-up each: wall time end to end (host arrays in, Python dicts out),
@@ -1262,7 +1346,7 @@ def main() -> int:
     ap.add_argument("--exit-gap", type=int, nargs=2, default=[16, 4], metavar=("OPEN", "EXTEND"),
                     help="--mode extend: the penalties of the early-exit comparison")
     ap.add_argument("--xdrop", type=int, default=100, help="--mode extend: the X-drop of the early-exit comparison")
-    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds", "chain", "cigar"], default=None,
+    ap.add_argument("--mode", choices=["fit", "ends", "mapped", "extend", "seeds", "chain", "cigar", "chaining"], default=None,
                     help="fit: the fit scorers against the global and local ones on a read-mapping workload; "
                          "ends: the ends-free scorers against the fit and global ones on it and on an overlap workload; "
                          "mapped: the band-at fit scorer around each read's true offset against the unbanded fit scorer "
@@ -1274,7 +1358,9 @@ def main() -> int:
                          "chain: the chains scorer and aligner on 10000-letter reads against the composition of existing calls "
                          "and against the band-at global scorer (profiles/r22/score_chain_bench.json); "
                          "cigar: align_pairs_cigar against align_pairs_affine with strings on the chain workload (all its reads, "
-                         "and the first 64) and on 4000 reads of the seeds workload (profiles/r23/score_cigar_bench.json)")
+                         "and the first 64) and on 4000 reads of the seeds workload (profiles/r23/score_cigar_bench.json); "
+                         "chaining: sa_chain_anchors against sa_chain_anchors_host on the k-mer anchors of the long reads, and the chains "
+                         "scorer on its chains against the alignment-derived ones (the next unused profiles/rNN/score_chaining_bench.json)")
     ap.add_argument("--band", type=int, nargs="+", default=None,
                     help="half-widths: the banded scorer and aligner against the unbanded ones on related 20000-letter pairs")
     ap.add_argument("--width", type=int, nargs="+", default=None,
@@ -1284,7 +1370,7 @@ def main() -> int:
                     help="take the sa_amd package and its library from this checkout (e.g. one of the parent commit, built)")
     args = ap.parse_args()
     if args.rounds is None:
-        args.rounds = 7 if args.mode in ("extend", "seeds", "chain", "cigar") else 5
+        args.rounds = 7 if args.mode in ("extend", "seeds", "chain", "cigar", "chaining") else 5
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", *(("r14", "score_band_bench.json") if args.band else
                                                     ("r13", "score_fit_bench.json") if args.mode == "fit" else
@@ -1294,6 +1380,7 @@ def main() -> int:
                                                     ("r21", "score_seeds_band_bench.json") if args.mode == "seeds" and args.width else
                                                     ("r22", "score_chain_bench.json") if args.mode == "chain" else
                                                     ("r23", "score_cigar_bench.json") if args.mode == "cigar" else
+                                                    (next_profile_dir(), "score_chaining_bench.json") if args.mode == "chaining" else
                                                     ("r17", "score_extend_bench.json") if args.mode == "extend" else
                                                     ("r18", "score_seeds_bench.json") if args.mode == "seeds" else ("r09", "score_bench.json")))
     if args.tree:
@@ -1409,6 +1496,24 @@ def main() -> int:
         row = cigar_row(args, engine, "mapped_seeds_4000", texts, pats, w["S"], args.gap_open, ge, {"xdrop": x, "seeds": seeds})
         report["workloads"].append(row)
         print(json.dumps(row), flush=True)
+    elif args.mode == "chaining":
+        from sa_amd import synthetic
+        ge = args.gap_extend if args.gap_extend is not None else 2
+        w = chain_workload(args.small)
+        cp = {"match": 5, "gap_open": args.gap_open, "gap_extend": ge, "skip": 0, "max_gap": engine.NO_LIMIT, "max_diag": 500, "lookback": 64}
+        report["conditions"] = {"timing": "time.perf_counter around the C call, device and host alternated round by round in one process",
+                                "library_build_id": engine.lib.sa_build_id().decode(), "host_cpus": os.cpu_count()}
+        derived = exact_match_chains(engine, w, args.gap_open, ge)
+        for k in (11, 15):
+            anchors = [synthetic.kmer_anchors(w["text"][p[0]:p[0] + p[1]], w["pattern"][p[2]:p[2] + p[3]], k) for p in w["pairs"]]
+            for count in (len(anchors), 64):
+                row = chaining_rows(args, engine, f"{w['name']}_k{k}_{count}", anchors[:count], cp)
+                report["workloads"].append(row)
+                print(json.dumps(row), flush=True)
+            _, chained = engine.chain_anchors(anchors, sort=False, **cp)
+            row = chaining_scores_row(args, engine, w, chained, derived, args.gap_open, ge, None, k)
+            report["workloads"].append(row)
+            print(json.dumps(row), flush=True)
     elif args.mode == "ends":
         report["library_build_id"] = engine.lib.sa_build_id().decode()
         for w in (mapping_workload(args.small), overlap_workload(args.small)):
